@@ -11,9 +11,18 @@ across ranks (LPT, no data-path collective).
 A step is one pass of the hot path over the whole genome: one FIR launch per chromosome
 (libgenodsp_hip.so through its C ABI), inputs resident in HBM before the clock starts.
 Rank 0 prints ONE JSON line.  `value` = bases of all ranks / max-over-ranks step time.
-`roofline` is measured live with HIP events on the launch stream; `cpu_baseline` times the
-unmodified reference (oracle/_ref, kind "reference") or, when that build is absent, the
-CPU restatement (kind "port") on this host, rank 0 at N=1 only, on a bounded sample.
+`roofline` is measured live with HIP events on the launch stream.
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  With
+`--full` the same run goes on to what the line carried before: the other two arithmetics
+(`other_modes`), the other split of the genome (N > 1), the parity spot check against the
+CPU oracle, the `sustained` figure, BASELINE configs[2..4] (`workloads`, one rank) and
+`cpu_baseline`, which times the unmodified reference (oracle/_ref, kind "reference") or, when
+that build is absent, the CPU restatement (kind "port") on this host, rank 0 at N=1 only, on
+a bounded sample.
+
+`--dump-outputs DIR` writes, right after the timed steps, a fixed sample of what the timed
+path computed in its last step as DIR/<name>.npy (float64): see dump_outputs().
 """
 import argparse
 import json
@@ -63,16 +72,16 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--mode", choices=["hann", "fma", "exact"], default="hann",
-                    help="arithmetic of the headline number (the other two are reported beside it): hann = block "
+                    help="arithmetic of the headline number (--full reports the other two beside it): hann = block "
                          "sums of the window's constant and cosine parts, fma = direct taps with fused "
                          "multiply-add (both within one rounding per operation of the reference), exact = direct "
                          "taps, bit-identical to the reference")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink every chromosome (debugging only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="leave BASELINE configs[2..4] out of the line (they are timed and checked by default at one rank)")
+                    help="leave BASELINE configs[2..4] out of the --full line (where they are timed and checked at one rank)")
     ap.add_argument("--sustain", type=float, default=3.0,
-                    help="seconds the headline kernel is launched back to back for the `sustained` figure (0 = skip)")
+                    help="seconds the headline kernel is launched back to back for the `sustained` figure of --full (0 = skip)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="debugging: every rank uses GPU 0 and the gloo backend, to exercise the N>1 code path "
                          "where only one GPU exists (numbers from such a run mean nothing)")
@@ -94,7 +103,16 @@ def main():
     ap.add_argument("--workload", choices=["smooth", "peaks", "morph", "percentile"], default="smooth",
                     help="smooth = BASELINE configs[1] (the metric); the others are configs[2..4], "
                          "reported in the same shape for DESIGN.md, never the driver's number")
+    ap.add_argument("--full", action="store_true",
+                    help="smooth: after the headline, also time the other two arithmetics, the other split of the genome "
+                         "(N > 1), the sustained figure, BASELINE configs[2..4] (one rank) and the CPU baselines, and "
+                         "check against the CPU oracle; without it the run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed sample of what the timed path computed in its last step "
+                         "as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # invoked plainly: start one fresh rank per GPU and relay rank 0's JSON line.  Nothing in THIS process has
@@ -210,13 +228,16 @@ def main():
     modes = {"hann": gd.FIR_HANN, "fma": gd.FIR_FMA, "exact": gd.FIR_EXACT}
     wall_ms, dev_ms = timed(modes[args.mode], args.steps, args.warmup)
     ranks_ms = list(per_rank_ms)
-    others = {m: timed(modes[m], max(1, args.steps // 2), 1) for m in modes if m != args.mode}
+    if args.dump_outputs:                            # before anything below writes vout again
+        dump_outputs(args.dump_outputs, [(piece_name(pieces[k], lengths), vout[k], held[k][0], pieces[k][0], pieces[k][2],
+                                          pieces[k][3]) for k in mine])
+    others = {m: timed(modes[m], max(1, args.steps // 2), 1) for m in modes if m != args.mode} if args.full else {}
 
     # ---- with more than one rank, the other split of the genome too, in the same run: equal stretches of the
     #      concatenated genome (makespan efficiency 1.000 by construction; whole chromosomes dealt longest-first reach
     #      0.965 at 8) -- one timed pass, the same arithmetic, so that one run of the driver records both
     other_split = None
-    if world > 1:
+    if world > 1 and args.full:
         alt = "bases" if args.sharding == "chromosomes" else "chromosomes"
         alt_shards = shard_pieces(lengths, world, alt, lpt_shards)
         alt_pieces = list(alt_shards[rank])
@@ -243,7 +264,7 @@ def main():
 
     # ---- parity spot check against the CPU oracle (checker only): sampled windows of the
     #      longest local chromosome, exact mode must be bit-identical, fma within tolerance
-    parity = spot_check(gd, vin, vout, pieces, held, lengths, stream)
+    parity = spot_check(gd, vin, vout, pieces, held, lengths, stream) if args.full else None
 
     def roofline(mode, dev_ms_per_step):
         # per launch: algorithmic bytes = 16 B/base x bases of that launch; averaged over the
@@ -271,7 +292,7 @@ def main():
     # ---- the headline kernel back to back for >= 3 s (HIP events on the launch stream): what the part sustains, beside
     #      the K-step figure the contract asks for (20 steps are 0.16 s; FP64-heavy kernels settle at a lower clock)
     sustained = None
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         sus_steps = max(args.steps, int(np.ceil(args.sustain * 1e3 / max(dev_ms, 1e-3))))
         sus_wall, sus_dev = timed(modes[args.mode], sus_steps, 0)
         sustained = {"kernel": batch_name(KERNELS[args.mode]) if batch else KERNELS[args.mode], "fir_mode": args.mode,
@@ -286,7 +307,7 @@ def main():
     # ---- BASELINE configs[2..4] in the same process, each with its own check against the oracle (one rank: the
     #      scaling runs time the metric only)
     workloads = None
-    if world == 1 and args.sharding == "chromosomes" and not args.no_workloads:
+    if args.full and world == 1 and args.sharding == "chromosomes" and not args.no_workloads:
         workloads = bench_workloads(args, gd, torch, names, mine, lengths, total_bases, vin, vout, stream, timed, lane_of)
 
     result = {
@@ -301,7 +322,7 @@ def main():
         "dtype": "f64",
         "data": "synthetic",
         "config": {"workload": "smooth W=101 on 24-chrom 3.1 Gbp synthetic signal (BASELINE configs[1]); arithmetic of `value`: "
-                               + ARITHMETIC[args.mode] + "; the other two arithmetics are in other_modes",
+                               + ARITHMETIC[args.mode] + "; the other two arithmetics are in other_modes (--full)",
                    "window": WINDOW, "chromosomes": len(GENOME), "bases": total_bases,
                    "fir_mode": args.mode, "library": gd.lib().gdsp_version().decode(),
                    "streams": args.streams, "launch": "one launch per step covers every chromosome of the rank" if batch
@@ -310,19 +331,20 @@ def main():
                                else "equal stretches of the concatenated genome, pieces with a half-window halo",
                    "signal": "read-depth-like x U(0.5,1.5), seed %d" % SEED},
         "roofline": roofline(args.mode, dev_ms),
-        "other_modes": [{"fir_mode": m, "value": round(total_bases / (w * 1e-3) / 1e9, 2),
-                         "ms_per_step": round(w, 4), "roofline": roofline(m, d)} for m, (w, d) in others.items()],
-        "parity": parity,
         "per_rank_ms": ranks_ms,
         "bases_per_rank": [sum(b - a for _, _, a, b in sh) for sh in shards],
     }
+    if args.full:
+        result["other_modes"] = [{"fir_mode": m, "value": round(total_bases / (w * 1e-3) / 1e9, 2),
+                                  "ms_per_step": round(w, 4), "roofline": roofline(m, d)} for m, (w, d) in others.items()]
+        result["parity"] = parity
     if other_split is not None:
         result["other_sharding"] = other_split
     if sustained is not None:
         result["sustained"] = sustained
     if workloads is not None:
         result["workloads"] = workloads
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(gd, lengths, names, stream)
         result["cpu_baseline_all_cores"] = cpu_baseline_all_cores(gd, lengths, names, stream)
     barrier()
@@ -369,6 +391,31 @@ def piece_extent(piece, lengths):
     c, _, a, b = piece
     half = (WINDOW - 1) // 2
     return max(0, a - half), min(lengths[c], b + half)
+
+
+def piece_name(piece, lengths):
+    """chr1 for a whole chromosome, chr1_<first>_<end> for the owned bases of a cut one"""
+    c, _, a, b = piece
+    return GENOME[c][0] if (a, b) == (0, lengths[c]) else "%s_%d_%d" % (GENOME[c][0], a, b)
+
+
+DUMP_SPAN = 4096                 # outputs per stretch of a dump
+DUMP_STRETCHES = 30              # seeded stretches per piece, besides its first and its last
+
+
+def dump_outputs(dirname, vectors):
+    """Write DIR/<name>.npy for each (name, DeviceVector, first base held, chromosome, first owned, end owned): the
+    outputs of the owned bases [a, b) at DUMP_STRETCHES + 2 stretches of DUMP_SPAN bases -- the first, the last and
+    stretches drawn by a generator seeded with (SEED, chromosome, a) -- concatenated in ascending order of their start,
+    float64.  The same arguments give the same positions, so two builds can be compared file by file; 24 whole
+    chromosomes make 24 MB."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, vec, lo, c, a, b in vectors:
+        span = min(DUMP_SPAN, b - a)
+        rng = np.random.default_rng([SEED, c, a])
+        starts = sorted([a, b - span] + [int(s) for s in rng.integers(a, b - span + 1, DUMP_STRETCHES)])
+        got = [vec.buf.download(np.float64, span, vec.offset + 8 * (s - lo)) for s in starts]
+        np.save(os.path.join(dirname, name + ".npy"), np.concatenate(got))
 
 
 def make_workload(gd, torch, dist, args, workload, fir, nofuse, mine, lengths, src, vout, tmp, stream, lane_of,
@@ -520,6 +567,11 @@ def other_workload(args, gd, torch, dist, rank, world, mine, lengths, total_base
     name, bytes_per_base, step, extra, kernels = make_workload(gd, torch, dist, args, args.workload, fir, args.nofuse, mine, lengths,
                                                                vin, vout, tmp, stream, lane_of, reduce_device)
     wall_ms, dev_ms = timed_fn(None, args.steps, args.warmup, step=step)
+    if args.dump_outputs:                            # the chain's result lands in tmp; percentile's value and count beside it
+        dump_outputs(args.dump_outputs, [(GENOME[i][0], tmp[i], 0, i, 0, lengths[i]) for i in mine])
+        if args.workload == "percentile" and rank == 0:
+            for key in ("percentile99", "sampled"):
+                np.save(os.path.join(args.dump_outputs, key + ".npy"), np.array([extra[key]], np.float64))
     moved_per_base = 16 if not args.nofuse else bytes_per_base        # a fused chain moves 8 B in and 8 B out per base in all
     batch = args.launch == "batch"
     result = {"metric": "Gbases/sec on %s over 3.1 Gbp" % name, "value": round(total_bases / (wall_ms * 1e-3) / 1e9, 2),

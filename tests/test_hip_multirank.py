@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,7 @@ def _free_port():
 
 def _bench(ranks, workload, scale, extra=()):
     common = ["bench.py", "--gpus", str(ranks), "--workload", workload, "--scale", str(scale), "--steps", "1",
-              "--warmup", "0", "--no-cpu-baseline", "--sustain", "0.2"] + list(extra)
+              "--warmup", "0", "--full", "--no-cpu-baseline", "--sustain", "0.2"] + list(extra)
     if ranks == 1:
         cmd = [sys.executable] + common
     else:
@@ -142,6 +143,39 @@ def test_default_line_carries_the_other_baseline_configs_and_a_sustained_figure(
     assert got[3]["percentile99"] == got[4]["percentile99"] and got[3]["parity"]["is_the_order_statistic"]
     two = _bench(2, "smooth", 0.02)
     assert "workloads" not in two and "sustained" in two           # the scaling runs time the metric only
+
+
+def test_plain_line_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing that takes runs or checks of its own; --dump-outputs
+    writes the last timed step's outputs, a fixed sample per chromosome, the same in two runs and equal to the
+    oracle's smooth of the regenerated stretches (exact arithmetic)."""
+    from oracle import cpu
+    import bench
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--scale", "0.002", "--steps", "3", "--warmup", "1", "--mode",
+               "exact", "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        got = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1, p.stdout
+        lines.append(json.loads(got[0]))
+        dumps.append({f: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f64"
+    for key in ("other_modes", "parity", "sustained", "workloads", "cpu_baseline", "cpu_baseline_all_cores"):
+        assert key not in line, key
+    assert sorted(dumps[0]) == sorted(n + ".npy" for n, _ in bench.GENOME)
+    lengths = [max(1, int(n * 0.002)) for _, n in bench.GENOME]
+    for c, (name, _) in enumerate(bench.GENOME):
+        a, b = dumps[0][name + ".npy"], dumps[1][name + ".npy"]
+        assert a.dtype == np.float64 and a.tobytes() == b.tobytes()
+        n = lengths[c]
+        span = min(bench.DUMP_SPAN, n)
+        assert a.size == span * (bench.DUMP_STRETCHES + 2)
+        want = cpu.smooth(cpu.synth_coverage(bench.SEED, c, 0, n, 1), bench.WINDOW)
+        assert a[:span].tobytes() == want[:span].tobytes() and a[-span:].tobytes() == want[n - span:].tobytes()
 
 
 def test_three_ranks_share_the_gpu():

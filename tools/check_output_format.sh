@@ -1,8 +1,8 @@
 #!/bin/bash
 # Extract put_u64/put_fixed from the driver and hold them to snprintf (prints bad=0 when every string matches).
 set -e
-T=${TMPDIR:-/tmp}/gdsp_fmt_check
-mkdir -p $T
+T=$(mktemp -d "${TMPDIR:-/tmp}/gdsp_fmt_check.XXXXXX")
+trap 'rm -rf "$T"' EXIT
 python3 - "$T" <<'PY'
 import sys
 src = open("genodsp_amd/host/genodsp_hip.c").read()

@@ -9,7 +9,7 @@ for f in "$@"; do
   touch genodsp_amd/csrc/$src
   if [ "$f" = "plain" ]; then make -C genodsp_amd/csrc HIPFLAGS="$BASE" > /dev/null 2>&1; else make -C genodsp_amd/csrc HIPFLAGS="$BASE -D$f" > /dev/null 2>&1; fi
   out=gpurun_out/ek_$f; rm -rf $out; mkdir -p $out
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 bench.py $args --no-cpu-baseline > $out/log.txt 2>&1 || tail -3 $out/log.txt
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 bench.py $args --full --no-cpu-baseline > $out/log.txt 2>&1 || tail -3 $out/log.txt
   python3 - "$out" "$pat" "$f" <<'PY'
 import csv, glob, sys
 out, pat, tag = sys.argv[1:4]
