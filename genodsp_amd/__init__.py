@@ -264,6 +264,23 @@ def best_extrema(v, W, want_max, out=None, stream=None):
     return out
 
 
+# -------------------------------- slidingpercentile / median (not in the reference) ----
+
+SLIDING_PERCENTILE_MAX_WINDOW = 4095          # GDSP_SLIDING_PERCENTILE_MAX_WINDOW
+
+
+def sliding_percentile(v, W, p_thousandths, out=None, stream=None):
+    """out[i] = the exact p-th percentile (in thousandths of a percent) of v over the window of base i: bestmax's
+    window, truncated at the ends; the k-th smallest with k = gdsp_percentile_rank(bases in the window, p)."""
+    out = out if out is not None else v.like()
+    call("gdsp_sliding_percentile", v.ptr, out.ptr, v.n, int(W), int(p_thousandths), _sp(stream))
+    return out
+
+
+def median(v, W, out=None, stream=None):
+    return sliding_percentile(v, W, 50000, out=out, stream=stream)
+
+
 # ---------------------------------------------------------- morphology.c ----
 
 def split_length(length):
@@ -756,6 +773,10 @@ def local_extrema_batch(vecs, N, want_max, fill, outs=None, stream=None):
 
 def best_extrema_batch(vecs, W, want_max, outs=None, stream=None):
     return _batch("gdsp_best_extrema_batch", vecs, outs, int(W), int(want_max), stream=stream)
+
+
+def sliding_percentile_batch(vecs, W, p_thousandths, outs=None, stream=None):
+    return _batch("gdsp_sliding_percentile_batch", vecs, outs, int(W), int(p_thousandths), stream=stream)
 
 
 def dilate_batch(vecs, left, right, T=0.0, one=1.0, zero=0.0, outs=None, stream=None):

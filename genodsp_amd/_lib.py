@@ -136,6 +136,10 @@ SIGNATURES = {
     "gdsp_erase_batch": (_int, [_vp, _int, _int, _f64, _int, _f64, _int, _f64, _vp]),
     "gdsp_add_constant_batch": (_int, [_vp, _int, _f64, _vp]),
     "gdsp_abs_batch": (_int, [_vp, _int, _vp]),
+    # slidingpercentile / median (not in the reference)
+    "gdsp_sliding_percentile_tile": (_u32, [_u32]),
+    "gdsp_sliding_percentile": (_int, [_vp, _vp, _u32, _u32, _u32, _vp]),
+    "gdsp_sliding_percentile_batch": (_int, [_vp, _int, _u32, _u32, _vp]),
 }
 
 # functions whose int return is a status code

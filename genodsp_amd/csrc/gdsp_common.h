@@ -252,6 +252,15 @@ __device__ __forceinline__ void gdsp_stage_f64 (double* lds, const double* __res
 		}
 	}
 
+// the reference's rank rule, percentile.c:587-589 / :681 and :688-710: k = (u32) ((u64) numValues * pt / (100.0*1000)),
+// a rank equal to numValues meaning the largest value (gdsp_percentile_rank, the percentile kernels, slidingpercentile)
+__host__ __device__ __forceinline__ uint32_t gdsp_rank_of (uint32_t numValues, uint32_t pThousandths)
+	{
+	uint32_t k = (uint32_t) (((uint64_t) numValues) * pThousandths / (100.0*1000));
+	if ((numValues != 0) && (k >= numValues)) k = numValues - 1;
+	return k;
+	}
+
 // order-preserving image of a double (radix select): -0.0 folded onto +0.0
 __host__ __device__ __forceinline__ uint64_t gdsp_key_of (double v)
 	{

@@ -683,10 +683,7 @@ void pc_pick_kernel (unsigned long long* __restrict__ hist, int shift, int bits,
 // old way.
 __device__ __forceinline__ uint32_t pc_res_rank (uint64_t N, uint32_t pThousandths)     // gdsp_percentile_rank (percentile.c:587-589, :688-710)
 	{
-	const uint32_t numValues = (uint32_t) N;
-	uint32_t k = (uint32_t) (((uint64_t) numValues) * pThousandths / (100.0*1000));
-	if ((numValues != 0) && (k >= numValues)) k = numValues - 1;
-	return k;
+	return gdsp_rank_of ((uint32_t) N, pThousandths);
 	}
 
 // one digit of a select over a list of keys.  stage SAMPLE: the subsample, ranks either side of percentile `which`'s

@@ -236,11 +236,6 @@ uint64_t gdsp_double_to_key (double v)     { return gdsp_key_of (v); }
 
 // percentile.c:587-589 / :681:  k = (u32) ((u64) numValues * pt / (100.0*1000)),
 // and a rank equal to numValues means the largest value (:688-710)
-uint32_t gdsp_percentile_rank (uint32_t numValues, uint32_t pThousandths)
-	{
-	uint32_t k = (uint32_t) (((uint64_t) numValues) * pThousandths / (100.0*1000));
-	if ((numValues != 0) && (k >= numValues)) k = numValues - 1;
-	return k;
-	}
+uint32_t gdsp_percentile_rank (uint32_t numValues, uint32_t pThousandths) { return gdsp_rank_of (numValues, pThousandths); }
 
 } // extern "C"

@@ -37,7 +37,8 @@
 
 /* ------------------------------------------------------------ operator table */
 /* same names, aliases and order as the reference's dspTable (genodsp.c:117-174): all 37
- * operators.  As in the reference a "plugin" is a link-time function group: a further group
+ * operators, then (with GDSP_RANK_FILTER, as the Makefile builds it) slidingpercentile and median, which the
+ * reference does not have.  As in the reference a "plugin" is a link-time function group: a further group
  * is added by compiling the driver with -DGDSP_EXTRA_OPERATORS='"my_ops.h"', a header that
  * declares the groups (dspprototypes) and defines GDSP_EXTRA_DSPTABLE_ROWS as the rows to append
  * (dspinforecord("name", op_x), ...), and by linking the group's object file (INTEGRATION.md;
@@ -55,6 +56,9 @@ dspprototypes(op_mask)           dspprototypes(op_mask_not)      dspprototypes(o
 dspprototypes(op_and)            dspprototypes(op_min_with)      dspprototypes(op_max_with)
 dspprototypes(op_map)            dspprototypes(op_min_in_interval) dspprototypes(op_max_in_interval)
 dspprototypes(op_clump)          dspprototypes(op_skimp)
+#ifdef GDSP_RANK_FILTER                                /* not in the reference: ops_rankfilt.c */
+dspprototypes(op_sliding_percentile) dspprototypes(op_sliding_median)
+#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
@@ -99,6 +103,10 @@ static dspinfo dspTable[] =
 	 dspinforecord("input"         , op_input)          ,
 	 dspinforecord("output"        , op_output)         ,
 	 dspinforecord("variables"     , op_show_variables)
+#ifdef GDSP_RANK_FILTER                                /* windowed order statistics, after the reference's 37 */
+	 , dspinforecord("slidingpercentile", op_sliding_percentile), dspinfoalias ("sliding_percentile"),
+	 dspinforecord("median"        , op_sliding_median) , dspinfoalias ("slidingmedian")  , dspinfoalias ("sliding_median")
+#endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS
 #endif

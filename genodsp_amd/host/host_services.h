@@ -71,6 +71,13 @@ const char* op_binarize_pending (dspop* op, int* tiesAbove, valtype* one, valtyp
  * operator after it is that binarize, the binarize with it; returns how many operators ran (1 or 2) */
 int   percentile_with_binarize (dspop* percentile, dspop* next);
 
+/* ops_percentile.c: a percentile as given on the command line -> thousandths of a percent (0 .. 100000) */
+u32   to_thousandths      (valtype pct);
+/* ops_rankfilt.c (slidingpercentile, median; compiled in with -DGDSP_RANK_FILTER): what ops_fused.c needs to know */
+int   op_rankfilt_is      (dspop* op);
+u32   op_rankfilt_window  (dspop* op);
+int   op_rankfilt_batch   (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
+
 /* argument helpers used by every operator's parse function */
 #define OP_SHORT(fn, text)                                                            \
 void fn##_short (char* name, int nameWidth, FILE* f, char* indent)                    \

@@ -34,6 +34,10 @@ int op_reach (dspop* op, u32* left, u32* right)
 	if ((f == op_binarize_apply) || (f == op_clip_apply) || (f == op_erase_apply) || (f == op_add_constant_apply)
 	 || (f == op_absolute_value_apply) || (f == op_map_apply))
 		return true;
+#ifdef GDSP_RANK_FILTER
+	if (op_rankfilt_is (op))                               /* bestmax's window: [i-wL, i+wR] */
+		{ u32 W = op_rankfilt_window (op);  *left = (W - 1) / 2;  *right = W - 1 - *left;  return true; }
+#endif
 	return false;                                          /* sum, slidingsum, cumulativesum, clump, anticlump, plugins */
 	}
 
@@ -81,6 +85,9 @@ int try_fused_apply (dspop* op, dspop* stopOp, spec* s)
 int op_batchable (dspop* op)
 	{
 	opfunc_apply f = op->funcApply;
+#ifdef GDSP_RANK_FILTER
+	if (op_rankfilt_is (op)) return true;
+#endif
 	return (f == op_smooth_apply) || (f == op_local_maxima_apply) || (f == op_local_minima_apply)
 	    || (f == op_best_local_max_apply) || (f == op_best_local_min_apply)
 	    || (f == op_dilate_apply) || (f == op_erode_apply)
@@ -154,6 +161,10 @@ int batch_apply_on_device (dspop* op, dspop* stopOp, spec** units, int nunits, i
 			if (rc == GDSP_EINVAL) goto one_by_one;            /* reach beyond one LDS tile */
 			}
 		}
+#ifdef GDSP_RANK_FILTER
+	else if (op_rankfilt_is (op))
+		rc = op_rankfilt_batch (op, items, nunits, st);       /* (windows above the maximum were refused at parse time) */
+#endif
 	else
 		{
 		outOfPlace = false;

@@ -55,7 +55,7 @@ void op_percentile_usage (char* name, FILE* f, char* indent)
 	fprintf (f, "%s                           the signal is simply left as it is\n", indent);
 	}
 
-static u32 to_thousandths (valtype pct)           /* percentile.c:296-302 */
+u32 to_thousandths (valtype pct)                  /* percentile.c:296-302 */
 	{
 	if (pct <   0.0) return 0;
 	if (pct > 100.0) return 100*percentileStepUnits;

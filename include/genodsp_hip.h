@@ -201,6 +201,23 @@ int gdsp_abs_batch                  (const gdsp_batch_item* items, int nitems, v
 /* GDSP_EINVAL from a *_batch call whose parameters the single-vector call would also refuse, or for which no tiled
  * kernel exists (the caller then loops over the vectors with the single-vector / *_any forms). */
 
+/* ---- slidingpercentile / median (not in the reference): exact order statistics over a sliding window ------------
+ * For a vector v of n values, a window W (1 <= W <= GDSP_SLIDING_PERCENTILE_MAX_WINDOW) and P in thousandths of a
+ * percent (0..100000): wL = (W-1)/2, wR = W-1-wL (bestmax's centring: for even W the extra base is on the right).
+ * The window of base i is [max(0, i-wL), min(n-1, i+wR)]: bases beyond the ends are not considered, as in bestmax;
+ * n_i is the number of bases in it and k_i = gdsp_percentile_rank(n_i, P).  out[i] is gdsp_key_to_double of the
+ * k_i-th smallest (from 0) of the keys gdsp_double_to_key(v[j]) over the window: the order `percentile` uses, -0.0
+ * folded onto +0.0 (printed as 0), NaNs ordered by their bits (positive NaNs above +inf, negative ones below -inf).
+ * The result is an input value, bit exact.  P = 0 and P = 100000 are bestmin and bestmax (on data without -0.0 and
+ * NaN).  Out-of-place; GDSP_EINVAL for d_in == d_out, W == 0, W above the maximum or P > 100000; n == 0 is a no-op.
+ * One kernel launch covers every vector of a batch (gdsp_rankfilt.hip: per tile a sort and a wavelet matrix in LDS,
+ * then one range-quantile query per base; the cost per base does not grow with W). */
+#define GDSP_SLIDING_PERCENTILE_MAX_WINDOW 4095
+/* Host: outputs per workgroup tile of the kernel for window W (0 outside 1..the maximum); results never depend on it */
+uint32_t gdsp_sliding_percentile_tile (uint32_t W);
+int gdsp_sliding_percentile       (const double* d_in, double* d_out, uint32_t n, uint32_t W, uint32_t pThousandths, void* stream);
+int gdsp_sliding_percentile_batch (const gdsp_batch_item* items, int nitems, uint32_t W, uint32_t pThousandths, void* stream);
+
 /* ---- logical.c, mask.c, add.c (in place) ---------------------------------------- */
 int gdsp_binarize     (double* d_v, uint32_t n, double T, int tiesAbove, double one, double zero,
                        void* stream);                                 /* logical.c:216-268 */
