@@ -543,6 +543,153 @@ def percentile(vecs, p_thousandths, window=1, lo=-DBL_MAX, hi=DBL_MAX, allreduce
     return int(count.value), [float(x) for x in vals]
 
 
+# ------------------------------------------------ stats / normalize (not in the reference) ----
+
+XSUM_WORDS, XSUM_DIGITS = 72, 68                   # GDSP_XSUM_WORDS, GDSP_XSUM_DIGITS
+XSUM_WORD_COUNT, XSUM_WORD_INF, XSUM_WORD_FLUSHES = 68, 69, 70
+
+
+class XsumSource(C.Structure):
+    """gdsp_xsum_source of include/genodsp_hip.h"""
+    _fields_ = [("d_v", C.c_void_p), ("n", C.c_uint32), ("first", C.c_uint32), ("device", C.c_int), ("stream", C.c_void_p)]
+
+
+def xsum_sources(vecs, stream=None):
+    """The source table of gdsp_genome_stats / gdsp_xsum_*: each item a DeviceVector (a whole chromosome), or a tuple
+    (vector, start, count[, first]) for values [start, start+count) of the vector whose chromosome position is `first`
+    (default: start) -- the window counts from the chromosome's first base."""
+    device = current_device()
+    src = (XsumSource * max(1, len(vecs)))()
+    for i, item in enumerate(vecs):
+        if isinstance(item, DeviceVector):
+            v, start, count, first = item, 0, item.n, 0
+        else:
+            v, start, count = item[0], int(item[1]), int(item[2])
+            first = int(item[3]) if len(item) > 3 else start
+        assert 0 <= start and start + count <= v.n
+        src[i].d_v, src[i].n, src[i].first = v.ptr.value + 8 * start, count, first
+        src[i].device, src[i].stream = device, stream
+    return src
+
+
+def genome_stats(vecs, window=1, lo=-DBL_MAX, hi=DBL_MAX, allreduce=None, stream=None):
+    """count, sum, mean, variance, stddev of the sampled genome, each exact and rounded once (gdsp_genome_stats): every
+    window-th value counted from each chromosome's first base with lo <= v <= hi (never NaN or +-inf).  vecs: as
+    xsum_sources.  allreduce(np.uint64 array, "sum") -> the array summed over ranks (None: one rank), percentile's hook.
+    count 0: sum 0.0 and the rest NaN."""
+    src = xsum_sources(vecs, stream)
+    out = (C.c_double * 5)()
+    failure = []
+
+    def reduce(_ctx, words, n, op):
+        try:
+            arr = np.ctypeslib.as_array(words, shape=(n,))
+            arr[:] = allreduce(arr.copy(), ("sum", "min", "max")[op])
+            return 0
+        except Exception as e:           # an exception must not unwind through the C frames
+            failure.append(e)
+            return 1
+
+    cb = REDUCE_FN(reduce) if allreduce is not None else C.cast(None, REDUCE_FN)
+    try:
+        call("gdsp_genome_stats", src, len(vecs), int(window), float(lo), float(hi), cb, None, out)
+    except GdspError:
+        if failure:
+            raise failure[0]
+        raise
+    return dict(zip(("count", "sum", "mean", "variance", "stddev"), [float(x) for x in out]))
+
+
+def genome_stats_last():
+    """What the last genome_stats did: n, lane flushes into LDS in pass 1 and pass 2, squares that were +inf."""
+    out = (C.c_uint64 * 4)()
+    lib().gdsp_genome_stats_last(out)
+    return dict(zip(("count", "flushes1", "flushes2", "inf_squares"), [int(x) for x in out]))
+
+
+def xsum_accumulate(vecs, acc, window=1, lo=-DBL_MAX, hi=DBL_MAX, mean=None, stream=None):
+    """One pass into the accumulator `acc` (a DeviceBuffer of XSUM_WORDS u64 words): v, or fl(fl(v - mean)^2) when mean
+    is given.  The image is not folded."""
+    src = xsum_sources(vecs, stream)
+    if mean is None:
+        call("gdsp_xsum_accumulate_batch", src, len(vecs), int(window), float(lo), float(hi), C.c_void_p(acc.ptr), _sp(stream))
+    else:
+        call("gdsp_xsum_accumulate_sq_batch", src, len(vecs), int(window), float(lo), float(hi), float(mean),
+             C.c_void_p(acc.ptr), _sp(stream))
+
+
+def xsum_image(vecs, window=1, lo=-DBL_MAX, hi=DBL_MAX, mean=None, stream=None, fold=True):
+    """The (folded) accumulator image of one pass over vecs, as np.uint64[XSUM_WORDS]."""
+    acc = DeviceBuffer(XSUM_WORDS * 8)
+    call("gdsp_xsum_init", C.c_void_p(acc.ptr), _sp(stream))
+    xsum_accumulate(vecs, acc, window, lo, hi, mean, stream)
+    if fold:
+        call("gdsp_xsum_fold", C.c_void_p(acc.ptr), _sp(stream))
+    return acc.download(np.uint64, XSUM_WORDS, stream=stream)
+
+
+def xsum_round(image):
+    """Host, no GPU: the value of an image rounded once."""
+    img = np.ascontiguousarray(image, dtype=np.uint64)
+    assert img.size == XSUM_WORDS
+    return lib().gdsp_xsum_round(img.ctypes.data_as(C.c_void_p))
+
+
+def xsum_div_round(image, n):
+    """Host, no GPU: the value of an image divided by n, rounded once."""
+    img = np.ascontiguousarray(image, dtype=np.uint64)
+    assert img.size == XSUM_WORDS
+    return lib().gdsp_xsum_div_round(img.ctypes.data_as(C.c_void_p), int(n))
+
+
+def xsum_add_host(image, x):
+    """Host, no GPU: add x to an image (np.uint64[XSUM_WORDS], in place) and 1 to its count."""
+    assert image.dtype == np.uint64 and image.flags.c_contiguous and image.size == XSUM_WORDS
+    lib().gdsp_xsum_add_host(image.ctypes.data_as(C.c_void_p), float(x))
+    return image
+
+
+def _each(name, vecs, *params, stream=None):
+    if isinstance(vecs, DeviceVector):
+        call(name, vecs.ptr, vecs.n, *params, _sp(stream))
+        return vecs
+    return _batch(name + "_batch", vecs, None, *params, stream=stream, in_place=True)
+
+
+def multiply_constant(vecs, c, stream=None):
+    """v = fl(v * c) in place, for one DeviceVector or a list of them (one launch per 32)."""
+    return _each("gdsp_multiply_constant", vecs, float(c), stream=stream)
+
+
+def divide_constant(vecs, c, stream=None):
+    """v = fl(v / c) in place; c == 0 is refused."""
+    return _each("gdsp_divide_constant", vecs, float(c), stream=stream)
+
+
+def standardize(vecs, center, scale, stream=None):
+    """v = fl(fl(v - center) / scale) in place; scale == 0 is refused."""
+    return _each("gdsp_standardize", vecs, float(center), float(scale), stream=stream)
+
+
+def normalize(vecs, to="mean", window=1, lo=-DBL_MAX, hi=DBL_MAX, allreduce=None, stream=None):
+    """The driver's `normalize`: the genome's figures (genome_stats over the sample), then every base of every vector
+    rewritten -- to="mean": fl(v / mean); to="zscore": fl(fl(v - mean) / stddev).  Refused (ValueError, nothing
+    written) when the sample is empty or the divisor is 0 or not finite.  vecs: DeviceVectors.  Returns the figures."""
+    if to not in ("mean", "zscore"):
+        raise ValueError("normalize: unknown --to=%s (mean or zscore)" % to)
+    st = genome_stats(vecs, window, lo, hi, allreduce, stream)
+    if st["count"] == 0:
+        raise ValueError("normalize: no values meet the criteria")
+    div = st["mean"] if to == "mean" else st["stddev"]
+    if not (div != 0 and abs(div) <= DBL_MAX):
+        raise ValueError("normalize: the %s is %r" % ("mean" if to == "mean" else "standard deviation", div))
+    if to == "mean":
+        divide_constant(list(vecs), div, stream=stream)
+    else:
+        standardize(list(vecs), st["mean"], div, stream=stream)
+    return st
+
+
 class Comm:
     """RCCL communicator over devices of this process (gdsp_comm_create: ncclCommInitAll)."""
 

@@ -140,6 +140,23 @@ SIGNATURES = {
     "gdsp_sliding_percentile_tile": (_u32, [_u32]),
     "gdsp_sliding_percentile": (_int, [_vp, _vp, _u32, _u32, _u32, _vp]),
     "gdsp_sliding_percentile_batch": (_int, [_vp, _int, _u32, _u32, _vp]),
+    # stats / normalize / multiplyconst / divideconst (not in the reference)
+    "gdsp_xsum_init": (_int, [_vp, _vp]),
+    "gdsp_xsum_accumulate_batch": (_int, [_vp, _int, _u32, _f64, _f64, _vp, _vp]),
+    "gdsp_xsum_accumulate_sq_batch": (_int, [_vp, _int, _u32, _f64, _f64, _f64, _vp, _vp]),
+    "gdsp_xsum_fold": (_int, [_vp, _vp]),
+    "gdsp_xsum_add_host": (None, [_vp, _f64]),
+    "gdsp_xsum_round": (_f64, [_vp]),
+    "gdsp_xsum_div_round": (_f64, [_vp, _u64]),
+    "gdsp_genome_stats": (_int, [_vp, _int, _u32, _f64, _f64, _vp, _vp, _vp]),
+    "gdsp_genome_stats_use_comm": (_int, [_vp]),
+    "gdsp_genome_stats_last": (None, [_vp]),
+    "gdsp_multiply_constant": (_int, [_vp, _u32, _f64, _vp]),
+    "gdsp_divide_constant": (_int, [_vp, _u32, _f64, _vp]),
+    "gdsp_standardize": (_int, [_vp, _u32, _f64, _f64, _vp]),
+    "gdsp_multiply_constant_batch": (_int, [_vp, _int, _f64, _vp]),
+    "gdsp_divide_constant_batch": (_int, [_vp, _int, _f64, _vp]),
+    "gdsp_standardize_batch": (_int, [_vp, _int, _f64, _f64, _vp]),
 }
 
 # functions whose int return is a status code

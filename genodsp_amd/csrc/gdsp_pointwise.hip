@@ -106,6 +106,10 @@ struct AddConst { double c;       __device__ double operator() (double x) const 
 struct AbsVal   {                 __device__ double operator() (double x) const { return (x < 0)? -x : x; } }; // add.c:1046-1047
 struct Invert   { double twoMid;  __device__ double operator() (double x) const { return twoMid - x; } };      // add.c:935-936
 struct FillVal  { double c;       __device__ double operator() (double)   const { return c; } };
+// multiplyconst, divideconst, normalize (not in the reference): one rounding each, never contracted
+struct MulConst { double c;       __device__ double operator() (double x) const { return __dmul_rn (x, c); } };
+struct DivConst { double c;       __device__ double operator() (double x) const { return __ddiv_rn (x, c); } };
+struct Standardize { double m, s; __device__ double operator() (double x) const { return __ddiv_rn (__dsub_rn (x, m), s); } };
 
 // ---------------------------------------------------------------- reduction ----
 // d_minmax[0] = min, [1] = max, [2] = count of the sampled values (every window-th
@@ -380,6 +384,36 @@ int gdsp_add_constant (double* d_v, uint32_t n, double c, void* stream)
 
 int gdsp_abs (double* d_v, uint32_t n, void* stream)
 	{ return pointwise_launch (d_v, n, AbsVal {}, stream); }
+
+int gdsp_multiply_constant (double* d_v, uint32_t n, double c, void* stream)
+	{ return pointwise_launch (d_v, n, MulConst {c}, stream); }
+
+int gdsp_divide_constant (double* d_v, uint32_t n, double c, void* stream)
+	{
+	GDSP_REQUIRE (c != 0.0, "division by zero");
+	return pointwise_launch (d_v, n, DivConst {c}, stream);
+	}
+
+int gdsp_standardize (double* d_v, uint32_t n, double center, double scale, void* stream)
+	{
+	GDSP_REQUIRE (scale != 0.0, "division by zero");
+	return pointwise_launch (d_v, n, Standardize {center, scale}, stream);
+	}
+
+int gdsp_multiply_constant_batch (const gdsp_batch_item* items, int nitems, double c, void* stream)
+	{ return pointwise_batch_launch (items, nitems, MulConst {c}, stream); }
+
+int gdsp_divide_constant_batch (const gdsp_batch_item* items, int nitems, double c, void* stream)
+	{
+	GDSP_REQUIRE (c != 0.0, "division by zero");
+	return pointwise_batch_launch (items, nitems, DivConst {c}, stream);
+	}
+
+int gdsp_standardize_batch (const gdsp_batch_item* items, int nitems, double center, double scale, void* stream)
+	{
+	GDSP_REQUIRE (scale != 0.0, "division by zero");
+	return pointwise_batch_launch (items, nitems, Standardize {center, scale}, stream);
+	}
 
 int gdsp_invert (double* d_v, uint32_t n, double mid, void* stream)
 	{ return pointwise_launch (d_v, n, Invert {2*mid}, stream); }

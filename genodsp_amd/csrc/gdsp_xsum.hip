@@ -1,0 +1,496 @@
+// gdsp_xsum.hip -- genome-wide stats (`stats`, `normalize`; not in the reference): the exact sum of the sampled genome
+// and the exact sum of the squared deviations from its mean, each rounded once, on the host, at the end.
+//
+// The accumulator is an integer image of GDSP_XSUM_WORDS u64 words (include/genodsp_hip.h): digit k holds a signed
+// multiple of 2^(32k-1074), so every finite double is a sum of three digits and the image spans 2^-1074 .. 2^1102.
+// Integer words add associatively: the image of a genome is the same whatever the order, the cut into vectors, stretches,
+// devices or ranks, the grid or the dispatch order -- the u64 SUM of the images is the image of the union.
+//
+// The pass (xsum_kernel): one read of the signal over every vector of a table of up to 32 (the batch convention of
+// gdsp_common.h; 16-byte loads of 32 KiB tiles, a grid of at most XS_MAX_BLOCKS workgroups walking the tiles).  Each lane
+// keeps two floating-point expansions of XS_K terms in registers, grown with TwoSum (ExBLAS): a summand enters term 0,
+// the rounding error term 1, and so on.  Only a residual that is still non-zero after the last term -- or a summand whose
+// TwoSum would overflow -- is deposited into the workgroup's image in LDS (ds_add_u64).  On read depth and on N(0,10^2)
+// values that almost never happens (GDSP_XSUM_WORD_FLUSHES counts it); adversarial data stays exact and gets slower.
+// At the end the lanes' expansions are added up a tree per wave (a lane takes the terms of the lane `off` above it:
+// each term is added once), lane 0 deposits its terms, one lane carries the LDS image into canonical digits and the
+// workgroup adds its non-zero words to the device image with integer atomics -- the fold of the workgroups' images, in
+// no particular order because integer addition has none.  gdsp_xsum_fold canonicalises the device image (a second, tiny
+// launch), so that images can be compared word for word and all-reduced with room to spare.
+//
+// Pass 2 is the same kernel with q = fl(fl(v - mean)^2) as the summand (__dsub_rn / __dmul_rn: never contracted); a q
+// of +inf is counted in GDSP_XSUM_WORD_INF instead of being added.  Rounding (gdsp_xsum_round, gdsp_xsum_div_round) is
+// host code that needs no GPU.
+
+#include <float.h>
+#include <math.h>
+#include <string.h>
+#include <vector>
+#include <algorithm>
+#include "gdsp_common.h"
+
+#define XS_THREADS    256
+#define XS_UNROLL     8                               // 16-byte loads in flight per lane
+#define XS_TILE       (XS_THREADS * XS_UNROLL * 2)    // 4096 values = 32 KiB
+#define XS_MAX_BLOCKS (256 * 4)                 // every workgroup resident (5 fit on a CU): equal shares finish together
+#define XS_K          2                               // terms of a lane's expansion
+#define XS_D          GDSP_XSUM_DIGITS
+
+static_assert (GDSP_XSUM_WORDS == 72 && XS_D == 68, "the layout below");
+
+// one launch's table: source s is base[s][lead[s] .. lead[s]+n[s]), base 16-byte aligned; its sampled values are those
+// of index i >= phase[s] with (i - phase[s]) % window == 0 (phase: the first index whose chromosome position is a
+// multiple of the window); it owns the tiles [tile0[s], tile0[s+1]) of the frame that starts at base
+struct XsBatch
+	{
+	const double* base[GDSP_BATCH_MAX];
+	uint32_t      n[GDSP_BATCH_MAX];
+	uint32_t      lead[GDSP_BATCH_MAX];
+	uint32_t      phase[GDSP_BATCH_MAX];
+	uint32_t      tile0[GDSP_BATCH_MAX + 1];
+	uint32_t      nvec;
+	};
+
+// a finite double as three signed digits at word w: x = (c0 + c1 2^32 + c2 2^64) 2^(32w-1074), each |c| < 2^32
+__host__ __device__ __forceinline__ void xs_split (double x, uint32_t& w, uint64_t& c0, uint64_t& c1, uint64_t& c2)
+	{
+	union { double d; uint64_t u; } b;
+	b.d = x;
+	const uint32_t be = (uint32_t) (b.u >> 52) & 0x7FF;
+	uint64_t mant = b.u & 0xFFFFFFFFFFFFFull;
+	uint32_t shift = 0;                                    // weight of mant's lowest bit: 2^(shift-1074)
+	if (be != 0) { mant |= 1ull << 52;  shift = be - 1; }
+	w = shift >> 5;
+	const uint32_t r  = shift & 31;
+	const uint64_t lo = mant << r;
+	const uint64_t hi = (r == 0)? 0 : (mant >> (64 - r));
+	c0 = lo & 0xFFFFFFFFull;  c1 = lo >> 32;  c2 = hi;
+	if (b.u >> 63) { c0 = 0 - c0;  c1 = 0 - c1;  c2 = 0 - c2; }     // two's complement: the words add as signed integers
+	}
+
+__device__ __forceinline__ void xs_deposit (unsigned long long* acc, double x)
+	{
+	uint32_t w;  uint64_t c0, c1, c2;
+	xs_split (x, w, c0, c1, c2);
+	if (c0 != 0) atomicAdd (&acc[w],     (unsigned long long) c0);
+	if (c1 != 0) atomicAdd (&acc[w + 1], (unsigned long long) c1);
+	if (c2 != 0) atomicAdd (&acc[w + 2], (unsigned long long) c2);
+	}
+
+__device__ __forceinline__ bool xs_finite (double x) { return fabs (x) <= DBL_MAX; }
+
+// a[] += x exactly, the careful way: TwoSum through the terms; what is left after the last one (or a summand whose TwoSum
+// overflows, which then leaves the term it met unchanged) goes to the LDS image
+__device__ __forceinline__ void xs_grow_careful (double (&a)[XS_K], double x, unsigned long long* acc)
+	{
+	double spill = 0.0;
+#pragma unroll
+	for (int k=0 ; k<XS_K ; k++)
+		{
+		const double s  = __dadd_rn (a[k], x);
+		const double bp = __dsub_rn (s, a[k]);
+		const double e  = __dadd_rn (__dsub_rn (a[k], __dsub_rn (s, bp)), __dsub_rn (x, bp));
+		const bool   ok = xs_finite (s) && xs_finite (e);   // an overflow anywhere leaves +-inf or NaN in s or e
+		a[k]  = ok? s : a[k];
+		spill = ok? spill : x;
+		x     = ok? e : 0.0;
+		}
+	if ((x != 0.0) || (spill != 0.0))
+		{
+		xs_deposit (acc, x);
+		xs_deposit (acc, spill);
+		atomicAdd (&acc[GDSP_XSUM_WORD_FLUSHES], 1ull);
+		}
+	}
+
+// a[] += x exactly.  The fast path runs the TwoSums unchecked: an overflow in any of them leaves NaN in the final
+// residual, so a residual that is not exactly zero -- a real one, or that NaN -- sends the lane back to the terms it
+// had and through the careful form (rare on real data; a branch the other lanes skip)
+__device__ __forceinline__ void xs_grow (double (&a)[XS_K], double x, unsigned long long* acc)
+	{
+	double keep[XS_K], r = x;
+#pragma unroll
+	for (int k=0 ; k<XS_K ; k++)
+		{
+		keep[k] = a[k];
+		const double s  = __dadd_rn (a[k], r);
+		const double bp = __dsub_rn (s, a[k]);
+		r    = __dadd_rn (__dsub_rn (a[k], __dsub_rn (s, bp)), __dsub_rn (r, bp));
+		a[k] = s;
+		}
+	if (r != 0.0)
+		{
+#pragma unroll
+		for (int k=0 ; k<XS_K ; k++) a[k] = keep[k];
+		xs_grow_careful (a, x, acc);
+		}
+	}
+
+// PASS 1 adds v, PASS 2 adds fl(fl(v - mean)^2); WINDOWED: the window is above 1
+template <int PASS, bool WINDOWED>
+__global__ __launch_bounds__(XS_THREADS)
+void xsum_kernel (XsBatch B, uint32_t window, double lo, double hi, double mean, unsigned long long* __restrict__ d_acc)
+	{
+	__shared__ unsigned long long acc[GDSP_XSUM_WORDS];
+	for (int i=threadIdx.x ; i<GDSP_XSUM_WORDS ; i+=XS_THREADS) acc[i] = 0;
+	__syncthreads ();
+
+	double   ax[XS_K], ay[XS_K];
+#pragma unroll
+	for (int k=0 ; k<XS_K ; k++) { ax[k] = 0.0;  ay[k] = 0.0; }
+	uint32_t cnt = 0, infs = 0;
+	auto take = [&] (double (&a)[XS_K], double x, bool sampled)
+		{
+		const bool in = sampled && !(x < lo) && !(x > hi) && xs_finite (x);   // percentile's tests; NaN and +-inf never
+		double t = x;
+		if (PASS == 2) { const double d = __dsub_rn (x, mean);  t = __dmul_rn (d, d); }
+		const bool big = (PASS == 2) && in && !xs_finite (t);                  // q = +inf
+		cnt  += in;
+		infs += big;
+		xs_grow (a, (in && !big)? t : 0.0, acc);
+		};
+
+	const uint32_t T = B.tile0[B.nvec];
+	uint32_t v = 0;
+	for (uint32_t g=blockIdx.x ; g<T ; g+=gridDim.x)
+		{
+		while (B.tile0[v + 1] <= g) v++;
+		const double*  base  = B.base[v];
+		const uint32_t lead  = B.lead[v], phase = B.phase[v];
+		const uint64_t m     = (uint64_t) B.n[v] + lead;              // values of the frame
+		const uint64_t j0    = (uint64_t) (g - B.tile0[v]) * XS_TILE;
+		auto sampled = [&] (uint64_t j) -> bool                        // frame index j is source index j - lead
+			{
+			if (j < lead) return false;
+			if (!WINDOWED) return true;
+			const uint32_t i = (uint32_t) (j - lead);
+			return (i >= phase) && ((i - phase) % window == 0);
+			};
+		if (j0 + XS_TILE <= m)
+			{
+			const double2* p = reinterpret_cast<const double2*> (base + j0) + threadIdx.x;
+			double2 d[XS_UNROLL];
+#pragma unroll
+			for (int u=0 ; u<XS_UNROLL ; u++) d[u] = gdsp_ld2 (&p[u*XS_THREADS]);
+#pragma unroll
+			for (int u=0 ; u<XS_UNROLL ; u++)
+				{
+				const uint64_t j = j0 + 2 * ((uint64_t) u*XS_THREADS + threadIdx.x);
+				take (ax, d[u].x, sampled (j));
+				take (ay, d[u].y, sampled (j + 1));
+				}
+			}
+		else
+			{
+			for (uint64_t j = j0 + threadIdx.x ; j < m ; j += XS_THREADS) take (ax, base[j], sampled (j));
+			}
+		}
+
+	// the lane's two expansions, then the wave's 64 as a tree: lane l takes lane l+off's terms when l % 2off == 0
+#pragma unroll
+	for (int k=0 ; k<XS_K ; k++) xs_grow (ax, ay[k], acc);
+	const int lane = threadIdx.x & 63;
+	for (int off=1 ; off<64 ; off<<=1)
+		{
+		double t[XS_K];
+#pragma unroll
+		for (int k=0 ; k<XS_K ; k++) t[k] = __shfl_down (ax[k], off, 64);
+		const bool mine = (lane & (2*off - 1)) == 0;
+#pragma unroll
+		for (int k=0 ; k<XS_K ; k++) xs_grow (ax, mine? t[k] : 0.0, acc);
+		}
+	uint64_t c = cnt, f = infs;
+	for (int off=32 ; off>0 ; off>>=1) { c += __shfl_down (c, off, 64);  f += __shfl_down (f, off, 64); }
+	if (lane == 0)
+		{
+#pragma unroll
+		for (int k=0 ; k<XS_K ; k++) xs_deposit (acc, ax[k]);
+		if (c != 0) atomicAdd (&acc[GDSP_XSUM_WORD_COUNT], (unsigned long long) c);
+		if (f != 0) atomicAdd (&acc[GDSP_XSUM_WORD_INF],   (unsigned long long) f);
+		}
+	__syncthreads ();
+	// canonical digits (0 <= digit < 2^32 below the top one): the workgroups' images then add without overflow
+	if (threadIdx.x == 0)
+		{
+		long long carry = 0;
+		for (int w=0 ; w<XS_D-1 ; w++)
+			{
+			const long long x = (long long) acc[w] + carry;
+			carry  = x >> 32;
+			acc[w] = (unsigned long long) (x & 0xFFFFFFFFll);
+			}
+		acc[XS_D-1] += (unsigned long long) carry;
+		}
+	__syncthreads ();
+	if ((threadIdx.x < GDSP_XSUM_WORDS) && (acc[threadIdx.x] != 0)) atomicAdd (&d_acc[threadIdx.x], acc[threadIdx.x]);
+	}
+
+// the device image in canonical digits (one lane: 68 steps)
+__global__ void xsum_fold_kernel (unsigned long long* d_acc)
+	{
+	if (threadIdx.x != 0) return;
+	long long carry = 0;
+	for (int w=0 ; w<XS_D-1 ; w++)
+		{
+		const long long x = (long long) d_acc[w] + carry;
+		carry    = x >> 32;
+		d_acc[w] = (unsigned long long) (x & 0xFFFFFFFFll);
+		}
+	d_acc[XS_D-1] += (unsigned long long) carry;
+	}
+
+static int xsum_launch (int pass, const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                        double mean, uint64_t* d_acc, void* stream)
+	{
+	GDSP_REQUIRE (d_acc != NULL, "NULL accumulator");
+	GDSP_REQUIRE ((nsources == 0) || (sources != NULL), "NULL sources");
+	if (window == 0) window = 1;
+	hipStream_t s = gdsp_stream (stream);
+	int i = 0;
+	while (i < nsources)
+		{
+		XsBatch B;
+		int k = 0;
+		B.tile0[0] = 0;
+		for ( ; (i<nsources) && (k<GDSP_BATCH_MAX) ; i++)
+			{
+			const gdsp_xsum_source& src = sources[i];
+			if (src.n == 0) continue;
+			GDSP_REQUIRE ((src.d_v != NULL) && ((((uintptr_t) src.d_v) & 7) == 0), "a source must be 8-byte aligned");
+			const uint32_t lead  = gdsp_aligned16 (src.d_v)? 0 : 1;
+			const uint32_t phase = (uint32_t) ((window - src.first % window) % window);
+			if (phase >= src.n) continue;                                  // nothing of it is sampled
+			const uint64_t t = (uint64_t) B.tile0[k] + ((uint64_t) src.n + lead + XS_TILE - 1) / XS_TILE;
+			if ((t > 0x7FFFFFFFull) && (k > 0)) break;                     // the rest goes into the next launch
+			B.base[k] = src.d_v - lead;  B.n[k] = src.n;  B.lead[k] = lead;  B.phase[k] = phase;
+			B.tile0[++k] = (uint32_t) t;
+			}
+		for (int j=k ; j<GDSP_BATCH_MAX ; j++) { B.base[j] = NULL;  B.n[j] = 0;  B.lead[j] = 0;  B.phase[j] = 0;  B.tile0[j+1] = B.tile0[k]; }
+		B.nvec = (uint32_t) k;
+		if (k == 0) continue;
+		const uint32_t tiles  = B.tile0[k];
+		const uint32_t blocks = (tiles < XS_MAX_BLOCKS)? tiles : XS_MAX_BLOCKS;
+		unsigned long long* acc = reinterpret_cast<unsigned long long*> (d_acc);
+		if (pass == 1)
+			{
+			if (window == 1) hipLaunchKernelGGL ((xsum_kernel<1, false>), dim3(blocks), dim3(XS_THREADS), 0, s, B, window, lo, hi, mean, acc);
+			else             hipLaunchKernelGGL ((xsum_kernel<1, true>),  dim3(blocks), dim3(XS_THREADS), 0, s, B, window, lo, hi, mean, acc);
+			}
+		else
+			{
+			if (window == 1) hipLaunchKernelGGL ((xsum_kernel<2, false>), dim3(blocks), dim3(XS_THREADS), 0, s, B, window, lo, hi, mean, acc);
+			else             hipLaunchKernelGGL ((xsum_kernel<2, true>),  dim3(blocks), dim3(XS_THREADS), 0, s, B, window, lo, hi, mean, acc);
+			}
+		GDSP_LAUNCH_CHECK ();
+		}
+	return GDSP_OK;
+	}
+
+// ------------------------------------------------------------------------------------------ host rounding ----
+// the image's value as a sign and a magnitude in 32-bit limbs (least significant first), weight of limb 0: 2^-1074
+static void xs_magnitude (const uint64_t* img, std::vector<uint32_t>& mag, bool& neg)
+	{
+	mag.assign (XS_D + 3, 0);
+	__int128 carry = 0;
+	for (int w=0 ; w<XS_D ; w++)
+		{
+		const __int128 x = (__int128) (int64_t) img[w] + carry;
+		mag[w] = (uint32_t) (x & 0xFFFFFFFF);
+		carry  = x >> 32;                                   // (arithmetic: floor division)
+		}
+	for (int w=XS_D ; w<XS_D+3 ; w++) { mag[w] = (uint32_t) (carry & 0xFFFFFFFF);  carry >>= 32; }
+	neg = (mag[XS_D+2] >> 31) != 0;                         // two's complement over the limbs
+	if (neg)
+		{
+		uint64_t c = 1;
+		for (auto& l : mag) { const uint64_t x = (uint64_t) (uint32_t) ~l + c;  l = (uint32_t) x;  c = x >> 32; }
+		}
+	}
+
+static inline bool xs_bit (const std::vector<uint32_t>& L, int64_t i)
+	{ return (i >= 0) && ((size_t) (i >> 5) < L.size ()) && ((L[i >> 5] >> (i & 31)) & 1); }
+
+// (-1)^neg * (L + something in (0,1) when sticky) * 2^scale, rounded once to nearest, ties to even
+static double xs_round_limbs (const std::vector<uint32_t>& L, bool sticky, int scale, bool neg)
+	{
+	int64_t h = -1;
+	for (int64_t w=(int64_t) L.size ()-1 ; (w>=0) && (h<0) ; w--)
+		{ if (L[w] != 0) h = w*32 + 31 - __builtin_clz (L[w]); }
+	if (h < 0) return 0.0;                                  // (an exact zero: +0.0)
+	const int64_t lsb = std::max<int64_t> (h - 52 + scale, -1074);   // weight of the result's last bit
+	const int64_t s   = lsb - scale;                        // bits of L below it
+	uint64_t mant = 0;
+	for (int64_t i=h ; i>=std::max<int64_t> (s, 0) ; i--) mant = (mant << 1) | (xs_bit (L, i)? 1 : 0);
+	if (s <= 0) { const double r = ldexp ((double) mant, (int) (scale + std::max<int64_t> (s, 0)));  return neg? -r : r; }   // exact
+	const bool half = xs_bit (L, s - 1);
+	for (int64_t i=0 ; (i<s-1) && !sticky ; i++) sticky = xs_bit (L, i);
+	if (half && (sticky || (mant & 1))) mant++;             // (mant may reach 2^53: still exact as a double)
+	const double r = ldexp ((double) mant, (int) lsb);       // exact, or +-inf beyond DBL_MAX
+	return neg? -r : r;
+	}
+
+extern "C" {
+
+int gdsp_xsum_init (uint64_t* d_acc, void* stream)
+	{
+	GDSP_REQUIRE (d_acc != NULL, "NULL accumulator");
+	GDSP_HIP_TRY (hipMemsetAsync (d_acc, 0, GDSP_XSUM_WORDS * sizeof(uint64_t), gdsp_stream (stream)));
+	return GDSP_OK;
+	}
+
+int gdsp_xsum_accumulate_batch (const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                                uint64_t* d_acc, void* stream)
+	{ return xsum_launch (1, sources, nsources, window, lo, hi, 0.0, d_acc, stream); }
+
+int gdsp_xsum_accumulate_sq_batch (const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                                   double mean, uint64_t* d_acc, void* stream)
+	{
+	GDSP_REQUIRE (fabs (mean) <= DBL_MAX, "the mean must be finite");
+	return xsum_launch (2, sources, nsources, window, lo, hi, mean, d_acc, stream);
+	}
+
+int gdsp_xsum_fold (uint64_t* d_acc, void* stream)
+	{
+	GDSP_REQUIRE (d_acc != NULL, "NULL accumulator");
+	hipLaunchKernelGGL (xsum_fold_kernel, dim3(1), dim3(64), 0, gdsp_stream (stream), reinterpret_cast<unsigned long long*> (d_acc));
+	GDSP_LAUNCH_CHECK ();
+	return GDSP_OK;
+	}
+
+void gdsp_xsum_add_host (uint64_t* h_acc, double x)
+	{
+	if (!(fabs (x) <= DBL_MAX)) return;
+	uint32_t w;  uint64_t c0, c1, c2;
+	xs_split (x, w, c0, c1, c2);
+	h_acc[w] += c0;  h_acc[w + 1] += c1;  h_acc[w + 2] += c2;
+	h_acc[GDSP_XSUM_WORD_COUNT]++;
+	}
+
+double gdsp_xsum_round (const uint64_t* h_acc)
+	{
+	if (h_acc[GDSP_XSUM_WORD_INF] != 0) return HUGE_VAL;
+	std::vector<uint32_t> mag;
+	bool neg;
+	xs_magnitude (h_acc, mag, neg);
+	return xs_round_limbs (mag, false, -1074, neg);
+	}
+
+double gdsp_xsum_div_round (const uint64_t* h_acc, uint64_t n)
+	{
+	if (n == 0) return NAN;
+	if (h_acc[GDSP_XSUM_WORD_INF] != 0) return HUGE_VAL;
+	std::vector<uint32_t> mag;
+	bool neg;
+	xs_magnitude (h_acc, mag, neg);
+	// long division of mag * 2^128 by n, limb by limb from the top: the quotient has at least 64 bits more than the
+	// result keeps, and the remainder only says whether anything is left (sticky)
+	std::vector<uint32_t> num (4, 0);
+	num.insert (num.end (), mag.begin (), mag.end ());
+	std::vector<uint32_t> q (num.size (), 0);
+	unsigned __int128 r = 0;
+	for (int64_t w=(int64_t) num.size ()-1 ; w>=0 ; w--)
+		{
+		const unsigned __int128 x = (r << 32) | num[w];
+		q[w] = (uint32_t) (x / n);
+		r    = x % n;
+		}
+	return xs_round_limbs (q, r != 0, -1074 - 128, neg);
+	}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------- end to end ----
+static gdsp_comm* xsComm = NULL;                             // see gdsp_genome_stats_use_comm
+static uint64_t   xsLast[4];                                 // see gdsp_genome_stats_last
+
+// one pass over every source, the devices' images reduced into img (host words, global)
+static int xs_pass (int pass, const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                    double mean, gdsp_reduce_fn reduce, void* reduceCtx, uint64_t* img)
+	{
+	int home = 0;
+	GDSP_HIP_TRY (hipGetDevice (&home));
+	std::vector<int> devices;
+	if (xsComm != NULL)
+		for (int r=0 ; r<gdsp_comm_size (xsComm) ; r++) devices.push_back (gdsp_comm_device (xsComm, r));
+	else
+		{
+		for (int i=0 ; i<nsources ; i++) devices.push_back (sources[i].device);
+		std::sort (devices.begin (), devices.end ());
+		devices.erase (std::unique (devices.begin (), devices.end ()), devices.end ());
+		if (devices.empty ()) devices.push_back (home);
+		}
+	for (int i=0 ; i<nsources ; i++)
+		GDSP_REQUIRE (std::find (devices.begin (), devices.end (), sources[i].device) != devices.end (),
+		              "a source sits on a device the communicator does not hold");
+	const size_t nd = devices.size ();
+	std::vector<uint64_t*> accs (nd, NULL);
+	std::vector<void*>     streams (nd, NULL);
+	std::vector<gdsp_xsum_source> mine;
+	int rc = GDSP_OK;
+	for (size_t d=0 ; (d<nd) && (rc == GDSP_OK) ; d++)
+		{
+		GDSP_HIP_TRY (hipSetDevice (devices[d]));
+		mine.clear ();
+		for (int i=0 ; i<nsources ; i++) { if (sources[i].device == devices[d]) mine.push_back (sources[i]); }
+		if (!mine.empty ()) streams[d] = mine[0].stream;
+		if (hipMalloc ((void**) &accs[d], GDSP_XSUM_WORDS * sizeof(uint64_t)) != hipSuccess)
+			{ accs[d] = NULL;  gdsp_set_error ("gdsp_genome_stats: no device memory for the accumulator");  rc = GDSP_ENOMEM;  break; }
+		rc = gdsp_xsum_init (accs[d], streams[d]);
+		if (rc == GDSP_OK) rc = (pass == 1)? gdsp_xsum_accumulate_batch (mine.data (), (int) mine.size (), window, lo, hi, accs[d], streams[d])
+		                                   : gdsp_xsum_accumulate_sq_batch (mine.data (), (int) mine.size (), window, lo, hi, mean, accs[d], streams[d]);
+		if (rc == GDSP_OK) rc = gdsp_xsum_fold (accs[d], streams[d]);
+		}
+	if ((rc == GDSP_OK) && (xsComm != NULL))
+		rc = gdsp_comm_allreduce_u64 (xsComm, accs.data (), GDSP_XSUM_WORDS, 0, streams.data ());
+	memset (img, 0, GDSP_XSUM_WORDS * sizeof(uint64_t));
+	for (size_t d=0 ; d<nd ; d++)
+		{
+		if (accs[d] == NULL) continue;
+		(void) hipSetDevice (devices[d]);
+		uint64_t h[GDSP_XSUM_WORDS];
+		if ((rc == GDSP_OK) && ((xsComm == NULL) || (d == 0)))        // (with the communicator every rank holds the sum)
+			{
+			if (hipMemcpyAsync (h, accs[d], sizeof(h), hipMemcpyDeviceToHost, gdsp_stream (streams[d])) != hipSuccess
+			 || hipStreamSynchronize (gdsp_stream (streams[d])) != hipSuccess)
+				{ gdsp_set_error ("gdsp_genome_stats: reading the accumulator back failed");  rc = GDSP_EHIP; }
+			else for (int w=0 ; w<GDSP_XSUM_WORDS ; w++) img[w] += h[w];
+			}
+		else (void) hipStreamSynchronize (gdsp_stream (streams[d]));
+		(void) hipFree (accs[d]);
+		}
+	(void) hipSetDevice (home);
+	if ((rc == GDSP_OK) && (reduce != NULL) && (reduce (reduceCtx, img, GDSP_XSUM_WORDS, 0) != 0))
+		{ gdsp_set_error ("gdsp_genome_stats: the caller's reduction failed");  rc = GDSP_EHIP; }
+	return rc;
+	}
+
+extern "C" {
+
+int gdsp_genome_stats_use_comm (gdsp_comm* comm) { xsComm = comm;  return GDSP_OK; }
+
+void gdsp_genome_stats_last (uint64_t out[4]) { memcpy (out, xsLast, sizeof(xsLast)); }
+
+int gdsp_genome_stats (const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                       gdsp_reduce_fn reduce, void* reduceCtx, double* out)
+	{
+	GDSP_REQUIRE (out != NULL, "NULL result");
+	GDSP_REQUIRE ((nsources == 0) || (sources != NULL), "NULL sources");
+	GDSP_REQUIRE (!((xsComm != NULL) && (reduce != NULL)), "a host reduction hook next to a communicator");
+	uint64_t img[GDSP_XSUM_WORDS];
+	int rc = xs_pass (1, sources, nsources, window, lo, hi, 0.0, reduce, reduceCtx, img);
+	if (rc != GDSP_OK) return rc;
+	const uint64_t n = img[GDSP_XSUM_WORD_COUNT];
+	xsLast[0] = n;  xsLast[1] = img[GDSP_XSUM_WORD_FLUSHES];  xsLast[2] = 0;  xsLast[3] = 0;
+	out[0] = (double) n;
+	out[1] = gdsp_xsum_round (img);
+	if (n == 0) { out[2] = out[3] = out[4] = NAN;  return GDSP_OK; }
+	out[2] = gdsp_xsum_div_round (img, n);
+	rc = xs_pass (2, sources, nsources, window, lo, hi, out[2], reduce, reduceCtx, img);
+	if (rc != GDSP_OK) return rc;
+	xsLast[2] = img[GDSP_XSUM_WORD_FLUSHES];  xsLast[3] = img[GDSP_XSUM_WORD_INF];
+	out[3] = gdsp_xsum_div_round (img, n);
+	out[4] = sqrt (out[3]);
+	return GDSP_OK;
+	}
+
+} // extern "C"

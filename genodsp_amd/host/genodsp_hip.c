@@ -59,6 +59,10 @@ dspprototypes(op_clump)          dspprototypes(op_skimp)
 #ifdef GDSP_RANK_FILTER                                /* not in the reference: ops_rankfilt.c */
 dspprototypes(op_sliding_percentile) dspprototypes(op_sliding_median)
 #endif
+#ifdef GDSP_GENOME_STATS                               /* not in the reference: ops_stats.c */
+dspprototypes(op_stats)          dspprototypes(op_normalize)     dspprototypes(op_multiply_constant)
+dspprototypes(op_divide_constant)
+#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
@@ -106,6 +110,12 @@ static dspinfo dspTable[] =
 #ifdef GDSP_RANK_FILTER                                /* windowed order statistics, after the reference's 37 */
 	 , dspinforecord("slidingpercentile", op_sliding_percentile), dspinfoalias ("sliding_percentile"),
 	 dspinforecord("median"        , op_sliding_median) , dspinfoalias ("slidingmedian")  , dspinfoalias ("sliding_median")
+#endif
+#ifdef GDSP_GENOME_STATS                               /* genome-wide figures and scaling by them, after the reference's 37 */
+	 , dspinforecord("stats"       , op_stats)          ,
+	 dspinforecord("normalize"     , op_normalize)      ,
+	 dspinforecord("multiplyconst" , op_multiply_constant), dspinfoalias ("multiply_const"), dspinfoalias ("scale"),
+	 dspinforecord("divideconst"   , op_divide_constant), dspinfoalias ("divide_const")
 #endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS
@@ -608,6 +618,9 @@ static void ensure_device_comm (void)
 		}
 	check_gdsp (rc, "create the RCCL communicator");
 	check_gdsp (gdsp_percentiles_use_comm (deviceComm), "hand the communicator to percentile");
+#ifdef GDSP_GENOME_STATS
+	check_gdsp (gdsp_genome_stats_use_comm (deviceComm), "hand the communicator to stats");
+#endif
 	if (trackOperations)
 		{
 		int version = 0;
@@ -830,7 +843,11 @@ static int pipeline_wants_partners (void)
 		  op_multiply_apply, op_divide_apply, op_absolute_value_apply, op_clip_apply, op_erase_apply, op_binarize_apply,
 		  op_input_apply, op_output_apply, op_show_variables_apply, op_mask_apply, op_mask_not_apply, op_or_apply, op_and_apply,
 		  op_min_with_apply, op_max_with_apply, op_map_apply, op_min_in_interval_apply, op_max_in_interval_apply,
-		  op_clump_apply, op_skimp_apply };
+		  op_clump_apply, op_skimp_apply,
+#ifdef GDSP_GENOME_STATS
+		  op_stats_apply, op_normalize_apply, op_multiply_constant_apply, op_divide_constant_apply,
+#endif
+		};
 	if (shardBases) return true;                               /* (stretches and their runs: not worth a second rule) */
 	for (dspop* op=pipeline ; op!=NULL ; op=op->next)
 		{
@@ -2059,9 +2076,12 @@ int main (int argc, char** argv)
 		else
 			{
 			if (trackOperations) tracking_report ("%s(*)\n", stopOp->name);
-			if ((stopOp->funcApply != op_percentile_apply) && (stopOp->funcApply != op_invert_apply)
-			 && (stopOp->funcApply != op_show_variables_apply))
-				to_whole ();                                   /* file-driven operators address whole chromosomes */
+			int onParts = (stopOp->funcApply == op_percentile_apply) || (stopOp->funcApply == op_invert_apply)
+			           || (stopOp->funcApply == op_show_variables_apply);
+#ifdef GDSP_GENOME_STATS
+			if (op_stats_is_stop (stopOp)) onParts = true;           /* (normalize rewrites halo and owner alike) */
+#endif
+			if (!onParts) to_whole ();                         /* file-driven operators address whole chromosomes */
 			double t0 = now_ms ();
 			u64 ivBefore = intervalsRead;
 			if (reportGpu) sync_all_devices ();
@@ -2087,7 +2107,14 @@ int main (int argc, char** argv)
 					wall_phase (stopOp, label, now_ms () - t0, intervalsRead - ivBefore, "intervals", 0);
 					}
 				else if (ran == 2) wall_phase (stopOp, "percentile=binarize", now_ms () - t0, total, "bases", 24);
-				else wall_phase (stopOp, stopOp->name, now_ms () - t0, total, "bases", (stopOp->funcApply == op_percentile_apply)? 8 : 16);
+				else
+					{
+					double bpb = (stopOp->funcApply == op_percentile_apply)? 8 : 16;
+#ifdef GDSP_GENOME_STATS
+					if (op_stats_is_stop (stopOp)) bpb = op_stats_is_normalize (stopOp)? 32 : 16;   /* 8 B/base per stats pass */
+#endif
+					wall_phase (stopOp, stopOp->name, now_ms () - t0, total, "bases", bpb);
+					}
 				}
 			firstOp = (ran == 2)? stopOp->next->next : stopOp->next;
 			}
@@ -2115,6 +2142,9 @@ int main (int argc, char** argv)
 
 	for (dspop* op=pipeline, *next ; op!=NULL ; op=next)
 		{ next = op->next;  free (op->name);  (*op->funcFree) (op); }
+#ifdef GDSP_GENOME_STATS
+	if (deviceComm != NULL) gdsp_genome_stats_use_comm (NULL);
+#endif
 	if (deviceComm != NULL) { gdsp_percentiles_use_comm (NULL);  gdsp_comm_destroy (deviceComm); }
 	return EXIT_SUCCESS;
 	}

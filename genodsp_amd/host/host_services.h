@@ -77,6 +77,11 @@ u32   to_thousandths      (valtype pct);
 int   op_rankfilt_is      (dspop* op);
 u32   op_rankfilt_window  (dspop* op);
 int   op_rankfilt_batch   (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
+/* ops_stats.c (stats, normalize, multiplyconst, divideconst; compiled in with -DGDSP_GENOME_STATS) */
+int   op_const_is         (dspop* op);       /* multiplyconst / divideconst: per-base, in place */
+int   op_const_batch      (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
+int   op_stats_is_stop    (dspop* op);       /* stats / normalize: whole-genome, on the signal's parts as they are */
+int   op_stats_is_normalize (dspop* op);
 
 /* argument helpers used by every operator's parse function */
 #define OP_SHORT(fn, text)                                                            \

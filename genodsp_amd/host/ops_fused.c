@@ -34,6 +34,9 @@ int op_reach (dspop* op, u32* left, u32* right)
 	if ((f == op_binarize_apply) || (f == op_clip_apply) || (f == op_erase_apply) || (f == op_add_constant_apply)
 	 || (f == op_absolute_value_apply) || (f == op_map_apply))
 		return true;
+#ifdef GDSP_GENOME_STATS
+	if (op_const_is (op)) return true;                     /* multiplyconst, divideconst */
+#endif
 #ifdef GDSP_RANK_FILTER
 	if (op_rankfilt_is (op))                               /* bestmax's window: [i-wL, i+wR] */
 		{ u32 W = op_rankfilt_window (op);  *left = (W - 1) / 2;  *right = W - 1 - *left;  return true; }
@@ -88,6 +91,9 @@ int op_batchable (dspop* op)
 #ifdef GDSP_RANK_FILTER
 	if (op_rankfilt_is (op)) return true;
 #endif
+#ifdef GDSP_GENOME_STATS
+	if (op_const_is (op)) return true;
+#endif
 	return (f == op_smooth_apply) || (f == op_local_maxima_apply) || (f == op_local_minima_apply)
 	    || (f == op_best_local_max_apply) || (f == op_best_local_min_apply)
 	    || (f == op_dilate_apply) || (f == op_erode_apply)
@@ -105,8 +111,11 @@ int batch_apply_on_device (dspop* op, dspop* stopOp, spec** units, int nunits, i
 	gdsp_batch_item* items = (gdsp_batch_item*) calloc (nunits? nunits : 1, sizeof(gdsp_batch_item));
 	if (items == NULL) { fprintf (stderr, "out of memory\n");  exit (EXIT_FAILURE); }
 	/* (the in-place operators never ask for a partner: a pipeline of them alone runs without the partners' arena) */
-	const int inPlace = (f == op_binarize_apply) || (f == op_clip_apply) || (f == op_erase_apply)
-	                 || (f == op_add_constant_apply) || (f == op_absolute_value_apply);
+	int inPlace = (f == op_binarize_apply) || (f == op_clip_apply) || (f == op_erase_apply)
+	           || (f == op_add_constant_apply) || (f == op_absolute_value_apply);
+#ifdef GDSP_GENOME_STATS
+	if (op_const_is (op)) inPlace = true;
+#endif
 	for (int i=0 ; i<nunits ; i++)
 		{ items[i].d_in = units[i]->valVector;  items[i].d_out = inPlace? NULL : partner_of (units[i]);  items[i].n = units[i]->length; }
 	void* st = op_stream ();
@@ -183,6 +192,9 @@ int batch_apply_on_device (dspop* op, dspop* stopOp, spec** units, int nunits, i
 			                         : gdsp_erase_batch (items, nunits, haveMin, lo, haveMax, hi, keepInside, zero, st);
 			}
 		else if (f == op_add_constant_apply) rc = gdsp_add_constant_batch (items, nunits, op_add_constant_value (op), st);
+#ifdef GDSP_GENOME_STATS
+		else if (op_const_is (op))           rc = op_const_batch (op, items, nunits, st);
+#endif
 		else                                 rc = gdsp_abs_batch (items, nunits, st);
 		}
 	free (items);

@@ -338,6 +338,63 @@ int gdsp_percentiles_binarize (const gdsp_select_source* sources, int nsources, 
  * (one device, nothing to reduce with; GDSP_PERCENTILE_RESIDENT_OFF forbids it) */
 void gdsp_percentiles_stats (uint64_t out[8]);
 
+/* ---- stats / normalize (not in the reference): genome-wide sum, mean and variance, exact and rounded once --------
+ * The sample is percentile's: every window-th value counted from each chromosome's first base whose value v satisfies
+ * !(v < lo) && !(v > hi), non-finite values never; n is its size.  sum = the exact sum rounded once to nearest-even (it
+ * may round to +-inf; an exact zero is +0.0).  mean = the exact sum / n rounded once (not sum / n: always finite).
+ * variance = the exact (sum over the sample of q) / n rounded once, q = fl(fl(v - mean)^2) without fma; +inf when some
+ * q is.  stddev = sqrt(variance).  None of them depends on how the genome is cut into vectors, stretches, devices or
+ * ranks, nor on tiles, grid or dispatch order (gdsp_xsum.hip).
+ *
+ * The accumulator: GDSP_XSUM_WORDS u64 words.  Word k < GDSP_XSUM_DIGITS is a signed (two's complement) multiple of
+ * 2^(32k - 1074); the value is the sum of them all (2^-1074 .. 2^1102).  GDSP_XSUM_WORD_COUNT counts the sampled values,
+ * GDSP_XSUM_WORD_INF the q that are +inf (pass 2), GDSP_XSUM_WORD_FLUSHES the times a lane's register expansion handed
+ * a residual to the workgroup's integer image (a diagnostic: it depends on the cut).  Images add as plain u64 SUMs
+ * (all-reduce them with op 0); each accumulate call grows a word by less than 2^43.
+ * A source is d_v[0 .. n) (8-byte aligned, on the current device for the *_batch calls); `first` is the chromosome
+ * position of d_v[0], so that the window counts from the chromosome's first base whatever stretch the source is. */
+#define GDSP_XSUM_DIGITS       68
+#define GDSP_XSUM_WORD_COUNT   68
+#define GDSP_XSUM_WORD_INF     69
+#define GDSP_XSUM_WORD_FLUSHES 70
+#define GDSP_XSUM_WORDS        72
+typedef struct gdsp_xsum_source { const double* d_v; uint32_t n; uint32_t first; int device; void* stream; } gdsp_xsum_source;
+int gdsp_xsum_init (uint64_t* d_acc, void* stream);                                  /* zero an accumulator */
+/* pass 1: add every sampled v of every source to d_acc (one launch per 32 sources) */
+int gdsp_xsum_accumulate_batch    (const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                                   uint64_t* d_acc, void* stream);
+/* pass 2: add fl(fl(v - mean)^2) of every sampled v (mean finite) */
+int gdsp_xsum_accumulate_sq_batch (const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                                   double mean, uint64_t* d_acc, void* stream);
+/* carry the digits into canonical form (0 <= digit < 2^32 below the top one, which keeps the sign): equal values give
+ * equal words, and up to 2^31 canonical images add without overflow */
+int gdsp_xsum_fold (uint64_t* d_acc, void* stream);
+/* Host, no GPU: add a finite x to a host image (and 1 to its count; non-finite x are ignored); the image's value rounded
+ * once (+inf when the INF word is set); the value / n rounded once (NaN for n == 0, +inf when the INF word is set).
+ * The image may be canonical or not. */
+void   gdsp_xsum_add_host  (uint64_t* h_acc, double x);
+double gdsp_xsum_round     (const uint64_t* h_acc);
+double gdsp_xsum_div_round (const uint64_t* h_acc, uint64_t n);
+/* end to end: out[0..4] = count, sum, mean, variance, stddev (count 0: sum 0 and the rest NaN).  Sources may sit on
+ * several devices of this process (each device's work is queued on the stream of its first source; the images are
+ * added on the host, or all-reduced in HBM through the communicator given to gdsp_genome_stats_use_comm, whose devices
+ * must then be the sources' devices); with one process per GPU pass `reduce` (op 0 = sum of the u64 words over all
+ * ranks), as for gdsp_percentiles.  Two passes over the signal; waits for them. */
+int gdsp_genome_stats (const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                       gdsp_reduce_fn reduce, void* reduceCtx, double* out);
+int gdsp_genome_stats_use_comm (gdsp_comm* comm);     /* NULL switches back to host sums */
+/* what the last gdsp_genome_stats did: [0] n, [1] lane flushes of pass 1, [2] of pass 2, [3] q that were +inf */
+void gdsp_genome_stats_last (uint64_t out[4]);
+
+/* multiplyconst / divideconst / normalize (in place, one pointwise launch per table of 32 vectors): v = fl(v * c),
+ * fl(v / c) (c == 0 is refused), fl(fl(v - center) / scale) (scale == 0 is refused) */
+int gdsp_multiply_constant       (double* d_v, uint32_t n, double c, void* stream);
+int gdsp_divide_constant         (double* d_v, uint32_t n, double c, void* stream);
+int gdsp_standardize             (double* d_v, uint32_t n, double center, double scale, void* stream);
+int gdsp_multiply_constant_batch (const gdsp_batch_item* items, int nitems, double c, void* stream);
+int gdsp_divide_constant_batch   (const gdsp_batch_item* items, int nitems, double c, void* stream);
+int gdsp_standardize_batch       (const gdsp_batch_item* items, int nitems, double center, double scale, void* stream);
+
 /* ---- genodsp.c read_intervals / add.c / multiply.c ------------------------------ */
 
 /* Interval-driven writes.  The host routes intervals to this chromosome, applies
