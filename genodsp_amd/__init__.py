@@ -649,6 +649,76 @@ def xsum_add_host(image, x):
     return image
 
 
+# ------------------------------------------------------ statsover (not in the reference) ----
+
+INTERVAL_STAT = np.dtype([("count", np.uint64), ("sum", np.float64), ("mean", np.float64), ("min", np.float64),
+                          ("max", np.float64), ("maxpos", np.uint32), ("image", np.uint32)])       # gdsp_interval_stat
+INTERVAL_PIECE = np.dtype([("a0", np.float64), ("a1", np.float64), ("min", np.float64), ("max", np.float64),
+                           ("count", np.uint32), ("maxpos", np.uint32), ("flag", np.uint32), ("reserved", np.uint32)])   # gdsp_interval_piece
+
+
+def interval_stats_tile():
+    """The tile the kernel cuts intervals at (values of the 16-byte aligned frame a vector lies in)."""
+    return int(lib().gdsp_interval_stats_tile())
+
+
+def _interval_figures(rec):
+    none = rec["count"] == 0
+    maxpos = rec["maxpos"].astype(np.int64)
+    maxpos[none] = -1
+    return {"count": rec["count"].copy(), "sum": rec["sum"].copy(), "mean": rec["mean"].copy(), "min": rec["min"].copy(),
+            "max": rec["max"].copy(), "maxpos": maxpos}
+
+
+def interval_stats(v, start, end, lo=-DBL_MAX, hi=DBL_MAX, stream=None, vec=None):
+    """count, sum, mean, min, max and maxpos of v over the intervals [start[i], end[i]) (gdsp_interval_stats: stats'
+    sample inside each interval, every figure exact and rounded once; NaN / -1 where the sample is empty).  -> dict of
+    numpy arrays in the caller's order.  v: a DeviceVector or a (vector, first, count) stretch of one; or a LIST of
+    them with vec[i] naming interval i's vector (gdsp_interval_stats_batch: one launch for all of them).  Waits."""
+    vecs = v if isinstance(v, list) else [v]
+    items = (BatchItem * max(1, len(vecs)))()
+    for k, item in enumerate(vecs):
+        if isinstance(item, DeviceVector):
+            items[k].d_in, items[k].n = item.ptr.value, item.n
+        else:
+            assert 0 <= int(item[1]) and int(item[1]) + int(item[2]) <= item[0].n
+            items[k].d_in, items[k].n = item[0].ptr.value + 8 * int(item[1]), int(item[2])
+    start = np.ascontiguousarray(start, dtype=np.uint32)
+    end = np.ascontiguousarray(end, dtype=np.uint32)
+    assert start.shape == end.shape and start.ndim == 1
+    which = None if vec is None else np.ascontiguousarray(vec, dtype=np.uint32)
+    assert which is None or which.shape == start.shape
+    rec = np.zeros(start.size, INTERVAL_STAT)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    call("gdsp_interval_stats_batch", items, len(vecs), vp(which), vp(start), vp(end), start.size, float(lo), float(hi),
+         vp(rec), _sp(stream))
+    return _interval_figures(rec)
+
+
+def interval_stats_combine(pieces, images=None):
+    """Host, no GPU: an interval's figures from its pieces' records (np array of INTERVAL_PIECE; images: one
+    XSUM_WORDS image per flagged piece, in order).  -> dict of scalars, as interval_stats gives arrays."""
+    pieces = np.ascontiguousarray(pieces, dtype=INTERVAL_PIECE)
+    img = None if images is None else np.ascontiguousarray(images, dtype=np.uint64)
+    rec = np.zeros(1, INTERVAL_STAT)
+    call("gdsp_interval_stats_combine", pieces.ctypes.data_as(C.c_void_p), pieces.size,
+         None if img is None else img.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p))
+    out = {k: a[0] for k, a in _interval_figures(rec).items()}
+    out["image"] = int(rec["image"][0])
+    return out
+
+
+def interval_stats_last():
+    """What the last interval_stats did: intervals, pieces, flagged pieces (summed again through the exact pass),
+    intervals rounded from the integer image; and ms spent cutting, in the kernel, copying and waiting, combining."""
+    out, ms = (C.c_uint64 * 4)(), (C.c_double * 4)()
+    lib().gdsp_interval_stats_last(out)
+    lib().gdsp_interval_stats_times(ms)
+    d = dict(zip(("intervals", "pieces", "flagged", "imaged"), [int(x) for x in out]))
+    d.update(zip(("ms_cut", "ms_kernel", "ms_copy", "ms_combine"), [float(x) for x in ms]))
+    return d
+
+
 def _each(name, vecs, *params, stream=None):
     if isinstance(vecs, DeviceVector):
         call(name, vecs.ptr, vecs.n, *params, _sp(stream))

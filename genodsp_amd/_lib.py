@@ -151,6 +151,13 @@ SIGNATURES = {
     "gdsp_genome_stats": (_int, [_vp, _int, _u32, _f64, _f64, _vp, _vp, _vp]),
     "gdsp_genome_stats_use_comm": (_int, [_vp]),
     "gdsp_genome_stats_last": (None, [_vp]),
+    # statsover (not in the reference)
+    "gdsp_interval_stats_tile": (_u32, []),
+    "gdsp_interval_stats": (_int, [_vp, _u32, _vp, _vp, _u32, _f64, _f64, _vp, _vp]),
+    "gdsp_interval_stats_batch": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _f64, _f64, _vp, _vp]),
+    "gdsp_interval_stats_combine": (_int, [_vp, _u32, _vp, _vp]),
+    "gdsp_interval_stats_last": (None, [_vp]),
+    "gdsp_interval_stats_times": (None, [_vp]),
     "gdsp_multiply_constant": (_int, [_vp, _u32, _f64, _vp]),
     "gdsp_divide_constant": (_int, [_vp, _u32, _f64, _vp]),
     "gdsp_standardize": (_int, [_vp, _u32, _f64, _f64, _vp]),

@@ -1,0 +1,525 @@
+// gdsp_intervalstats.hip -- statsover (not in the reference): count, exact sum and mean, min, max and summit of one
+// signal over millions of arbitrary intervals -- short and long, overlapping, in any order (include/genodsp_hip.h).
+//
+// Work is cut into PIECES: an interval intersected with a tile of IS_TILE values of the 16-byte aligned frame its vector
+// lies in.  The host sorts the pieces of a call by tile (a counting sort, the caller's order kept inside a tile) and cuts
+// every tile's list into ITEMS of at most IS_ITEM_PIECES pieces; a workgroup takes one item, so one 249 Mbp interval and
+// a million intervals inside one tile both fill the device, and a tile no interval touches is never read.  The workgroup
+// brings the part of the tile its pieces cover into LDS with 16-byte loads, and its four waves take the pieces in turn:
+// a lane walks its piece with stride 64, keeps two 2-term TwoSum expansions (gdsp_xsum_dev.h: unchecked, a residual or
+// an overflow sets `flag`), the count, the least value, and the greatest value with its lowest position; a shuffle tree
+// folds the lanes and lane 0 writes the piece's record.  A workgroup reads the signal and writes its own records: there
+// is no atomic, no workgroup reads what another wrote, and nothing depends on the dispatch order.
+//
+// The host then combines an interval's pieces exactly (gdsp_interval_stats_combine, no GPU): the terms of unflagged
+// pieces are added with TwoSum into two terms; when nothing is left over and their sum is one double, that double is the
+// sum and one IEEE division gives the mean (always so on integer read depth); when two doubles s + e hold it, s is the
+// sum and a 128-bit division gives the mean.  Otherwise the terms go into a 72-word
+// integer image (gdsp_xsum_add_host) and gdsp_xsum_round / gdsp_xsum_div_round round it once.  A flagged piece (huge
+// cancelling values, residuals across hundreds of binades) is summed again by gdsp_xsum_accumulate_batch with that piece
+// as its one source: adversarial data stays exact and gets slower.
+
+#include <float.h>
+#include <math.h>
+#include <string.h>
+#include <vector>
+#include <algorithm>
+#include <chrono>
+#include "gdsp_common.h"
+#include "gdsp_xsum_dev.h"
+
+#define IS_THREADS      256
+#define IS_WAVES        (IS_THREADS / 64)
+#define IS_TILE         4096                          // values: 32 KiB of LDS, five workgroups on a CU
+#define IS_ITEM_PIECES  64                            // pieces of one tile a workgroup takes
+#define IS_CHUNK_PIECES (1u << 22)                    // pieces of one launch (records: 192 MiB); one interval has at most 2^20 + 1
+#define IS_FLAG_BATCH   1024                          // flagged pieces summed again per read-back
+
+static_assert (sizeof(gdsp_interval_piece) == 48 && sizeof(gdsp_interval_stat) == 48, "the records of the header");
+static_assert (IS_TILE <= 65536 && IS_ITEM_PIECES <= 65535 && GDSP_BATCH_MAX <= 65535, "16-bit fields below");
+
+// one launch's table (the batch convention of gdsp_common.h): vector s is base[s][lead[s] .. lead[s]+n), base 16-byte aligned
+struct IsBatch
+	{
+	const double* base[GDSP_BATCH_MAX];
+	uint32_t      lead[GDSP_BATCH_MAX];
+	};
+
+// a workgroup's work: pieces [first, first+count) of the launch, all in tile `tile` of vector `vec`; together they cover
+// values [h0, h1) of the tile.  A piece is lo | (hi-1) << 16, values [lo, hi) of the tile.
+struct IsItem { uint32_t first, tile;  uint16_t count, vec, h0, h1m1; };
+static_assert (sizeof(IsItem) == 16, "loaded as one 16-byte word");
+
+__global__ __launch_bounds__(IS_THREADS)
+void interval_stats_kernel (IsBatch B, const uint4* __restrict__ items, const uint32_t* __restrict__ pieces, double lo, double hi,
+                            gdsp_interval_piece* __restrict__ out)
+	{
+	__shared__ double tile[IS_TILE];
+	const uint4    raw   = items[blockIdx.x];
+	const uint32_t first = __builtin_amdgcn_readfirstlane (raw.x);
+	const uint32_t t     = __builtin_amdgcn_readfirstlane (raw.y);
+	const uint32_t cv    = __builtin_amdgcn_readfirstlane (raw.z);
+	const uint32_t hh    = __builtin_amdgcn_readfirstlane (raw.w);
+	const uint32_t count = cv & 0xFFFF, vec = cv >> 16;
+	const uint32_t h0    = hh & 0xFFFF, h1 = (hh >> 16) + 1;
+	const double*  base  = B.base[vec] + (uint64_t) t * IS_TILE;
+	const uint32_t pos0  = t * IS_TILE - B.lead[vec];          // the vector position of tile[0] (tile 0 behind a lead: tile[0] is in no piece)
+
+	// values [h0, h1) of the tile, whole 16-byte words first; the hull ends inside the vector, so an odd last value is
+	// loaded on its own (its word's other half may lie beyond the vector)
+	const uint32_t e0 = h0 & ~1u;
+	const uint32_t np = (h1 - e0) >> 1;
+	const double2* src = reinterpret_cast<const double2*> (base + e0);
+	double2*       dst = reinterpret_cast<double2*> (tile + e0);
+	for (uint32_t b0=0 ; b0<np ; b0+=GDSP_STAGE_DEPTH*IS_THREADS)
+		{
+		double2 r[GDSP_STAGE_DEPTH];
+#pragma unroll
+		for (int u=0 ; u<GDSP_STAGE_DEPTH ; u++)                // (every lane loads, index clamped: see gdsp_stage_f64)
+			{ const uint32_t p = b0 + u*IS_THREADS + threadIdx.x;  r[u] = src[(p < np)? p : np-1]; }
+#pragma unroll
+		for (int u=0 ; u<GDSP_STAGE_DEPTH ; u++)
+			{ const uint32_t p = b0 + u*IS_THREADS + threadIdx.x;  if (p < np) dst[p] = r[u]; }
+		}
+	if ((((h1 - e0) & 1) != 0) && (threadIdx.x == 0)) tile[h1-1] = base[h1-1];
+	__syncthreads ();
+
+	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	for (uint32_t k=wave ; k<count ; k+=IS_WAVES)
+		{
+		const uint32_t d = __builtin_amdgcn_readfirstlane (pieces[first + k]);
+		const uint32_t a = d & 0xFFFF, b = (d >> 16) + 1;
+		double   ax[XS_K], ay[XS_K], mn = HUGE_VAL, mx = -HUGE_VAL;
+		uint32_t cnt = 0, flag = 0, pos = UINT32_MAX;
+#pragma unroll
+		for (int j=0 ; j<XS_K ; j++) { ax[j] = 0.0;  ay[j] = 0.0; }
+		auto take = [&] (double (&acc)[XS_K], uint32_t i)
+			{
+			const double x  = tile[i];
+			const bool   in = !(x < lo) && !(x > hi) && xs_finite (x);    // stats' tests; NaN and +-inf never
+			cnt += in;
+			xs_grow_or_flag (acc, in? x : 0.0, flag);
+			mn = (in && (x < mn))? x : mn;
+			if (in && (x > mx)) { mx = x;  pos = i; }                   // (i ascends: the first of equals stays)
+			};
+		uint32_t i = a + lane;
+		for ( ; i+64<b ; i+=128) { take (ax, i);  take (ay, i+64); }
+		if (i < b) take (ax, i);
+
+		// the lane's two expansions, then the wave's 64 as a tree: lane l takes lane l+off's terms when l % 2off == 0
+#pragma unroll
+		for (int j=0 ; j<XS_K ; j++) xs_grow_or_flag (ax, ay[j], flag);
+		for (int off=1 ; off<64 ; off<<=1)
+			{
+			double tt[XS_K];
+#pragma unroll
+			for (int j=0 ; j<XS_K ; j++) tt[j] = __shfl_down (ax[j], off, 64);
+			const bool mine = (lane & (2*off - 1)) == 0;
+#pragma unroll
+			for (int j=0 ; j<XS_K ; j++) xs_grow_or_flag (ax, mine? tt[j] : 0.0, flag);
+			}
+		for (int off=32 ; off>0 ; off>>=1)
+			{
+			cnt  += __shfl_down (cnt, off, 64);
+			flag |= __shfl_down (flag, off, 64);
+			const double   omn = __shfl_down (mn, off, 64), omx = __shfl_down (mx, off, 64);
+			const uint32_t opos = __shfl_down (pos, off, 64);
+			mn = (omn < mn)? omn : mn;
+			if ((omx > mx) || ((omx == mx) && (opos < pos))) { mx = omx;  pos = opos; }
+			}
+		if (lane == 0)
+			{
+			gdsp_interval_piece r;
+			r.a0 = ax[0];  r.a1 = ax[1];  r.min = mn;  r.max = mx;
+			r.count = cnt;  r.maxpos = (cnt != 0)? pos0 + pos : UINT32_MAX;  r.flag = flag;  r.reserved = 0;
+			out[first + k] = r;
+			}
+		}
+	}
+
+// ---------------------------------------------------------------------------------------------- host ----
+// per device: staging and result buffers, grown on demand and kept
+struct IsBuffers
+	{
+	uint32_t *h_pieces, *d_pieces;  size_t capPieces;
+	IsItem   *h_items,  *d_items;   size_t capItems;
+	gdsp_interval_piece *h_out, *d_out;  size_t capOut;
+	uint64_t *h_img, *d_img;
+	};
+static IsBuffers isBuffers[64];
+static uint64_t  isLast[4];
+static double    isTimes[4];
+
+static int is_grow (void** h, void** d, size_t* cap, size_t want, size_t elem)
+	{
+	if (want <= *cap) return GDSP_OK;
+	size_t n = (*cap == 0)? 65536 : *cap;
+	while (n < want) n *= 2;
+	if (*h != NULL) { (void) hipHostFree (*h);  *h = NULL; }
+	if (*d != NULL) { (void) hipFree (*d);  *d = NULL; }
+	*cap = 0;
+	if (hipHostMalloc (h, n * elem, hipHostMallocDefault) != hipSuccess) { *h = NULL;  gdsp_set_error ("gdsp_interval_stats: no pinned memory");  return GDSP_ENOMEM; }
+	if (hipMalloc (d, n * elem) != hipSuccess) { *d = NULL;  gdsp_set_error ("gdsp_interval_stats: no device memory");  return GDSP_ENOMEM; }
+	*cap = n;
+	return GDSP_OK;
+	}
+
+static inline double is_ms_since (std::chrono::steady_clock::time_point t0)
+	{ return std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now () - t0).count (); }
+
+struct IsVector { const double* v;  uint32_t n, lead, tile0; };      // tile0: its first tile in the launch's numbering
+
+// the intervals sel[0 .. nsel) (indices into the caller's arrays; all on the vectors vecs[0 .. nvec) of this launch,
+// vector `vecBase + k` of the caller being vecs[k]), at most IS_CHUNK_PIECES pieces or one interval
+static int is_launch (const IsVector* vecs, int nvec, int vecBase, uint32_t tiles, const uint32_t* sel, uint32_t nsel,
+                      const uint32_t* h_vec, const uint32_t* h_start, const uint32_t* h_end, double lo, double hi,
+                      gdsp_interval_stat* h_out, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+	{
+	auto tBin = std::chrono::steady_clock::now ();
+	int dev = 0;
+	GDSP_HIP_TRY (hipGetDevice (&dev));
+	GDSP_REQUIRE ((dev >= 0) && (dev < 64), "device index beyond 63");
+	IsBuffers& W = isBuffers[dev];
+
+	// pieces per tile and per interval
+	std::vector<uint32_t> tileFirst ((size_t) tiles + 1, 0), ivFirst ((size_t) nsel + 1, 0);
+	auto span = [&] (uint32_t i, const IsVector*& V, uint64_t& fs, uint64_t& fe)
+		{
+		V  = &vecs[((h_vec != NULL)? (int) h_vec[i] : 0) - vecBase];
+		fs = (uint64_t) h_start[i] + V->lead;  fe = (uint64_t) h_end[i] + V->lead;       // in the frame
+		};
+	for (uint32_t j=0 ; j<nsel ; j++)
+		{
+		const IsVector* V;  uint64_t fs, fe;
+		span (sel[j], V, fs, fe);
+		const uint32_t ts = (uint32_t) (fs / IS_TILE), te = (uint32_t) ((fe - 1) / IS_TILE);
+		for (uint32_t t=ts ; t<=te ; t++) tileFirst[V->tile0 + t + 1]++;
+		ivFirst[j+1] = ivFirst[j] + (te - ts + 1);
+		}
+	const uint32_t P = ivFirst[nsel];
+	uint32_t nitems = 0;
+	std::vector<uint32_t> itemBase (tiles, 0);
+	for (uint32_t g=0 ; g<tiles ; g++)
+		{
+		itemBase[g] = nitems;
+		nitems += (tileFirst[g+1] + IS_ITEM_PIECES - 1) / IS_ITEM_PIECES;
+		tileFirst[g+1] += tileFirst[g];
+		}
+	int rc = is_grow ((void**) &W.h_pieces, (void**) &W.d_pieces, &W.capPieces, P, sizeof(uint32_t));
+	if (rc == GDSP_OK) rc = is_grow ((void**) &W.h_items, (void**) &W.d_items, &W.capItems, nitems, sizeof(IsItem));
+	if (rc == GDSP_OK) rc = is_grow ((void**) &W.h_out, (void**) &W.d_out, &W.capOut, P, sizeof(gdsp_interval_piece));
+	if (rc != GDSP_OK) return rc;
+
+	// the items of every tile that has pieces, their hulls still empty
+		{
+		int v = 0;
+		for (uint32_t g=0 ; g<tiles ; g++)
+			{
+			const uint32_t c = tileFirst[g+1] - tileFirst[g];
+			if (c == 0) continue;
+			while ((v+1 < nvec) && (vecs[v+1].tile0 <= g)) v++;
+			for (uint32_t k=0 ; k<c ; k+=IS_ITEM_PIECES)
+				{
+				IsItem& it = W.h_items[itemBase[g] + k / IS_ITEM_PIECES];
+				it.first = tileFirst[g] + k;  it.tile = g - vecs[v].tile0;
+				it.count = (uint16_t) std::min<uint32_t> (c - k, IS_ITEM_PIECES);  it.vec = (uint16_t) v;
+				it.h0 = 0xFFFF;  it.h1m1 = 0;
+				}
+			}
+		}
+	// the pieces, sorted by tile (the caller's order inside a tile); where each interval's pieces went
+	std::vector<uint32_t> cursor (tileFirst.begin (), tileFirst.end () - 1), ivPiece (P);
+	for (uint32_t j=0 ; j<nsel ; j++)
+		{
+		const IsVector* V;  uint64_t fs, fe;
+		span (sel[j], V, fs, fe);
+		const uint32_t ts = (uint32_t) (fs / IS_TILE), te = (uint32_t) ((fe - 1) / IS_TILE);
+		for (uint32_t t=ts ; t<=te ; t++)
+			{
+			const uint32_t g = V->tile0 + t;
+			const uint64_t t0 = (uint64_t) t * IS_TILE;
+			const uint32_t a = (uint32_t) (std::max (fs, t0) - t0), b = (uint32_t) (std::min (fe, t0 + IS_TILE) - t0);
+			const uint32_t pos = cursor[g]++;
+			W.h_pieces[pos] = a | ((b - 1) << 16);
+			ivPiece[ivFirst[j] + (t - ts)] = pos;
+			IsItem& it = W.h_items[itemBase[g] + (pos - tileFirst[g]) / IS_ITEM_PIECES];
+			it.h0   = (uint16_t) std::min<uint32_t> (it.h0, a);
+			it.h1m1 = (uint16_t) std::max<uint32_t> (it.h1m1, b - 1);
+			}
+		}
+	isTimes[0] += is_ms_since (tBin);
+
+	auto tDev = std::chrono::steady_clock::now ();
+	IsBatch B;
+	for (int k=0 ; k<GDSP_BATCH_MAX ; k++)
+		{
+		B.base[k] = (k < nvec)? vecs[k].v - vecs[k].lead : NULL;
+		B.lead[k] = (k < nvec)? vecs[k].lead : 0;
+		}
+	GDSP_HIP_TRY (hipMemcpyAsync (W.d_pieces, W.h_pieces, (size_t) P * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+	GDSP_HIP_TRY (hipMemcpyAsync (W.d_items, W.h_items, (size_t) nitems * sizeof(IsItem), hipMemcpyHostToDevice, s));
+	GDSP_HIP_TRY (hipEventRecord (ev0, s));
+	hipLaunchKernelGGL (interval_stats_kernel, dim3(nitems), dim3(IS_THREADS), 0, s, B, reinterpret_cast<const uint4*> (W.d_items),
+	                    W.d_pieces, lo, hi, W.d_out);
+	GDSP_LAUNCH_CHECK ();
+	GDSP_HIP_TRY (hipEventRecord (ev1, s));
+	GDSP_HIP_TRY (hipMemcpyAsync (W.h_out, W.d_out, (size_t) P * sizeof(gdsp_interval_piece), hipMemcpyDeviceToHost, s));
+	GDSP_HIP_TRY (hipStreamSynchronize (s));
+	float kernelMs = 0;
+	GDSP_HIP_TRY (hipEventElapsedTime (&kernelMs, ev0, ev1));
+
+	// flagged pieces: each is summed again as the one source of an exact pass
+	std::vector<uint32_t> flagged;
+	for (uint32_t p=0 ; p<P ; p++) { if (W.h_out[p].flag != 0) flagged.push_back (p); }
+	std::vector<uint64_t> images (flagged.size () * GDSP_XSUM_WORDS);
+	if (!flagged.empty ())
+		{
+		if (W.h_img == NULL)
+			{
+			const size_t bytes = (size_t) IS_FLAG_BATCH * GDSP_XSUM_WORDS * sizeof(uint64_t);
+			if (hipHostMalloc ((void**) &W.h_img, bytes, hipHostMallocDefault) != hipSuccess) { W.h_img = NULL;  gdsp_set_error ("gdsp_interval_stats: no pinned memory");  return GDSP_ENOMEM; }
+			if (hipMalloc ((void**) &W.d_img, bytes) != hipSuccess) { W.d_img = NULL;  gdsp_set_error ("gdsp_interval_stats: no device memory");  return GDSP_ENOMEM; }
+			}
+		for (size_t f0=0 ; f0<flagged.size () ; f0+=IS_FLAG_BATCH)
+			{
+			const size_t m = std::min<size_t> (IS_FLAG_BATCH, flagged.size () - f0);
+			GDSP_HIP_TRY (hipMemsetAsync (W.d_img, 0, m * GDSP_XSUM_WORDS * sizeof(uint64_t), s));
+			for (size_t f=0 ; f<m ; f++)
+				{
+				const uint32_t p = flagged[f0 + f];
+				const uint32_t g = (uint32_t) (std::upper_bound (tileFirst.begin (), tileFirst.end (), p) - tileFirst.begin ()) - 1;
+				int v = 0;
+				while ((v+1 < nvec) && (vecs[v+1].tile0 <= g)) v++;
+				const uint32_t a = W.h_pieces[p] & 0xFFFF, b = (W.h_pieces[p] >> 16) + 1;
+				gdsp_xsum_source src;
+				src.d_v = B.base[v] + (uint64_t) (g - vecs[v].tile0) * IS_TILE + a;  src.n = b - a;  src.first = 0;
+				src.device = dev;  src.stream = (void*) s;
+				rc = gdsp_xsum_accumulate_batch (&src, 1, 1, lo, hi, W.d_img + f * GDSP_XSUM_WORDS, (void*) s);
+				if (rc != GDSP_OK) return rc;
+				}
+			GDSP_HIP_TRY (hipMemcpyAsync (W.h_img, W.d_img, m * GDSP_XSUM_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+			GDSP_HIP_TRY (hipStreamSynchronize (s));
+			memcpy (&images[f0 * GDSP_XSUM_WORDS], W.h_img, m * GDSP_XSUM_WORDS * sizeof(uint64_t));
+			}
+		}
+	isTimes[1] += kernelMs;
+	isTimes[2] += is_ms_since (tDev) - kernelMs;
+
+	auto tCombine = std::chrono::steady_clock::now ();
+	std::vector<gdsp_interval_piece> mine;
+	std::vector<uint64_t> mineImages;
+	for (uint32_t j=0 ; j<nsel ; j++)
+		{
+		const uint32_t np = ivFirst[j+1] - ivFirst[j];
+		const gdsp_interval_piece* pc = &W.h_out[ivPiece[ivFirst[j]]];
+		const uint64_t* im = NULL;
+		if ((np > 1) || (pc->flag != 0))
+			{
+			mine.clear ();  mineImages.clear ();
+			for (uint32_t k=0 ; k<np ; k++)
+				{
+				const uint32_t p = ivPiece[ivFirst[j] + k];
+				mine.push_back (W.h_out[p]);
+				if (W.h_out[p].flag == 0) continue;
+				const size_t f = (size_t) (std::lower_bound (flagged.begin (), flagged.end (), p) - flagged.begin ());
+				mineImages.insert (mineImages.end (), &images[f * GDSP_XSUM_WORDS], &images[(f+1) * GDSP_XSUM_WORDS]);
+				}
+			pc = mine.data ();
+			im = mineImages.empty ()? NULL : mineImages.data ();
+			}
+		rc = gdsp_interval_stats_combine (pc, np, im, &h_out[sel[j]]);
+		if (rc != GDSP_OK) return rc;
+		isLast[3] += h_out[sel[j]].image;
+		}
+	isTimes[3] += is_ms_since (tCombine);
+	isLast[0] += nsel;  isLast[1] += P;  isLast[2] += flagged.size ();
+	return GDSP_OK;
+	}
+
+// x = (-1)^neg * m * 2^e with m an integer below 2^53 (x finite and not zero)
+static inline void is_decompose (double x, uint64_t& m, int& e, bool& neg)
+	{
+	union { double d; uint64_t u; } b;
+	b.d = x;
+	const int be = (int) ((b.u >> 52) & 0x7FF);
+	m   = b.u & 0xFFFFFFFFFFFFFull;
+	neg = (b.u >> 63) != 0;
+	if (be != 0) { m |= 1ull << 52;  e = be - 1075; }
+	else         e = -1074;
+	}
+
+// (s + e) / n rounded once, for s = fl(s + e), e != 0, n >= 1: the sum as one integer M * 2^ee of at most 115 bits, a
+// 128-bit division that leaves the quotient 56 bits or more, and the image's rounding (xs_round_limbs) of quotient and
+// remainder.  False when e lies more than 60 bits below s's last place (the caller takes the integer image).
+static bool is_mean_of_two (double s, double e, uint64_t n, double* mean)
+	{
+	uint64_t ms, me;  int es, ee;  bool ns, ne;
+	if ((s == 0.0) || (n == 0) || (n >> 32) > 1) return false;
+	is_decompose (s, ms, es, ns);
+	is_decompose (e, me, ee, ne);
+	const int z = __builtin_ctzll (me);
+	me >>= z;  ee += z;
+	const int d = es - ee;
+	if ((d < 0) || (d > 60)) return false;
+	__int128 M = (__int128) ms << d;
+	if (ns) M = -M;
+	M += ne? -(__int128) me : (__int128) me;
+	const bool neg = M < 0;
+	unsigned __int128 A = neg? (unsigned __int128) (-M) : (unsigned __int128) M;
+	const int k = (d < 37)? 37 - d : 0;                      // |M| has 52 + d bits or more: the quotient at least 56
+	A <<= k;
+	const unsigned __int128 q = A / n, r = A % n;
+	std::vector<uint32_t> L (4);
+	for (int w=0 ; w<4 ; w++) L[w] = (uint32_t) (q >> (32*w));
+	*mean = xs_round_limbs (L, r != 0, ee - k, neg);
+	return true;
+	}
+
+extern "C" {
+
+uint32_t gdsp_interval_stats_tile (void) { return IS_TILE; }
+
+int gdsp_interval_stats_combine (const gdsp_interval_piece* pieces, uint32_t npieces, const uint64_t* images, gdsp_interval_stat* out)
+	{
+	GDSP_REQUIRE (out != NULL, "NULL result");
+	GDSP_REQUIRE ((npieces == 0) || (pieces != NULL), "NULL pieces");
+	uint64_t count = 0;
+	double   mn = HUGE_VAL, mx = -HUGE_VAL;
+	uint32_t pos = UINT32_MAX;
+	bool     anyFlag = false;
+	for (uint32_t k=0 ; k<npieces ; k++)
+		{
+		const gdsp_interval_piece& p = pieces[k];
+		anyFlag |= (p.flag != 0);
+		if (p.count == 0) continue;
+		count += p.count;
+		if (p.min < mn) mn = p.min;
+		if ((p.max > mx) || ((p.max == mx) && (p.maxpos < pos))) { mx = p.max;  pos = p.maxpos; }
+		}
+	GDSP_REQUIRE (!anyFlag || (images != NULL), "a flagged piece without its image");
+	out->count = count;  out->image = 0;
+	if (count == 0) { out->sum = 0.0;  out->mean = out->min = out->max = NAN;  out->maxpos = UINT32_MAX;  return GDSP_OK; }
+	out->min = mn + 0.0;  out->max = mx + 0.0;  out->maxpos = pos;         // (-0.0 + 0.0 is +0.0)
+	if (!anyFlag)
+		{
+		// the pieces' terms into two terms with TwoSum; exact while every residual is zero (an overflow leaves a NaN)
+		double a[2] = { 0.0, 0.0 }, left = 0.0;
+		for (uint32_t k=0 ; (k<npieces) && (left == 0.0) ; k++)
+			{
+			const double term[2] = { pieces[k].a0, pieces[k].a1 };
+			for (int j=0 ; (j<2) && (left == 0.0) ; j++)
+				{
+				double r = term[j];
+				for (int i=0 ; i<2 ; i++)
+					{
+					const double s  = a[i] + r;
+					const double bp = s - a[i];
+					r    = (a[i] - (s - bp)) + (r - bp);
+					a[i] = s;
+					}
+				left = r;
+				}
+			}
+		if (left == 0.0)
+			{
+			const double s  = a[0] + a[1];
+			const double bp = s - a[0];
+			const double e  = (a[0] - (s - bp)) + (a[1] - bp);
+			// the exact sum is s + e and s is it rounded once; the mean is one IEEE division when e is zero, else a
+			// 128-bit one (is_mean_of_two) unless e lies too far below s for that
+			if (xs_finite (s) && ((e == 0.0) || is_mean_of_two (s, e, count, &out->mean)))
+				{
+				out->sum = s + 0.0;
+				if (e == 0.0) out->mean = s / (double) count;
+				return GDSP_OK;
+				}
+			}
+		}
+	uint64_t img[GDSP_XSUM_WORDS];
+	memset (img, 0, sizeof(img));
+	for (uint32_t k=0 ; k<npieces ; k++)
+		{
+		if (pieces[k].flag == 0) { gdsp_xsum_add_host (img, pieces[k].a0);  gdsp_xsum_add_host (img, pieces[k].a1);  continue; }
+		for (int w=0 ; w<GDSP_XSUM_DIGITS ; w++) img[w] += images[w];
+		images += GDSP_XSUM_WORDS;
+		}
+	img[GDSP_XSUM_WORD_INF] = 0;
+	out->sum  = gdsp_xsum_round (img);
+	out->mean = gdsp_xsum_div_round (img, count);
+	out->image = 1;
+	return GDSP_OK;
+	}
+
+int gdsp_interval_stats_batch (const gdsp_batch_item* items, int nitems, const uint32_t* h_vec, const uint32_t* h_start,
+                               const uint32_t* h_end, uint32_t count, double lo, double hi, gdsp_interval_stat* h_out, void* stream)
+	{
+	memset (isLast, 0, sizeof(isLast));
+	for (int k=0 ; k<4 ; k++) isTimes[k] = 0;
+	if (count == 0) return GDSP_OK;
+	GDSP_REQUIRE ((h_start != NULL) && (h_end != NULL), "NULL interval arrays");
+	GDSP_REQUIRE (h_out != NULL, "NULL result array");
+	GDSP_REQUIRE ((items != NULL) && (nitems > 0), "no vectors");
+	for (int k=0 ; k<nitems ; k++)
+		GDSP_REQUIRE ((items[k].n == 0) || ((items[k].d_in != NULL) && ((((uintptr_t) items[k].d_in) & 7) == 0)), "a vector must be 8-byte aligned");
+	for (uint32_t i=0 ; i<count ; i++)
+		{
+		const uint32_t v = (h_vec != NULL)? h_vec[i] : 0;
+		GDSP_REQUIRE (v < (uint32_t) nitems, "an interval names a vector beyond the table");
+		GDSP_REQUIRE (h_start[i] < h_end[i], "an interval must have start < end");
+		GDSP_REQUIRE (h_end[i] <= items[v].n, "an interval ends beyond its vector");
+		}
+	hipStream_t s = gdsp_stream (stream);
+	hipEvent_t ev0, ev1;
+	GDSP_HIP_TRY (hipEventCreate (&ev0));
+	if (hipEventCreate (&ev1) != hipSuccess) { (void) hipEventDestroy (ev0);  gdsp_set_error ("gdsp_interval_stats: no event");  return GDSP_EHIP; }
+	int rc = GDSP_OK;
+	std::vector<uint32_t> sel;
+	for (int v0=0 ; (v0<nitems) && (rc == GDSP_OK) ; v0+=GDSP_BATCH_MAX)         // a table of vectors at a time
+		{
+		const int nvec = std::min (GDSP_BATCH_MAX, nitems - v0);
+		IsVector vecs[GDSP_BATCH_MAX];
+		uint32_t tiles = 0;
+		for (int k=0 ; k<nvec ; k++)
+			{
+			vecs[k].v = items[v0+k].d_in;  vecs[k].n = items[v0+k].n;
+			vecs[k].lead  = ((items[v0+k].n != 0) && !gdsp_aligned16 (items[v0+k].d_in))? 1 : 0;
+			vecs[k].tile0 = tiles;
+			tiles += (uint32_t) (((uint64_t) vecs[k].n + vecs[k].lead + IS_TILE - 1) / IS_TILE);
+			}
+		// the caller's order, cut where a launch is full
+		uint64_t pieces = 0;
+		sel.clear ();
+		for (uint32_t i=0 ; (i<=count) && (rc == GDSP_OK) ; i++)
+			{
+			uint64_t mine = 0;
+			if (i < count)
+				{
+				const int v = (h_vec != NULL)? (int) h_vec[i] : 0;
+				if ((v < v0) || (v >= v0 + nvec)) continue;
+				const uint64_t fs = (uint64_t) h_start[i] + vecs[v-v0].lead, fe = (uint64_t) h_end[i] + vecs[v-v0].lead;
+				mine = (fe - 1) / IS_TILE - fs / IS_TILE + 1;
+				}
+			if (!sel.empty () && ((i == count) || (pieces + mine > IS_CHUNK_PIECES)))
+				{
+				rc = is_launch (vecs, nvec, v0, tiles, sel.data (), (uint32_t) sel.size (), h_vec, h_start, h_end, lo, hi, h_out, s, ev0, ev1);
+				sel.clear ();  pieces = 0;
+				}
+			if (i < count) { sel.push_back (i);  pieces += mine; }
+			}
+		}
+	(void) hipEventDestroy (ev0);  (void) hipEventDestroy (ev1);
+	return rc;
+	}
+
+int gdsp_interval_stats (const double* d_v, uint32_t n, const uint32_t* h_start, const uint32_t* h_end, uint32_t count,
+                         double lo, double hi, gdsp_interval_stat* h_out, void* stream)
+	{
+	gdsp_batch_item item;
+	item.d_in = d_v;  item.d_out = NULL;  item.n = n;
+	return gdsp_interval_stats_batch (&item, 1, NULL, h_start, h_end, count, lo, hi, h_out, stream);
+	}
+
+void gdsp_interval_stats_last  (uint64_t out[4]) { memcpy (out, isLast, sizeof(isLast)); }
+void gdsp_interval_stats_times (double ms[4])    { memcpy (ms, isTimes, sizeof(isTimes)); }
+
+} // extern "C"

@@ -28,12 +28,12 @@
 #include <vector>
 #include <algorithm>
 #include "gdsp_common.h"
+#include "gdsp_xsum_dev.h"                              // xs_split, xs_deposit, xs_grow: shared with gdsp_intervalstats.hip
 
 #define XS_THREADS    256
 #define XS_UNROLL     8                               // 16-byte loads in flight per lane
 #define XS_TILE       (XS_THREADS * XS_UNROLL * 2)    // 4096 values = 32 KiB
 #define XS_MAX_BLOCKS (256 * 4)                 // every workgroup resident (5 fit on a CU): equal shares finish together
-#define XS_K          2                               // terms of a lane's expansion
 #define XS_D          GDSP_XSUM_DIGITS
 
 static_assert (GDSP_XSUM_WORDS == 72 && XS_D == 68, "the layout below");
@@ -50,81 +50,6 @@ struct XsBatch
 	uint32_t      tile0[GDSP_BATCH_MAX + 1];
 	uint32_t      nvec;
 	};
-
-// a finite double as three signed digits at word w: x = (c0 + c1 2^32 + c2 2^64) 2^(32w-1074), each |c| < 2^32
-__host__ __device__ __forceinline__ void xs_split (double x, uint32_t& w, uint64_t& c0, uint64_t& c1, uint64_t& c2)
-	{
-	union { double d; uint64_t u; } b;
-	b.d = x;
-	const uint32_t be = (uint32_t) (b.u >> 52) & 0x7FF;
-	uint64_t mant = b.u & 0xFFFFFFFFFFFFFull;
-	uint32_t shift = 0;                                    // weight of mant's lowest bit: 2^(shift-1074)
-	if (be != 0) { mant |= 1ull << 52;  shift = be - 1; }
-	w = shift >> 5;
-	const uint32_t r  = shift & 31;
-	const uint64_t lo = mant << r;
-	const uint64_t hi = (r == 0)? 0 : (mant >> (64 - r));
-	c0 = lo & 0xFFFFFFFFull;  c1 = lo >> 32;  c2 = hi;
-	if (b.u >> 63) { c0 = 0 - c0;  c1 = 0 - c1;  c2 = 0 - c2; }     // two's complement: the words add as signed integers
-	}
-
-__device__ __forceinline__ void xs_deposit (unsigned long long* acc, double x)
-	{
-	uint32_t w;  uint64_t c0, c1, c2;
-	xs_split (x, w, c0, c1, c2);
-	if (c0 != 0) atomicAdd (&acc[w],     (unsigned long long) c0);
-	if (c1 != 0) atomicAdd (&acc[w + 1], (unsigned long long) c1);
-	if (c2 != 0) atomicAdd (&acc[w + 2], (unsigned long long) c2);
-	}
-
-__device__ __forceinline__ bool xs_finite (double x) { return fabs (x) <= DBL_MAX; }
-
-// a[] += x exactly, the careful way: TwoSum through the terms; what is left after the last one (or a summand whose TwoSum
-// overflows, which then leaves the term it met unchanged) goes to the LDS image
-__device__ __forceinline__ void xs_grow_careful (double (&a)[XS_K], double x, unsigned long long* acc)
-	{
-	double spill = 0.0;
-#pragma unroll
-	for (int k=0 ; k<XS_K ; k++)
-		{
-		const double s  = __dadd_rn (a[k], x);
-		const double bp = __dsub_rn (s, a[k]);
-		const double e  = __dadd_rn (__dsub_rn (a[k], __dsub_rn (s, bp)), __dsub_rn (x, bp));
-		const bool   ok = xs_finite (s) && xs_finite (e);   // an overflow anywhere leaves +-inf or NaN in s or e
-		a[k]  = ok? s : a[k];
-		spill = ok? spill : x;
-		x     = ok? e : 0.0;
-		}
-	if ((x != 0.0) || (spill != 0.0))
-		{
-		xs_deposit (acc, x);
-		xs_deposit (acc, spill);
-		atomicAdd (&acc[GDSP_XSUM_WORD_FLUSHES], 1ull);
-		}
-	}
-
-// a[] += x exactly.  The fast path runs the TwoSums unchecked: an overflow in any of them leaves NaN in the final
-// residual, so a residual that is not exactly zero -- a real one, or that NaN -- sends the lane back to the terms it
-// had and through the careful form (rare on real data; a branch the other lanes skip)
-__device__ __forceinline__ void xs_grow (double (&a)[XS_K], double x, unsigned long long* acc)
-	{
-	double keep[XS_K], r = x;
-#pragma unroll
-	for (int k=0 ; k<XS_K ; k++)
-		{
-		keep[k] = a[k];
-		const double s  = __dadd_rn (a[k], r);
-		const double bp = __dsub_rn (s, a[k]);
-		r    = __dadd_rn (__dsub_rn (a[k], __dsub_rn (s, bp)), __dsub_rn (r, bp));
-		a[k] = s;
-		}
-	if (r != 0.0)
-		{
-#pragma unroll
-		for (int k=0 ; k<XS_K ; k++) a[k] = keep[k];
-		xs_grow_careful (a, x, acc);
-		}
-	}
 
 // PASS 1 adds v, PASS 2 adds fl(fl(v - mean)^2); WINDOWED: the window is above 1
 template <int PASS, bool WINDOWED>
@@ -311,7 +236,7 @@ static inline bool xs_bit (const std::vector<uint32_t>& L, int64_t i)
 	{ return (i >= 0) && ((size_t) (i >> 5) < L.size ()) && ((L[i >> 5] >> (i & 31)) & 1); }
 
 // (-1)^neg * (L + something in (0,1) when sticky) * 2^scale, rounded once to nearest, ties to even
-static double xs_round_limbs (const std::vector<uint32_t>& L, bool sticky, int scale, bool neg)
+double xs_round_limbs (const std::vector<uint32_t>& L, bool sticky, int scale, bool neg)      // (gdsp_xsum_dev.h)
 	{
 	int64_t h = -1;
 	for (int64_t w=(int64_t) L.size ()-1 ; (w>=0) && (h<0) ; w--)

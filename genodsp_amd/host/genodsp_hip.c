@@ -63,6 +63,9 @@ dspprototypes(op_sliding_percentile) dspprototypes(op_sliding_median)
 dspprototypes(op_stats)          dspprototypes(op_normalize)     dspprototypes(op_multiply_constant)
 dspprototypes(op_divide_constant)
 #endif
+#ifdef GDSP_INTERVAL_STATS                             /* not in the reference: ops_statsover.c */
+dspprototypes(op_statsover)
+#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
@@ -116,6 +119,10 @@ static dspinfo dspTable[] =
 	 dspinforecord("normalize"     , op_normalize)      ,
 	 dspinforecord("multiplyconst" , op_multiply_constant), dspinfoalias ("multiply_const"), dspinfoalias ("scale"),
 	 dspinforecord("divideconst"   , op_divide_constant), dspinfoalias ("divide_const")
+#endif
+#ifdef GDSP_INTERVAL_STATS                             /* the signal quantified over the intervals of a file, after those */
+	 , dspinforecord("statsover"   , op_statsover)      , dspinfoalias ("stats_over")     , dspinfoalias ("intervalstats"),
+	 dspinfoalias ("interval_stats")
 #endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS
@@ -847,6 +854,9 @@ static int pipeline_wants_partners (void)
 #ifdef GDSP_GENOME_STATS
 		  op_stats_apply, op_normalize_apply, op_multiply_constant_apply, op_divide_constant_apply,
 #endif
+#ifdef GDSP_INTERVAL_STATS
+		  op_statsover_apply,
+#endif
 		};
 	if (shardBases) return true;                               /* (stretches and their runs: not worth a second rule) */
 	for (dspop* op=pipeline ; op!=NULL ; op=op->next)
@@ -1160,6 +1170,16 @@ void ib_add (spec* s, u32 start, u32 end, valtype val)
 	}
 
 u64 ib_pending (void) { return pendTotal; }
+
+/* the pending intervals as they are, for an operator that hands them to the device itself (ops_statsover.c; like the
+ * other services, there whatever operators the build holds) */
+int ib_chromosomes (void) { return numChroms; }
+
+u32 ib_pending_of (int ci, spec** s, u32** start, u32** end, valtype** val)
+	{
+	*s = chromsSorted[ci];  *start = pend[ci].start;  *end = pend[ci].end;  *val = pend[ci].val;
+	return pend[ci].count;
+	}
 
 static void grow (void** h, void** d, size_t* cap, size_t want, size_t elem)
 	{
@@ -1589,6 +1609,8 @@ void report_intervals (FILE* f, int precision, int noValues, int collapse, int u
 /* read_all_chromosomes / write_all_chromosomes, genodsp.c:1718-1792: the signal as text, ten decimals, runs
  * collapsed, zero stretches left out; read back over a cleared genome.  (percentile --preserve: values come
  * back rounded to ten decimals, exactly as they do in the reference.) */
+char* put_value_fixed (char* p, valtype v, int precision) { return put_fixed (p, v, precision); }   /* (ops_statsover.c's table) */
+
 void write_all_chromosomes (char* filename)
 	{
 	FILE* f = fopen (filename, "wt");
@@ -2100,6 +2122,10 @@ int main (int argc, char** argv)
 				for (int i=0 ; chromsSorted[i]!=NULL ; i++) total += chromsSorted[i]->length;
 				sync_all_devices ();
 				if (stopOp->funcApply == op_show_variables_apply) ;
+#ifdef GDSP_INTERVAL_STATS
+				else if (op_statsover_is (stopOp))                 /* 8 B per base of interval length */
+					wall_phase (stopOp, stopOp->name, now_ms () - t0, op_statsover_bases (stopOp), "bases", 8);
+#endif
 				else if ((intervalsRead != ivBefore) && (stopOp->funcApply != op_percentile_apply))
 					{
 					char label[160];

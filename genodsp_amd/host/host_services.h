@@ -82,6 +82,14 @@ int   op_const_is         (dspop* op);       /* multiplyconst / divideconst: per
 int   op_const_batch      (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
 int   op_stats_is_stop    (dspop* op);       /* stats / normalize: whole-genome, on the signal's parts as they are */
 int   op_stats_is_normalize (dspop* op);
+/* ops_statsover.c (statsover; compiled in with -DGDSP_INTERVAL_STATS) and what the driver lends it: the pending
+ * intervals of chromsSorted[ci] as ib_add left them (ib_begin forgets them), and the report's "%.*f" (NULL: not a case
+ * for the hand-rolled form, print through printf) */
+int   op_statsover_is     (dspop* op);
+u64   op_statsover_bases  (dspop* op);       /* summed length of the intervals since the last call (--report=gpu) */
+int   ib_chromosomes      (void);
+u32   ib_pending_of       (int ci, spec** s, u32** start, u32** end, valtype** val);
+char* put_value_fixed     (char* p, valtype v, int precision);
 
 /* argument helpers used by every operator's parse function */
 #define OP_SHORT(fn, text)                                                            \

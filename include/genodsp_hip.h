@@ -386,6 +386,43 @@ int gdsp_genome_stats_use_comm (gdsp_comm* comm);     /* NULL switches back to h
 /* what the last gdsp_genome_stats did: [0] n, [1] lane flushes of pass 1, [2] of pass 2, [3] q that were +inf */
 void gdsp_genome_stats_last (uint64_t out[4]);
 
+/* ---- statsover (not in the reference): one signal quantified over many intervals, exact ---------------------------
+ * For a vector v of n doubles, an interval [s, e) with 0 <= s < e <= n, and limits lo, hi:
+ *   the sample of the interval is stats' sample restricted to it: the bases i in [s, e) with !(v[i] < lo) &&
+ *     !(v[i] > hi) and v[i] finite (never NaN, never +-inf).  There is no window here.
+ *   count   the number of sampled bases;
+ *   sum     the exact sum of the sample, rounded once (+-inf only when the rounded value is beyond DBL_MAX);
+ *   mean    the exact sum divided by count, rounded once -- the two figures gdsp_genome_stats gives for that sample;
+ *   min, max  the least and greatest sampled value as IEEE compares them; a result that is a zero is +0.0;
+ *   maxpos  the lowest i in the sample with v[i] == max (the summit);
+ *   count == 0: sum is +0.0, and mean, min, max are NaN and maxpos is UINT32_MAX.
+ * Every figure is a function of the sample alone: nothing depends on tiles, grid, dispatch order, the order of the
+ * intervals or how they overlap.  (No variance per interval: it would take a second pass against each interval's mean.)
+ *
+ * The calls take the intervals as HOST arrays (any order, overlapping and duplicate intervals allowed; start < end <= n
+ * or GDSP_EINVAL), read the signal on the current device without modifying it, wait for the device, and fill a HOST
+ * array of records in the caller's order.  The batch form covers every vector of a device in one launch: interval i
+ * lies on vector items[h_vec[i]] (d_in and n of an item are read; h_vec == NULL: all on items[0]).  Vectors must be
+ * 8-byte aligned.  The device reduces pieces -- an interval cut at multiples of gdsp_interval_stats_tile() values of
+ * the 16-byte aligned frame its vector lies in -- to records (a0 + a1 is the piece's exact sum unless `flag` says a
+ * lane's two-term expansion could not hold it; such a piece is summed again through gdsp_xsum_accumulate_batch), and
+ * gdsp_interval_stats_combine, host code that needs no GPU, turns an interval's pieces into its figures: `images` holds
+ * one GDSP_XSUM_WORDS image per flagged piece, in the pieces' order (NULL when none is flagged).  A record's `image` is 1
+ * when its sum and mean were rounded from the integer image and not from two doubles (a diagnostic). */
+typedef struct gdsp_interval_stat  { uint64_t count;  double sum, mean, min, max;  uint32_t maxpos, image; } gdsp_interval_stat;
+typedef struct gdsp_interval_piece { double a0, a1, min, max;  uint32_t count, maxpos, flag, reserved; } gdsp_interval_piece;
+uint32_t gdsp_interval_stats_tile (void);
+int gdsp_interval_stats       (const double* d_v, uint32_t n, const uint32_t* h_start, const uint32_t* h_end, uint32_t count,
+                               double lo, double hi, gdsp_interval_stat* h_out, void* stream);
+int gdsp_interval_stats_batch (const gdsp_batch_item* items, int nitems, const uint32_t* h_vec, const uint32_t* h_start,
+                               const uint32_t* h_end, uint32_t count, double lo, double hi, gdsp_interval_stat* h_out, void* stream);
+int gdsp_interval_stats_combine (const gdsp_interval_piece* pieces, uint32_t npieces, const uint64_t* images, gdsp_interval_stat* out);
+/* what the last gdsp_interval_stats[_batch] did: [0] intervals, [1] pieces, [2] flagged pieces (summed again), [3] intervals
+ * whose sum went through the integer image; and where its time went, in ms: [0] cutting the intervals into pieces (host),
+ * [1] the kernel (HIP events), [2] copies, waiting and flagged pieces, [3] combining the pieces (host) */
+void gdsp_interval_stats_last  (uint64_t out[4]);
+void gdsp_interval_stats_times (double ms[4]);
+
 /* multiplyconst / divideconst / normalize (in place, one pointwise launch per table of 32 vectors): v = fl(v * c),
  * fl(v / c) (c == 0 is refused), fl(fl(v - center) / scale) (scale == 0 is refused) */
 int gdsp_multiply_constant       (double* d_v, uint32_t n, double c, void* stream);
