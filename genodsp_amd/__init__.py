@@ -649,6 +649,89 @@ def xsum_add_host(image, x):
     return image
 
 
+# ------------------------------------------------------ histogram (not in the reference) ----
+
+HISTOGRAM_MAX_BINS = 65536
+
+
+def histogram_uniform_edges(lo=0.0, width=1.0, bins=256):
+    """Host, no GPU: the uniform table e[k] = fma(k, width, lo), k = 0 .. bins, each edge rounded once
+    (gdsp_histogram_uniform_edges).  ValueError for a table that is not strictly increasing and finite."""
+    bins = int(bins)
+    if not 1 <= bins <= HISTOGRAM_MAX_BINS:
+        raise ValueError("bins must be 1 .. %d" % HISTOGRAM_MAX_BINS)
+    e = np.empty(bins + 1, np.float64)
+    if lib().gdsp_histogram_uniform_edges(float(lo), float(width), bins, e.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("lo=%r width=%r bins=%d is not a strictly increasing finite table" % (lo, width, bins))
+    return e
+
+
+def _histogram_table(edges, lo, width, bins):
+    """-> (np.float64 table, its number of bins, the uniform hint); ValueError for a table the library would refuse"""
+    if edges is None:
+        return histogram_uniform_edges(lo, width, bins), int(bins), 1
+    e = np.ascontiguousarray(edges, dtype=np.float64)
+    if e.ndim != 1 or not 2 <= e.size <= HISTOGRAM_MAX_BINS + 1:
+        raise ValueError("edges must be a vector of 2 .. %d values" % (HISTOGRAM_MAX_BINS + 1))
+    if not (np.all(np.isfinite(e)) and np.all(e[:-1] < e[1:])):
+        raise ValueError("edges must be finite and strictly increasing")
+    return e, e.size - 1, 0
+
+
+def histogram_accumulate(vecs, counts, edges, window=1, lo=-DBL_MAX, hi=DBL_MAX, uniform=False, stream=None):
+    """Add the sample of vecs (as xsum_sources) to `counts`, a DeviceBuffer of len(edges) + 2 u64 words
+    (gdsp_histogram_accumulate_batch; zero it with gdsp_histogram_init).  uniform: the hint that edges are evenly spaced."""
+    e, nbins, _ = _histogram_table(edges, 0.0, 1.0, 1)
+    assert counts.nbytes >= (nbins + 3) * 8
+    src = xsum_sources(vecs, stream)
+    call("gdsp_histogram_accumulate_batch", src, len(vecs), int(window), float(lo), float(hi),
+         e.ctypes.data_as(C.c_void_p), nbins, 1 if uniform else 0, C.c_void_p(counts.ptr), _sp(stream))
+
+
+def histogram_words(vecs, edges, window=1, lo=-DBL_MAX, hi=DBL_MAX, uniform=False, stream=None):
+    """The len(edges) + 2 words of one accumulate over vecs, as np.uint64: bins, below, above, n."""
+    e, nbins, _ = _histogram_table(edges, 0.0, 1.0, 1)
+    acc = DeviceBuffer((nbins + 3) * 8)
+    call("gdsp_histogram_init", C.c_void_p(acc.ptr), nbins, _sp(stream))
+    histogram_accumulate(vecs, acc, e, window, lo, hi, uniform, stream)
+    return acc.download(np.uint64, nbins + 3, stream=stream)
+
+
+def genome_histogram(vecs, edges=None, lo=0.0, width=1.0, bins=256, window=1, min=-DBL_MAX, max=DBL_MAX, allreduce=None,
+                     stream=None, uniform=None):
+    """(counts, below, above, n) of the sampled genome (gdsp_genome_histogram): counts[k] values v with
+    e[k] <= v < e[k+1], below those under e[0], above those at or over e[-1], n all of them.  The table is `edges`, or
+    the uniform one of histogram_uniform_edges(lo, width, bins).  The sample is genome_stats': every window-th value
+    counted from each chromosome's first base with min <= v <= max (never NaN or +-inf).  vecs: as xsum_sources.
+    allreduce(np.uint64 array, "sum") -> the array summed over ranks (None: one rank).  uniform: force the hint on or off
+    (None: on for a uniform table, off for `edges`); the words do not depend on it."""
+    e, nbins, hint = _histogram_table(edges, lo, width, bins)
+    if uniform is not None:
+        hint = 1 if uniform else 0
+    src = xsum_sources(vecs, stream)
+    out = np.zeros(nbins + 3, np.uint64)
+    failure = []
+
+    def reduce(_ctx, words, n, op):
+        try:
+            arr = np.ctypeslib.as_array(words, shape=(n,))
+            arr[:] = allreduce(arr.copy(), ("sum", "min", "max")[op])
+            return 0
+        except Exception as ex:          # an exception must not unwind through the C frames
+            failure.append(ex)
+            return 1
+
+    cb = REDUCE_FN(reduce) if allreduce is not None else C.cast(None, REDUCE_FN)
+    try:
+        call("gdsp_genome_histogram", src, len(vecs), int(window), float(min), float(max), e.ctypes.data_as(C.c_void_p),
+             nbins, hint, cb, None, out.ctypes.data_as(C.c_void_p))
+    except GdspError:
+        if failure:
+            raise failure[0]
+        raise
+    return out[:nbins].copy(), int(out[nbins]), int(out[nbins + 1]), int(out[nbins + 2])
+
+
 # ------------------------------------------------------ statsover (not in the reference) ----
 
 INTERVAL_STAT = np.dtype([("count", np.uint64), ("sum", np.float64), ("mean", np.float64), ("min", np.float64),

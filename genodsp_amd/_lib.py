@@ -158,6 +158,12 @@ SIGNATURES = {
     "gdsp_interval_stats_combine": (_int, [_vp, _u32, _vp, _vp]),
     "gdsp_interval_stats_last": (None, [_vp]),
     "gdsp_interval_stats_times": (None, [_vp]),
+    # histogram (not in the reference)
+    "gdsp_histogram_uniform_edges": (_int, [_f64, _f64, _u32, _vp]),
+    "gdsp_histogram_init": (_int, [_vp, _u32, _vp]),
+    "gdsp_histogram_accumulate_batch": (_int, [_vp, _int, _u32, _f64, _f64, _vp, _u32, _int, _vp, _vp]),
+    "gdsp_genome_histogram": (_int, [_vp, _int, _u32, _f64, _f64, _vp, _u32, _int, _vp, _vp, _vp]),
+    "gdsp_genome_histogram_use_comm": (_int, [_vp]),
     "gdsp_multiply_constant": (_int, [_vp, _u32, _f64, _vp]),
     "gdsp_divide_constant": (_int, [_vp, _u32, _f64, _vp]),
     "gdsp_standardize": (_int, [_vp, _u32, _f64, _f64, _vp]),

@@ -66,6 +66,9 @@ dspprototypes(op_divide_constant)
 #ifdef GDSP_INTERVAL_STATS                             /* not in the reference: ops_statsover.c */
 dspprototypes(op_statsover)
 #endif
+#ifdef GDSP_HISTOGRAM                                  /* not in the reference: ops_histogram.c */
+dspprototypes(op_histogram)
+#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
@@ -123,6 +126,9 @@ static dspinfo dspTable[] =
 #ifdef GDSP_INTERVAL_STATS                             /* the signal quantified over the intervals of a file, after those */
 	 , dspinforecord("statsover"   , op_statsover)      , dspinfoalias ("stats_over")     , dspinfoalias ("intervalstats"),
 	 dspinfoalias ("interval_stats")
+#endif
+#ifdef GDSP_HISTOGRAM                                  /* the genome-wide distribution of the values, after those */
+	 , dspinforecord("histogram"   , op_histogram)      , dspinfoalias ("hist")           , dspinfoalias ("distribution")
 #endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS
@@ -628,6 +634,9 @@ static void ensure_device_comm (void)
 #ifdef GDSP_GENOME_STATS
 	check_gdsp (gdsp_genome_stats_use_comm (deviceComm), "hand the communicator to stats");
 #endif
+#ifdef GDSP_HISTOGRAM
+	check_gdsp (gdsp_genome_histogram_use_comm (deviceComm), "hand the communicator to histogram");
+#endif
 	if (trackOperations)
 		{
 		int version = 0;
@@ -856,6 +865,9 @@ static int pipeline_wants_partners (void)
 #endif
 #ifdef GDSP_INTERVAL_STATS
 		  op_statsover_apply,
+#endif
+#ifdef GDSP_HISTOGRAM
+		  op_histogram_apply,
 #endif
 		};
 	if (shardBases) return true;                               /* (stretches and their runs: not worth a second rule) */
@@ -2103,6 +2115,9 @@ int main (int argc, char** argv)
 #ifdef GDSP_GENOME_STATS
 			if (op_stats_is_stop (stopOp)) onParts = true;           /* (normalize rewrites halo and owner alike) */
 #endif
+#ifdef GDSP_HISTOGRAM
+			if (op_histogram_is_stop (stopOp)) onParts = true;       /* (reads the parts as they are, each with its `first`) */
+#endif
 			if (!onParts) to_whole ();                         /* file-driven operators address whole chromosomes */
 			double t0 = now_ms ();
 			u64 ivBefore = intervalsRead;
@@ -2139,6 +2154,9 @@ int main (int argc, char** argv)
 #ifdef GDSP_GENOME_STATS
 					if (op_stats_is_stop (stopOp)) bpb = op_stats_is_normalize (stopOp)? 32 : 16;   /* 8 B/base per stats pass */
 #endif
+#ifdef GDSP_HISTOGRAM
+					if (op_histogram_is_stop (stopOp)) bpb = 8;              /* one read of the signal */
+#endif
 					wall_phase (stopOp, stopOp->name, now_ms () - t0, total, "bases", bpb);
 					}
 				}
@@ -2170,6 +2188,9 @@ int main (int argc, char** argv)
 		{ next = op->next;  free (op->name);  (*op->funcFree) (op); }
 #ifdef GDSP_GENOME_STATS
 	if (deviceComm != NULL) gdsp_genome_stats_use_comm (NULL);
+#endif
+#ifdef GDSP_HISTOGRAM
+	if (deviceComm != NULL) gdsp_genome_histogram_use_comm (NULL);
 #endif
 	if (deviceComm != NULL) { gdsp_percentiles_use_comm (NULL);  gdsp_comm_destroy (deviceComm); }
 	return EXIT_SUCCESS;

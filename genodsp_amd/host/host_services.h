@@ -87,6 +87,8 @@ int   op_stats_is_normalize (dspop* op);
  * for the hand-rolled form, print through printf) */
 int   op_statsover_is     (dspop* op);
 u64   op_statsover_bases  (dspop* op);       /* summed length of the intervals since the last call (--report=gpu) */
+/* ops_histogram.c (histogram; compiled in with -DGDSP_HISTOGRAM) */
+int   op_histogram_is_stop (dspop* op);      /* whole-genome, on the signal's parts as they are; the signal is only read */
 int   ib_chromosomes      (void);
 u32   ib_pending_of       (int ci, spec** s, u32** start, u32** end, valtype** val);
 char* put_value_fixed     (char* p, valtype v, int precision);

@@ -423,6 +423,35 @@ int gdsp_interval_stats_combine (const gdsp_interval_piece* pieces, uint32_t npi
 void gdsp_interval_stats_last  (uint64_t out[4]);
 void gdsp_interval_stats_times (double ms[4]);
 
+/* ---- histogram (not in the reference): the genome-wide distribution of the values, exact, in one pass ---------------
+ * The sample is stats': every window-th value counted from each chromosome's first base (a source carries `first`) whose
+ * value v satisfies !(v < lo) && !(v > hi), finite values only (never NaN, never +-inf); n is its size.
+ * The bins are an edge table e[0] < e[1] < ... < e[B] of finite doubles, 1 <= B <= 65536: a sampled v belongs to bin k
+ * iff e[k] <= v < e[k+1] as IEEE compares them (-0.0 falls where +0.0 falls), is `below` when v < e[0] and `above` when
+ * v >= e[B].  Uniform bins are the table e[k] = fma (k, width, lo), each edge rounded once: gdsp_histogram_uniform_edges,
+ * host code that needs no GPU, fills h_edges[0 .. nbins] and refuses (GDSP_EINVAL) a lo / width / nbins whose table is not
+ * strictly increasing and finite.
+ * The result is nbins + 3 u64 words: counts[0 .. B) the bins, counts[B] below, counts[B+1] above, counts[B+2] = n, the sum
+ * of all the others.  It is a function of the sample and the table alone: it does not depend on tiles, grid, dispatch
+ * order, the cut of the genome, devices or ranks, and the words of two samples add to the words of their union
+ * (all-reduce them with op 0).
+ * `uniform` != 0 is a hint that the table is (close to) evenly spaced: the bin is guessed by one multiplication and then
+ * corrected by comparing against the table, which alone decides; any table gives the same words with and without it.
+ * The signal is only read.  Sources as for the xsum calls (8-byte aligned, on the current device for the _batch call). */
+int gdsp_histogram_uniform_edges (double lo, double width, uint32_t nbins, double* h_edges);
+int gdsp_histogram_init (uint64_t* d_counts, uint32_t nbins, void* stream);          /* zero nbins + 3 words */
+/* add the sample of every source to d_counts (one launch per 32 sources; h_edges is a HOST table of nbins + 1 values) */
+int gdsp_histogram_accumulate_batch (const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                                     const double* h_edges, uint32_t nbins, int uniform, uint64_t* d_counts, void* stream);
+/* end to end, like gdsp_genome_stats: sources may sit on several devices of this process (each device's work is queued on
+ * the stream of its first source; the words are added on the host, or all-reduced in HBM through the communicator given
+ * to gdsp_genome_histogram_use_comm); with one process per GPU pass `reduce` (op 0).  h_counts: nbins + 3 HOST words; no
+ * sources, or an empty sample: all zeros.  Waits for the pass. */
+int gdsp_genome_histogram (const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                           const double* h_edges, uint32_t nbins, int uniform,
+                           gdsp_reduce_fn reduce, void* reduceCtx, uint64_t* h_counts);
+int gdsp_genome_histogram_use_comm (gdsp_comm* comm);  /* NULL switches back to host sums */
+
 /* multiplyconst / divideconst / normalize (in place, one pointwise launch per table of 32 vectors): v = fl(v * c),
  * fl(v / c) (c == 0 is refused), fl(fl(v - center) / scale) (scale == 0 is refused) */
 int gdsp_multiply_constant       (double* d_v, uint32_t n, double c, void* stream);
