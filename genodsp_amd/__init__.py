@@ -482,8 +482,39 @@ DEVICE_REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_
 SELECT_AUTO, SELECT_RADIX, SELECT_BRACKET = 0, 1, 2
 
 
+import contextlib as _contextlib
 import threading as _threading
 _PERCENTILE_HOOK = _threading.RLock()
+
+
+def _reduce_hook(allreduce, failure):
+    """allreduce(np.uint64 array, "sum"|"min"|"max") -> the reduced array, as the gdsp_reduce_fn of a library call (a
+    NULL one for None).  An exception must not unwind through the C frames: it is kept in `failure` and the library is
+    told that the reduction failed."""
+    if allreduce is None:
+        return C.cast(None, REDUCE_FN)
+
+    def reduce(_ctx, words, n, op):
+        try:
+            arr = np.ctypeslib.as_array(words, shape=(n,))
+            arr[:] = allreduce(arr.copy(), ("sum", "min", "max")[op])
+            return 0
+        except Exception as e:
+            failure.append(e)
+            return 1
+
+    return REDUCE_FN(reduce)
+
+
+@_contextlib.contextmanager
+def _hook_failure_first(failure):
+    """The library's complaint about a failed hook becomes the exception the hook raised."""
+    try:
+        yield
+    except GdspError:
+        if failure:
+            raise failure[0]
+        raise
 
 
 def percentile(vecs, p_thousandths, window=1, lo=-DBL_MAX, hi=DBL_MAX, allreduce=None, stream=None,
@@ -503,15 +534,6 @@ def percentile(vecs, p_thousandths, window=1, lo=-DBL_MAX, hi=DBL_MAX, allreduce
     count = C.c_uint64(0)
     failure = []
 
-    def reduce(_ctx, words, n, op):
-        try:
-            arr = np.ctypeslib.as_array(words, shape=(n,))
-            arr[:] = allreduce(arr.copy(), ("sum", "min", "max")[op])
-            return 0
-        except Exception as e:           # an exception must not unwind through the C frames
-            failure.append(e)
-            return 1
-
     def device_reduce(_ctx, d_words, n, op, s):
         try:
             device_allreduce(d_words, n, ("sum", "min", "max")[op], s)
@@ -521,20 +543,17 @@ def percentile(vecs, p_thousandths, window=1, lo=-DBL_MAX, hi=DBL_MAX, allreduce
             return 1
 
     assert allreduce is None or device_allreduce is None
-    cb = REDUCE_FN(reduce) if allreduce is not None else C.cast(None, REDUCE_FN)
+    cb = _reduce_hook(allreduce, failure)
     dcb = DEVICE_REDUCE_FN(device_reduce) if device_allreduce is not None else None
     # the device hook is state of the library (one per process): installed, used and cleared under one lock, so that
     # two threads calling percentile() cannot swap or clear each other's hook in mid-call
     with _PERCENTILE_HOOK:
         try:
-            if dcb is not None:
-                call("gdsp_percentiles_use_device_reduce", dcb, None)
-            call("gdsp_percentiles", src, len(vecs), int(window), float(lo), float(hi), pts, len(p_thousandths),
-                 int(strategy), int(sample_target), cb, None, vals, C.byref(count))
-        except GdspError:
-            if failure:
-                raise failure[0]
-            raise
+            with _hook_failure_first(failure):
+                if dcb is not None:
+                    call("gdsp_percentiles_use_device_reduce", dcb, None)
+                call("gdsp_percentiles", src, len(vecs), int(window), float(lo), float(hi), pts, len(p_thousandths),
+                     int(strategy), int(sample_target), cb, None, vals, C.byref(count))
         finally:
             if dcb is not None:
                 call("gdsp_percentiles_use_device_reduce", None, None)
@@ -580,23 +599,9 @@ def genome_stats(vecs, window=1, lo=-DBL_MAX, hi=DBL_MAX, allreduce=None, stream
     src = xsum_sources(vecs, stream)
     out = (C.c_double * 5)()
     failure = []
-
-    def reduce(_ctx, words, n, op):
-        try:
-            arr = np.ctypeslib.as_array(words, shape=(n,))
-            arr[:] = allreduce(arr.copy(), ("sum", "min", "max")[op])
-            return 0
-        except Exception as e:           # an exception must not unwind through the C frames
-            failure.append(e)
-            return 1
-
-    cb = REDUCE_FN(reduce) if allreduce is not None else C.cast(None, REDUCE_FN)
-    try:
+    cb = _reduce_hook(allreduce, failure)
+    with _hook_failure_first(failure):
         call("gdsp_genome_stats", src, len(vecs), int(window), float(lo), float(hi), cb, None, out)
-    except GdspError:
-        if failure:
-            raise failure[0]
-        raise
     return dict(zip(("count", "sum", "mean", "variance", "stddev"), [float(x) for x in out]))
 
 
@@ -711,24 +716,10 @@ def genome_histogram(vecs, edges=None, lo=0.0, width=1.0, bins=256, window=1, mi
     src = xsum_sources(vecs, stream)
     out = np.zeros(nbins + 3, np.uint64)
     failure = []
-
-    def reduce(_ctx, words, n, op):
-        try:
-            arr = np.ctypeslib.as_array(words, shape=(n,))
-            arr[:] = allreduce(arr.copy(), ("sum", "min", "max")[op])
-            return 0
-        except Exception as ex:          # an exception must not unwind through the C frames
-            failure.append(ex)
-            return 1
-
-    cb = REDUCE_FN(reduce) if allreduce is not None else C.cast(None, REDUCE_FN)
-    try:
+    cb = _reduce_hook(allreduce, failure)
+    with _hook_failure_first(failure):
         call("gdsp_genome_histogram", src, len(vecs), int(window), float(min), float(max), e.ctypes.data_as(C.c_void_p),
              nbins, hint, cb, None, out.ctypes.data_as(C.c_void_p))
-    except GdspError:
-        if failure:
-            raise failure[0]
-        raise
     return out[:nbins].copy(), int(out[nbins]), int(out[nbins + 1]), int(out[nbins + 2])
 
 
@@ -912,14 +903,11 @@ def percentile_binarize(vecs, p_thousandths, which=0, outs=None, ties_above=Fals
     dcb = DEVICE_REDUCE_FN(device_reduce) if device_allreduce is not None else None
     _PERCENTILE_HOOK.acquire()
     try:
-        if dcb is not None:
-            call("gdsp_percentiles_use_device_reduce", dcb, None)
-        call("gdsp_percentiles_binarize", src, len(vecs), int(window), float(lo), float(hi), pts, len(p_thousandths),
-             int(strategy), int(sample_target), C.cast(None, REDUCE_FN), None, vals, C.byref(count), C.byref(fuse), C.byref(one_pass))
-    except GdspError:
-        if failure:
-            raise failure[0]
-        raise
+        with _hook_failure_first(failure):
+            if dcb is not None:
+                call("gdsp_percentiles_use_device_reduce", dcb, None)
+            call("gdsp_percentiles_binarize", src, len(vecs), int(window), float(lo), float(hi), pts, len(p_thousandths),
+                 int(strategy), int(sample_target), C.cast(None, REDUCE_FN), None, vals, C.byref(count), C.byref(fuse), C.byref(one_pass))
     finally:
         if dcb is not None:
             call("gdsp_percentiles_use_device_reduce", None, None)

@@ -18,6 +18,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include <mutex>
+#include <vector>
+#include <algorithm>
 #include <rccl/rccl.h>
 #include "gdsp_common.h"
 
@@ -175,3 +177,68 @@ int gdsp_comm_allreduce_f64 (gdsp_comm* comm, double* const* d_bufs, size_t coun
 	{ return comm_allreduce (comm, (void* const*) d_bufs, count, ncclFloat64, op, streams); }
 
 } // extern "C"
+
+// ---- one pass of a whole-genome operator that only reads the signal (gdsp_genome_stats, gdsp_genome_histogram) ----
+// The devices are the communicator's ranks, or without one the distinct devices of the sources.  Each gets `words` u64
+// words of its own and runs pass () over its sources on the stream of the first of them; the devices' words are then
+// summed -- by the communicator's all-reduce, after which rank 0 holds what every rank holds, or on the host -- into
+// h_words, and the caller's hook (the other ranks of a larger job) has the last word.
+int gdsp_reduce_sources (const char* who, const char* what, gdsp_comm* comm, const gdsp_xsum_source* sources, int nsources,
+                         size_t words, const gdsp_device_pass& pass, gdsp_reduce_fn reduce, void* reduceCtx, uint64_t* h_words)
+	{
+	int home = 0;
+	GDSP_HIP_TRY (hipGetDevice (&home));
+	std::vector<int> devices;
+	if (comm != NULL)
+		for (int r=0 ; r<gdsp_comm_size (comm) ; r++) devices.push_back (gdsp_comm_device (comm, r));
+	else
+		{
+		for (int i=0 ; i<nsources ; i++) devices.push_back (sources[i].device);
+		std::sort (devices.begin (), devices.end ());
+		devices.erase (std::unique (devices.begin (), devices.end ()), devices.end ());
+		if (devices.empty ()) devices.push_back (home);
+		}
+	for (int i=0 ; i<nsources ; i++)
+		{
+		if (std::find (devices.begin (), devices.end (), sources[i].device) != devices.end ()) continue;
+		gdsp_set_error ("%s: a source sits on a device the communicator does not hold", who);
+		return GDSP_EINVAL;
+		}
+	const size_t nd = devices.size ();
+	std::vector<uint64_t*> accs (nd, NULL);
+	std::vector<void*>     streams (nd, NULL);
+	std::vector<gdsp_xsum_source> mine;
+	std::vector<uint64_t>  h (words);
+	int rc = GDSP_OK;
+	for (size_t d=0 ; (d<nd) && (rc == GDSP_OK) ; d++)
+		{
+		GDSP_HIP_TRY (hipSetDevice (devices[d]));
+		mine.clear ();
+		for (int i=0 ; i<nsources ; i++) { if (sources[i].device == devices[d]) mine.push_back (sources[i]); }
+		if (!mine.empty ()) streams[d] = mine[0].stream;
+		if (hipMalloc ((void**) &accs[d], words * sizeof(uint64_t)) != hipSuccess)
+			{ accs[d] = NULL;  gdsp_set_error ("%s: no device memory for the %s", who, what);  rc = GDSP_ENOMEM;  break; }
+		rc = pass (mine.data (), (int) mine.size (), accs[d], streams[d]);
+		}
+	if ((rc == GDSP_OK) && (comm != NULL))
+		rc = gdsp_comm_allreduce_u64 (comm, accs.data (), words, 0, streams.data ());
+	std::fill (h_words, h_words + words, (uint64_t) 0);
+	for (size_t d=0 ; d<nd ; d++)
+		{
+		if (accs[d] == NULL) continue;
+		(void) hipSetDevice (devices[d]);
+		if ((rc == GDSP_OK) && ((comm == NULL) || (d == 0)))         // (with the communicator every rank holds the sum)
+			{
+			if (hipMemcpyAsync (h.data (), accs[d], words * sizeof(uint64_t), hipMemcpyDeviceToHost, gdsp_stream (streams[d])) != hipSuccess
+			 || hipStreamSynchronize (gdsp_stream (streams[d])) != hipSuccess)
+				{ gdsp_set_error ("%s: reading the %s back failed", who, what);  rc = GDSP_EHIP; }
+			else for (size_t w=0 ; w<words ; w++) h_words[w] += h[w];
+			}
+		else (void) hipStreamSynchronize (gdsp_stream (streams[d]));
+		(void) hipFree (accs[d]);
+		}
+	(void) hipSetDevice (home);
+	if ((rc == GDSP_OK) && (reduce != NULL) && (reduce (reduceCtx, h_words, words, 0) != 0))
+		{ gdsp_set_error ("%s: the caller's reduction failed", who);  rc = GDSP_EHIP; }
+	return rc;
+	}

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdio.h>
+#include <functional>
 #include "genodsp_hip.h"
 
 // error plumbing: the C ABI returns codes; the message is kept per thread
@@ -55,6 +56,15 @@ bool gdsp_morph_blocks_batch (const gdsp_batch_item* items, int nitems, uint32_t
 // gdsp_fir_slide.hip: `smooth W=101` in the reference's arithmetic with every product computed once (sliding accumulators)
 bool gdsp_fir_slide_wanted (uint64_t bases);
 int  gdsp_fir_slide_batch (const gdsp_batch_item* items, int nitems, const double* h_taps, void* stream);
+
+// gdsp_comm.hip: one pass of a whole-genome operator that only reads the signal, over every device that holds some of
+// it.  pass (mine, nmine, d_words, stream): with the device current, initialise its `words` words d_words and launch
+// over its sources mine[0 .. nmine) on the stream.  The words of all devices are summed into h_words (the communicator's
+// all-reduce, or on the host when comm is NULL), then handed to the caller's hook `reduce` when there is one.  who,
+// what: the entry point and its words ("accumulator", "counts") as the error messages name them.
+typedef std::function<int (const gdsp_xsum_source* mine, int nmine, uint64_t* d_words, void* stream)> gdsp_device_pass;
+int  gdsp_reduce_sources (const char* who, const char* what, gdsp_comm* comm, const gdsp_xsum_source* sources, int nsources,
+                          size_t words, const gdsp_device_pass& pass, gdsp_reduce_fn reduce, void* reduceCtx, uint64_t* h_words);
 
 static inline hipStream_t gdsp_stream (void* s) { return (hipStream_t) s; }
 

@@ -4,7 +4,7 @@
 // the tiles, the grid, the dispatch order, the cut into vectors, the devices or the ranks.
 //
 // The pass (hist_kernel): one launch per table of up to 32 sources, a grid of resident workgroups walking 32 KiB tiles
-// with 16-byte non-temporal loads, sampling by window / first and unaligned heads as gdsp_xsum.hip does.  Inside a tile a
+// with 16-byte non-temporal loads, sampling by window / first and unaligned heads as gdsp_sample.h has them.  Inside a tile a
 // WAVE owns 1024 consecutive values and takes them in eight steps of 128 (lane l holds values 2l and 2l+1 of the step),
 // so that what a wave sees in one step, and from one step to the next, is a contiguous stretch of the chromosome.
 //
@@ -48,6 +48,7 @@
 #include <mutex>
 #include <algorithm>
 #include "gdsp_common.h"
+#include "gdsp_sample.h"                                // the table of sources and which of their values are sampled
 
 // aggregation level (see above): HG_AGGREGATE_SPREAD where a slot has four or more LDS copies, HG_AGGREGATE_HOT where
 // it has fewer and on the large route; -DHG_AGGREGATE=<k> forces both (the A/B)
@@ -70,16 +71,6 @@
 #define HG_MAX_BINS   65536
 #define HG_NONE       0xFFFFFFFFu
 #define HG_MAX_TILES  (1u << 28)                      // per launch; a full grid has at least 512 workgroups: 2^19 + 1 tiles, 2^31 values and a bit each
-
-struct HgBatch                                         // (XsBatch of gdsp_xsum.hip)
-	{
-	const double* base[GDSP_BATCH_MAX];
-	uint32_t      n[GDSP_BATCH_MAX];
-	uint32_t      lead[GDSP_BATCH_MAX];
-	uint32_t      phase[GDSP_BATCH_MAX];
-	uint32_t      tile0[GDSP_BATCH_MAX + 1];
-	uint32_t      nvec;
-	};
 
 // d_pad: the padded table P (nbins + 5 values); topStep: the largest power of two <= nbins + 1 (the search's first step);
 // lo, hi: the sample's limits with a NaN or an infinity replaced by -+DBL_MAX, so that lo <= v && v <= hi is the whole test
@@ -149,7 +140,7 @@ template <> struct HgCounters<false>
 // LDS: counters and table in LDS; UNIFORM: guess first; WINDOWED: the window is above 1; AGG: aggregation level
 template <bool LDS, bool UNIFORM, bool WINDOWED, int AGG>
 __global__ __launch_bounds__(HG_THREADS)
-void hist_kernel (HgBatch B, HgTable T, uint32_t window, unsigned long long* __restrict__ d_counts)
+void hist_kernel (GdspSample B, HgTable T, uint32_t window, unsigned long long* __restrict__ d_counts)
 	{
 	extern __shared__ double hg_lds[];         // LDS: nbins + 5 table values, then (nbins + 2) << copiesLog2 counters; or the cache
 	const uint32_t nslots = T.nbins + 2;
@@ -175,21 +166,12 @@ void hist_kernel (HgBatch B, HgTable T, uint32_t window, unsigned long long* __r
 	uint32_t v = 0;
 	for (uint32_t g=blockIdx.x ; g<tiles ; g+=gridDim.x)
 		{
-		while (B.tile0[v + 1] <= g) v++;
-		const double*  base  = B.base[v];
-		const uint32_t lead  = B.lead[v], phase = B.phase[v];
-		const uint64_t m     = (uint64_t) B.n[v] + lead;              // values of the frame
-		const uint64_t j0    = (uint64_t) (g - B.tile0[v]) * HG_TILE;
-		auto wanted = [&] (double x, uint64_t j) -> bool               // frame index j is source index j - lead
-			{
-			bool in = (x >= T.lo) && (x <= T.hi) && (j >= lead);       // stats' tests; NaN and +-inf never
-			if (WINDOWED)
-				{
-				const uint32_t i = (uint32_t) (j - lead);
-				in = in && (i >= phase) && ((i - phase) % window == 0);
-				}
-			return in;
-			};
+		const GdspSampleTile t = gdsp_sample_tile<HG_TILE> (B, g, v);
+		v = t.v;
+		const double*  base = t.base;
+		const uint64_t m = t.m, j0 = t.j0;
+		auto wanted = [&] (double x, uint64_t j) -> bool               // stats' tests; NaN and +-inf never
+			{ return (x >= T.lo) && (x <= T.hi) && gdsp_sampled<WINDOWED> (t, window, j); };
 		if (j0 + HG_TILE <= m)
 			{
 			// the wave's 1024 values: step u is the 128 values from j0 + (wave*HG_UNROLL + u) * 128
@@ -341,7 +323,7 @@ static int hg_device_table (const double* h_edges, uint32_t nbins, hipStream_t s
 	}
 
 template <bool LDS, bool UNIFORM, int AGG>
-static void hg_dispatch (bool windowed, uint32_t blocks, size_t lds, hipStream_t s, const HgBatch& B, const HgTable& T,
+static void hg_dispatch (bool windowed, uint32_t blocks, size_t lds, hipStream_t s, const GdspSample& B, const HgTable& T,
                          uint32_t window, unsigned long long* d_counts)
 	{
 	if (windowed) hipLaunchKernelGGL ((hist_kernel<LDS, UNIFORM, true, AGG>),  dim3(blocks), dim3(HG_THREADS), lds, s, B, T, window, d_counts);
@@ -378,24 +360,9 @@ static int hist_launch (const gdsp_xsum_source* sources, int nsources, uint32_t 
 	int i = 0;
 	while (i < nsources)
 		{
-		HgBatch B;
-		int k = 0;
-		B.tile0[0] = 0;
-		for ( ; (i<nsources) && (k<GDSP_BATCH_MAX) ; i++)
-			{
-			const gdsp_xsum_source& src = sources[i];
-			if (src.n == 0) continue;
-			GDSP_REQUIRE ((src.d_v != NULL) && ((((uintptr_t) src.d_v) & 7) == 0), "a source must be 8-byte aligned");
-			const uint32_t lead  = gdsp_aligned16 (src.d_v)? 0 : 1;
-			const uint32_t phase = (uint32_t) ((window - src.first % window) % window);
-			if (phase >= src.n) continue;                                  // nothing of it is sampled
-			const uint64_t t = (uint64_t) B.tile0[k] + ((uint64_t) src.n + lead + HG_TILE - 1) / HG_TILE;
-			if ((t > HG_MAX_TILES) && (k > 0)) break;                      // the rest goes into the next launch
-			B.base[k] = src.d_v - lead;  B.n[k] = src.n;  B.lead[k] = lead;  B.phase[k] = phase;
-			B.tile0[++k] = (uint32_t) t;
-			}
-		for (int j=k ; j<GDSP_BATCH_MAX ; j++) { B.base[j] = NULL;  B.n[j] = 0;  B.lead[j] = 0;  B.phase[j] = 0;  B.tile0[j+1] = B.tile0[k]; }
-		B.nvec = (uint32_t) k;
+		GdspSample B;
+		const int k = gdsp_sample_next (B, sources, nsources, &i, window, HG_TILE, HG_MAX_TILES);
+		GDSP_REQUIRE (k >= 0, "a source must be 8-byte aligned");
 		if (k == 0) continue;
 		if (T.d_pad == NULL)
 			{
@@ -460,7 +427,6 @@ extern "C" {
 
 int gdsp_genome_histogram_use_comm (gdsp_comm* comm) { hgComm = comm;  return GDSP_OK; }
 
-// gdsp_genome_stats' one pass (xs_pass, gdsp_xsum.hip) with nbins + 3 words per device
 int gdsp_genome_histogram (const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
                            const double* h_edges, uint32_t nbins, int uniform,
                            gdsp_reduce_fn reduce, void* reduceCtx, uint64_t* h_counts)
@@ -469,60 +435,14 @@ int gdsp_genome_histogram (const gdsp_xsum_source* sources, int nsources, uint32
 	GDSP_REQUIRE ((nsources == 0) || (sources != NULL), "NULL sources");
 	GDSP_REQUIRE (hg_table_ok (h_edges, nbins), "the edge table must hold 2 .. 65537 strictly increasing finite values");
 	GDSP_REQUIRE (!((hgComm != NULL) && (reduce != NULL)), "a host reduction hook next to a communicator");
-	const size_t words = (size_t) nbins + 3;
-	int home = 0;
-	GDSP_HIP_TRY (hipGetDevice (&home));
-	std::vector<int> devices;
-	if (hgComm != NULL)
-		for (int r=0 ; r<gdsp_comm_size (hgComm) ; r++) devices.push_back (gdsp_comm_device (hgComm, r));
-	else
+	auto onDevice = [&] (const gdsp_xsum_source* mine, int nmine, uint64_t* d_counts, void* stream) -> int
 		{
-		for (int i=0 ; i<nsources ; i++) devices.push_back (sources[i].device);
-		std::sort (devices.begin (), devices.end ());
-		devices.erase (std::unique (devices.begin (), devices.end ()), devices.end ());
-		if (devices.empty ()) devices.push_back (home);
-		}
-	for (int i=0 ; i<nsources ; i++)
-		GDSP_REQUIRE (std::find (devices.begin (), devices.end (), sources[i].device) != devices.end (),
-		              "a source sits on a device the communicator does not hold");
-	const size_t nd = devices.size ();
-	std::vector<uint64_t*> accs (nd, NULL);
-	std::vector<void*>     streams (nd, NULL);
-	std::vector<gdsp_xsum_source> mine;
-	std::vector<uint64_t>  h (words);
-	int rc = GDSP_OK;
-	for (size_t d=0 ; (d<nd) && (rc == GDSP_OK) ; d++)
-		{
-		GDSP_HIP_TRY (hipSetDevice (devices[d]));
-		mine.clear ();
-		for (int i=0 ; i<nsources ; i++) { if (sources[i].device == devices[d]) mine.push_back (sources[i]); }
-		if (!mine.empty ()) streams[d] = mine[0].stream;
-		if (hipMalloc ((void**) &accs[d], words * sizeof(uint64_t)) != hipSuccess)
-			{ accs[d] = NULL;  gdsp_set_error ("gdsp_genome_histogram: no device memory for the counts");  rc = GDSP_ENOMEM;  break; }
-		rc = gdsp_histogram_init (accs[d], nbins, streams[d]);
-		if (rc == GDSP_OK) rc = hist_launch (mine.data (), (int) mine.size (), window, lo, hi, h_edges, nbins, uniform, accs[d], streams[d]);
-		}
-	if ((rc == GDSP_OK) && (hgComm != NULL))
-		rc = gdsp_comm_allreduce_u64 (hgComm, accs.data (), words, 0, streams.data ());
-	std::fill (h_counts, h_counts + words, (uint64_t) 0);
-	for (size_t d=0 ; d<nd ; d++)
-		{
-		if (accs[d] == NULL) continue;
-		(void) hipSetDevice (devices[d]);
-		if ((rc == GDSP_OK) && ((hgComm == NULL) || (d == 0)))        // (with the communicator every rank holds the sum)
-			{
-			if (hipMemcpyAsync (h.data (), accs[d], words * sizeof(uint64_t), hipMemcpyDeviceToHost, gdsp_stream (streams[d])) != hipSuccess
-			 || hipStreamSynchronize (gdsp_stream (streams[d])) != hipSuccess)
-				{ gdsp_set_error ("gdsp_genome_histogram: reading the counts back failed");  rc = GDSP_EHIP; }
-			else for (size_t w=0 ; w<words ; w++) h_counts[w] += h[w];
-			}
-		else (void) hipStreamSynchronize (gdsp_stream (streams[d]));
-		(void) hipFree (accs[d]);
-		}
-	(void) hipSetDevice (home);
-	if ((rc == GDSP_OK) && (reduce != NULL) && (reduce (reduceCtx, h_counts, words, 0) != 0))
-		{ gdsp_set_error ("gdsp_genome_histogram: the caller's reduction failed");  rc = GDSP_EHIP; }
-	return rc;
+		int rc = gdsp_histogram_init (d_counts, nbins, stream);
+		if (rc == GDSP_OK) rc = hist_launch (mine, nmine, window, lo, hi, h_edges, nbins, uniform, d_counts, stream);
+		return rc;
+		};
+	return gdsp_reduce_sources ("gdsp_genome_histogram", "counts", hgComm, sources, nsources, (size_t) nbins + 3, onDevice,
+	                            reduce, reduceCtx, h_counts);
 	}
 
 } // extern "C"

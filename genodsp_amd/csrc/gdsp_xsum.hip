@@ -29,6 +29,7 @@
 #include <algorithm>
 #include "gdsp_common.h"
 #include "gdsp_xsum_dev.h"                              // xs_split, xs_deposit, xs_grow: shared with gdsp_intervalstats.hip
+#include "gdsp_sample.h"                                // the table of sources and which of their values are sampled
 
 #define XS_THREADS    256
 #define XS_UNROLL     8                               // 16-byte loads in flight per lane
@@ -38,23 +39,10 @@
 
 static_assert (GDSP_XSUM_WORDS == 72 && XS_D == 68, "the layout below");
 
-// one launch's table: source s is base[s][lead[s] .. lead[s]+n[s]), base 16-byte aligned; its sampled values are those
-// of index i >= phase[s] with (i - phase[s]) % window == 0 (phase: the first index whose chromosome position is a
-// multiple of the window); it owns the tiles [tile0[s], tile0[s+1]) of the frame that starts at base
-struct XsBatch
-	{
-	const double* base[GDSP_BATCH_MAX];
-	uint32_t      n[GDSP_BATCH_MAX];
-	uint32_t      lead[GDSP_BATCH_MAX];
-	uint32_t      phase[GDSP_BATCH_MAX];
-	uint32_t      tile0[GDSP_BATCH_MAX + 1];
-	uint32_t      nvec;
-	};
-
 // PASS 1 adds v, PASS 2 adds fl(fl(v - mean)^2); WINDOWED: the window is above 1
 template <int PASS, bool WINDOWED>
 __global__ __launch_bounds__(XS_THREADS)
-void xsum_kernel (XsBatch B, uint32_t window, double lo, double hi, double mean, unsigned long long* __restrict__ d_acc)
+void xsum_kernel (GdspSample B, uint32_t window, double lo, double hi, double mean, unsigned long long* __restrict__ d_acc)
 	{
 	__shared__ unsigned long long acc[GDSP_XSUM_WORDS];
 	for (int i=threadIdx.x ; i<GDSP_XSUM_WORDS ; i+=XS_THREADS) acc[i] = 0;
@@ -79,18 +67,11 @@ void xsum_kernel (XsBatch B, uint32_t window, double lo, double hi, double mean,
 	uint32_t v = 0;
 	for (uint32_t g=blockIdx.x ; g<T ; g+=gridDim.x)
 		{
-		while (B.tile0[v + 1] <= g) v++;
-		const double*  base  = B.base[v];
-		const uint32_t lead  = B.lead[v], phase = B.phase[v];
-		const uint64_t m     = (uint64_t) B.n[v] + lead;              // values of the frame
-		const uint64_t j0    = (uint64_t) (g - B.tile0[v]) * XS_TILE;
-		auto sampled = [&] (uint64_t j) -> bool                        // frame index j is source index j - lead
-			{
-			if (j < lead) return false;
-			if (!WINDOWED) return true;
-			const uint32_t i = (uint32_t) (j - lead);
-			return (i >= phase) && ((i - phase) % window == 0);
-			};
+		const GdspSampleTile t = gdsp_sample_tile<XS_TILE> (B, g, v);
+		v = t.v;
+		const double*  base = t.base;
+		const uint64_t m = t.m, j0 = t.j0;
+		auto sampled = [&] (uint64_t j) -> bool { return gdsp_sampled<WINDOWED> (t, window, j); };
 		if (j0 + XS_TILE <= m)
 			{
 			const double2* p = reinterpret_cast<const double2*> (base + j0) + threadIdx.x;
@@ -134,18 +115,7 @@ void xsum_kernel (XsBatch B, uint32_t window, double lo, double hi, double mean,
 		if (f != 0) atomicAdd (&acc[GDSP_XSUM_WORD_INF],   (unsigned long long) f);
 		}
 	__syncthreads ();
-	// canonical digits (0 <= digit < 2^32 below the top one): the workgroups' images then add without overflow
-	if (threadIdx.x == 0)
-		{
-		long long carry = 0;
-		for (int w=0 ; w<XS_D-1 ; w++)
-			{
-			const long long x = (long long) acc[w] + carry;
-			carry  = x >> 32;
-			acc[w] = (unsigned long long) (x & 0xFFFFFFFFll);
-			}
-		acc[XS_D-1] += (unsigned long long) carry;
-		}
+	if (threadIdx.x == 0) xs_carry (acc);                    // canonical digits: the workgroups' images then add without overflow
 	__syncthreads ();
 	if ((threadIdx.x < GDSP_XSUM_WORDS) && (acc[threadIdx.x] != 0)) atomicAdd (&d_acc[threadIdx.x], acc[threadIdx.x]);
 	}
@@ -154,14 +124,7 @@ void xsum_kernel (XsBatch B, uint32_t window, double lo, double hi, double mean,
 __global__ void xsum_fold_kernel (unsigned long long* d_acc)
 	{
 	if (threadIdx.x != 0) return;
-	long long carry = 0;
-	for (int w=0 ; w<XS_D-1 ; w++)
-		{
-		const long long x = (long long) d_acc[w] + carry;
-		carry    = x >> 32;
-		d_acc[w] = (unsigned long long) (x & 0xFFFFFFFFll);
-		}
-	d_acc[XS_D-1] += (unsigned long long) carry;
+	xs_carry (d_acc);
 	}
 
 static int xsum_launch (int pass, const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
@@ -174,24 +137,9 @@ static int xsum_launch (int pass, const gdsp_xsum_source* sources, int nsources,
 	int i = 0;
 	while (i < nsources)
 		{
-		XsBatch B;
-		int k = 0;
-		B.tile0[0] = 0;
-		for ( ; (i<nsources) && (k<GDSP_BATCH_MAX) ; i++)
-			{
-			const gdsp_xsum_source& src = sources[i];
-			if (src.n == 0) continue;
-			GDSP_REQUIRE ((src.d_v != NULL) && ((((uintptr_t) src.d_v) & 7) == 0), "a source must be 8-byte aligned");
-			const uint32_t lead  = gdsp_aligned16 (src.d_v)? 0 : 1;
-			const uint32_t phase = (uint32_t) ((window - src.first % window) % window);
-			if (phase >= src.n) continue;                                  // nothing of it is sampled
-			const uint64_t t = (uint64_t) B.tile0[k] + ((uint64_t) src.n + lead + XS_TILE - 1) / XS_TILE;
-			if ((t > 0x7FFFFFFFull) && (k > 0)) break;                     // the rest goes into the next launch
-			B.base[k] = src.d_v - lead;  B.n[k] = src.n;  B.lead[k] = lead;  B.phase[k] = phase;
-			B.tile0[++k] = (uint32_t) t;
-			}
-		for (int j=k ; j<GDSP_BATCH_MAX ; j++) { B.base[j] = NULL;  B.n[j] = 0;  B.lead[j] = 0;  B.phase[j] = 0;  B.tile0[j+1] = B.tile0[k]; }
-		B.nvec = (uint32_t) k;
+		GdspSample B;
+		const int k = gdsp_sample_next (B, sources, nsources, &i, window, XS_TILE, 0x7FFFFFFFull);
+		GDSP_REQUIRE (k >= 0, "a source must be 8-byte aligned");
 		if (k == 0) continue;
 		const uint32_t tiles  = B.tile0[k];
 		const uint32_t blocks = (tiles < XS_MAX_BLOCKS)? tiles : XS_MAX_BLOCKS;
@@ -329,64 +277,19 @@ static gdsp_comm* xsComm = NULL;                             // see gdsp_genome_
 static uint64_t   xsLast[4];                                 // see gdsp_genome_stats_last
 
 // one pass over every source, the devices' images reduced into img (host words, global)
-static int xs_pass (int pass, const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
-                    double mean, gdsp_reduce_fn reduce, void* reduceCtx, uint64_t* img)
+static int xs_genome_pass (int pass, const gdsp_xsum_source* sources, int nsources, uint32_t window, double lo, double hi,
+                           double mean, gdsp_reduce_fn reduce, void* reduceCtx, uint64_t* img)
 	{
-	int home = 0;
-	GDSP_HIP_TRY (hipGetDevice (&home));
-	std::vector<int> devices;
-	if (xsComm != NULL)
-		for (int r=0 ; r<gdsp_comm_size (xsComm) ; r++) devices.push_back (gdsp_comm_device (xsComm, r));
-	else
+	auto onDevice = [&] (const gdsp_xsum_source* mine, int nmine, uint64_t* d_acc, void* stream) -> int
 		{
-		for (int i=0 ; i<nsources ; i++) devices.push_back (sources[i].device);
-		std::sort (devices.begin (), devices.end ());
-		devices.erase (std::unique (devices.begin (), devices.end ()), devices.end ());
-		if (devices.empty ()) devices.push_back (home);
-		}
-	for (int i=0 ; i<nsources ; i++)
-		GDSP_REQUIRE (std::find (devices.begin (), devices.end (), sources[i].device) != devices.end (),
-		              "a source sits on a device the communicator does not hold");
-	const size_t nd = devices.size ();
-	std::vector<uint64_t*> accs (nd, NULL);
-	std::vector<void*>     streams (nd, NULL);
-	std::vector<gdsp_xsum_source> mine;
-	int rc = GDSP_OK;
-	for (size_t d=0 ; (d<nd) && (rc == GDSP_OK) ; d++)
-		{
-		GDSP_HIP_TRY (hipSetDevice (devices[d]));
-		mine.clear ();
-		for (int i=0 ; i<nsources ; i++) { if (sources[i].device == devices[d]) mine.push_back (sources[i]); }
-		if (!mine.empty ()) streams[d] = mine[0].stream;
-		if (hipMalloc ((void**) &accs[d], GDSP_XSUM_WORDS * sizeof(uint64_t)) != hipSuccess)
-			{ accs[d] = NULL;  gdsp_set_error ("gdsp_genome_stats: no device memory for the accumulator");  rc = GDSP_ENOMEM;  break; }
-		rc = gdsp_xsum_init (accs[d], streams[d]);
-		if (rc == GDSP_OK) rc = (pass == 1)? gdsp_xsum_accumulate_batch (mine.data (), (int) mine.size (), window, lo, hi, accs[d], streams[d])
-		                                   : gdsp_xsum_accumulate_sq_batch (mine.data (), (int) mine.size (), window, lo, hi, mean, accs[d], streams[d]);
-		if (rc == GDSP_OK) rc = gdsp_xsum_fold (accs[d], streams[d]);
-		}
-	if ((rc == GDSP_OK) && (xsComm != NULL))
-		rc = gdsp_comm_allreduce_u64 (xsComm, accs.data (), GDSP_XSUM_WORDS, 0, streams.data ());
-	memset (img, 0, GDSP_XSUM_WORDS * sizeof(uint64_t));
-	for (size_t d=0 ; d<nd ; d++)
-		{
-		if (accs[d] == NULL) continue;
-		(void) hipSetDevice (devices[d]);
-		uint64_t h[GDSP_XSUM_WORDS];
-		if ((rc == GDSP_OK) && ((xsComm == NULL) || (d == 0)))        // (with the communicator every rank holds the sum)
-			{
-			if (hipMemcpyAsync (h, accs[d], sizeof(h), hipMemcpyDeviceToHost, gdsp_stream (streams[d])) != hipSuccess
-			 || hipStreamSynchronize (gdsp_stream (streams[d])) != hipSuccess)
-				{ gdsp_set_error ("gdsp_genome_stats: reading the accumulator back failed");  rc = GDSP_EHIP; }
-			else for (int w=0 ; w<GDSP_XSUM_WORDS ; w++) img[w] += h[w];
-			}
-		else (void) hipStreamSynchronize (gdsp_stream (streams[d]));
-		(void) hipFree (accs[d]);
-		}
-	(void) hipSetDevice (home);
-	if ((rc == GDSP_OK) && (reduce != NULL) && (reduce (reduceCtx, img, GDSP_XSUM_WORDS, 0) != 0))
-		{ gdsp_set_error ("gdsp_genome_stats: the caller's reduction failed");  rc = GDSP_EHIP; }
-	return rc;
+		int rc = gdsp_xsum_init (d_acc, stream);
+		if (rc == GDSP_OK) rc = (pass == 1)? gdsp_xsum_accumulate_batch (mine, nmine, window, lo, hi, d_acc, stream)
+		                                   : gdsp_xsum_accumulate_sq_batch (mine, nmine, window, lo, hi, mean, d_acc, stream);
+		if (rc == GDSP_OK) rc = gdsp_xsum_fold (d_acc, stream);
+		return rc;
+		};
+	return gdsp_reduce_sources ("gdsp_genome_stats", "accumulator", xsComm, sources, nsources, GDSP_XSUM_WORDS, onDevice,
+	                            reduce, reduceCtx, img);
 	}
 
 extern "C" {
@@ -402,7 +305,7 @@ int gdsp_genome_stats (const gdsp_xsum_source* sources, int nsources, uint32_t w
 	GDSP_REQUIRE ((nsources == 0) || (sources != NULL), "NULL sources");
 	GDSP_REQUIRE (!((xsComm != NULL) && (reduce != NULL)), "a host reduction hook next to a communicator");
 	uint64_t img[GDSP_XSUM_WORDS];
-	int rc = xs_pass (1, sources, nsources, window, lo, hi, 0.0, reduce, reduceCtx, img);
+	int rc = xs_genome_pass (1, sources, nsources, window, lo, hi, 0.0, reduce, reduceCtx, img);
 	if (rc != GDSP_OK) return rc;
 	const uint64_t n = img[GDSP_XSUM_WORD_COUNT];
 	xsLast[0] = n;  xsLast[1] = img[GDSP_XSUM_WORD_FLUSHES];  xsLast[2] = 0;  xsLast[3] = 0;
@@ -410,7 +313,7 @@ int gdsp_genome_stats (const gdsp_xsum_source* sources, int nsources, uint32_t w
 	out[1] = gdsp_xsum_round (img);
 	if (n == 0) { out[2] = out[3] = out[4] = NAN;  return GDSP_OK; }
 	out[2] = gdsp_xsum_div_round (img, n);
-	rc = xs_pass (2, sources, nsources, window, lo, hi, out[2], reduce, reduceCtx, img);
+	rc = xs_genome_pass (2, sources, nsources, window, lo, hi, out[2], reduce, reduceCtx, img);
 	if (rc != GDSP_OK) return rc;
 	xsLast[2] = img[GDSP_XSUM_WORD_FLUSHES];  xsLast[3] = img[GDSP_XSUM_WORD_INF];
 	out[3] = gdsp_xsum_div_round (img, n);

@@ -39,6 +39,20 @@ __device__ __forceinline__ void xs_deposit (unsigned long long* acc, double x)
 	if (c2 != 0) atomicAdd (&acc[w + 2], (unsigned long long) c2);
 	}
 
+// an image (LDS or device) in canonical digits, 0 <= digit < 2^32 below the top one, by one lane (68 steps): canonical
+// images add word by word with room to spare, and can be compared word for word
+__device__ __forceinline__ void xs_carry (unsigned long long* acc)
+	{
+	long long carry = 0;
+	for (int w=0 ; w<GDSP_XSUM_DIGITS-1 ; w++)
+		{
+		const long long x = (long long) acc[w] + carry;
+		carry  = x >> 32;
+		acc[w] = (unsigned long long) (x & 0xFFFFFFFFll);
+		}
+	acc[GDSP_XSUM_DIGITS-1] += (unsigned long long) carry;
+	}
+
 __host__ __device__ __forceinline__ bool xs_finite (double x) { return fabs (x) <= DBL_MAX; }
 
 // a[] += x exactly, the careful way: TwoSum through the terms; what is left after the last one (or a summand whose TwoSum

@@ -44,6 +44,19 @@ u32   window_arg       (char* name, char* arg, char* argVal, const char* what);
 /* "--x=<value|variable>": number now, or a named variable resolved at first apply */
 void  value_or_variable (char* argVal, valtype* val, char** varName);
 void  resolve_variable  (dspop* op, char** varName, valtype* val, const char* role);
+/* what percentile, stats, normalize, histogram and statsover let the user say about the sample and its report; init
+ * gives today's defaults (the named global windowSize, 0 meaning 1; no limits; every digit; not quiet), take consumes
+ * --min= / --max= and those of the other options that `accepts` names, with the complaints they have always made */
+typedef struct sample_opts { u32 window;  valtype minAllowed, maxAllowed;  int precision, quiet; } sample_opts;
+#define SAMPLE_OPT_WINDOW    1
+#define SAMPLE_OPT_PRECISION 2
+#define SAMPLE_OPT_QUIET     4
+void  sample_opts_init  (sample_opts* o);
+int   sample_opts_take  (sample_opts* o, char* name, char* arg, int accepts);
+int   signal_sources    (char* name, gdsp_xsum_source** sources);   /* signal_parts() as the library's source table */
+int   format_value      (char* text, size_t size, valtype v, int precision);   /* %.17g when precision < 0 */
+FILE* open_table        (char* name, char* filename);               /* --output=<file>, or stdout */
+void  close_table       (FILE* out);
 
 /* ops_fused.c: run op (and the operators after it, up to stopOp) as one fused kernel when
  * the chain is one the device library fuses; returns how many operators were consumed (0 = none) */

@@ -2,6 +2,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
+#include <float.h>
 #include "genodsp_interface.h"
 #include "utilities.h"
 #include "host_services.h"
@@ -45,3 +46,80 @@ void resolve_variable (dspop* op, char** varName, valtype* val, const char* role
 	free (*varName);
 	*varName = NULL;
 	}
+
+/* ---- what the operators that only read the signal (percentile, stats, normalize, histogram, statsover) share ---- */
+
+/* percentile.c:150-156: the sample is every base with any value, looked at one per window of the global --window= */
+void sample_opts_init (sample_opts* o)
+	{
+	o->minAllowed = -valtypeMax;
+	o->maxAllowed =  valtypeMax;
+	o->window     = (u32) get_named_global ("windowSize", 1);
+	if (o->window == 0) o->window = 1;
+	o->precision  = -1;                                              /* -1: %.17g, every digit a double has */
+	o->quiet      = false;
+	}
+
+/* --min= and --max=, and of --window= (W=), --precision= and --quiet (--silent) those the operator accepts
+ * (SAMPLE_OPT_*); true when arg was one of them */
+int sample_opts_take (sample_opts* o, char* name, char* arg, int accepts)
+	{
+	char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
+	if ((accepts & SAMPLE_OPT_WINDOW) && is_opt3 (arg, "window", "W"))
+		{
+		int w = string_to_unitized_int (argVal, /*thousands*/ true);
+		if (w == 0) w = 1;
+		if (w < 0) chastise ("[%s] window size can't be negative (\"%s\")\n", name, arg);
+		o->window = (u32) w;
+		return true;
+		}
+	if (strcmp_prefix (arg, "--min=") == 0) { o->minAllowed = string_to_valtype (argVal);  return true; }
+	if (strcmp_prefix (arg, "--max=") == 0) { o->maxAllowed = string_to_valtype (argVal);  return true; }
+	if ((accepts & SAMPLE_OPT_PRECISION) && (strcmp_prefix (arg, "--precision=") == 0))
+		{
+		o->precision = string_to_int (argVal);
+		if (o->precision < 0) chastise ("[%s] precision can't be negative (\"%s\")\n", name, arg);
+		return true;
+		}
+	if ((accepts & SAMPLE_OPT_QUIET) && ((strcmp (arg, "--quiet") == 0) || (strcmp (arg, "--silent") == 0)))
+		{ o->quiet = true;  return true; }
+	return false;
+	}
+
+/* the signal's parts as the source table of gdsp_genome_stats / gdsp_genome_histogram (the caller frees it): every
+ * device has finished what it was doing, each part's stream is its device's, and the device of part 0 is current */
+int signal_sources (char* name, gdsp_xsum_source** sources)
+	{
+	sigpart* parts;
+	int nsrc = signal_parts (&parts);
+	gdsp_xsum_source* src = (gdsp_xsum_source*) calloc (nsrc? nsrc : 1, sizeof(gdsp_xsum_source));
+	if (src == NULL) { fprintf (stderr, "[%s] out of memory\n", name);  exit (EXIT_FAILURE); }
+	sync_all_devices ();
+	for (int i=0 ; i<nsrc ; i++)
+		{
+		select_device_of (parts[i].s);
+		src[i].d_v = parts[i].v;  src[i].n = parts[i].n;  src[i].first = parts[i].first;
+		src[i].device = physical_device_of (parts[i].s);  src[i].stream = op_stream ();
+		}
+	if (nsrc > 0) select_device_of (parts[0].s);
+	*sources = src;
+	return nsrc;
+	}
+
+/* "%.17g", or valtypeFmtPrec with a precision (>= 0), into text[size]; -> what snprintf returns */
+int format_value (char* text, size_t size, valtype v, int precision)
+	{
+	if (precision < 0) return snprintf (text, size, "%.17g", v);
+	return snprintf (text, size, valtypeFmtPrec, precision, v);
+	}
+
+/* --output=<file>: where an operator's table goes -- the file, or stdout when there is none */
+FILE* open_table (char* name, char* filename)
+	{
+	if (filename == NULL) return stdout;
+	FILE* out = fopen (filename, "wt");
+	if (out == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for writing\n", name, filename);  exit (EXIT_FAILURE); }
+	return out;
+	}
+
+void close_table (FILE* out) { if (out != stdout) fclose (out);  else fflush (stdout); }

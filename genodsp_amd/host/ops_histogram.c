@@ -27,13 +27,12 @@ dspprototypes(op_histogram)
 
 typedef struct dspop_histogram
 	{
-	dspop   common;
-	u32     windowSize, numBins;
-	valtype minAllowed, maxAllowed;
-	double* edges;                              /* numBins + 1 of them */
-	int     uniform;                            /* the table is lo + k*width */
-	char*   outFilename;
-	int     valPrecision, quiet;
+	dspop       common;
+	sample_opts sample;                         /* (as stats) */
+	u32         numBins;
+	double*     edges;                          /* numBins + 1 of them */
+	int         uniform;                        /* the table is lo + k*width */
+	char*       outFilename;
 	} dspop_histogram;
 
 OP_SHORT (op_histogram, "print the genome-wide distribution of the values: count, fraction and breadth per bin (not in genodsp)")
@@ -94,11 +93,7 @@ static double* read_edges (char* name, char* filename, u32* numBins)
 dspop* op_histogram_parse (char* name, int argc, char** argv)
 	{
 	dspop_histogram* op = (dspop_histogram*) new_op (name, sizeof(dspop_histogram), true);
-	op->minAllowed   = -valtypeMax;
-	op->maxAllowed   =  valtypeMax;
-	op->windowSize   = (u32) get_named_global ("windowSize", 1);       /* as stats */
-	if (op->windowSize == 0) op->windowSize = 1;
-	op->valPrecision = -1;                                            /* -1: %.17g, every digit a double has */
+	sample_opts_init (&op->sample);
 	int    bins = 256, haveUniform = false;
 	double lo = 0, width = 1;
 	char*  edgesFilename = NULL;
@@ -106,14 +101,7 @@ dspop* op_histogram_parse (char* name, int argc, char** argv)
 		{
 		char* arg = argv[0];
 		char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
-		if (is_opt3 (arg, "window", "W"))
-			{
-			int w = string_to_unitized_int (argVal, /*thousands*/ true);
-			if (w == 0) w = 1;
-			if (w < 0) chastise ("[%s] window size can't be negative (\"%s\")\n", name, arg);
-			op->windowSize = (u32) w;
-			continue;
-			}
+		if (sample_opts_take (&op->sample, name, arg, SAMPLE_OPT_WINDOW | SAMPLE_OPT_PRECISION | SAMPLE_OPT_QUIET)) continue;
 		if (strcmp_prefix (arg, "--bins=") == 0)
 			{
 			bins = string_to_int (argVal);
@@ -131,17 +119,8 @@ dspop* op_histogram_parse (char* name, int argc, char** argv)
 			}
 		if (strcmp_prefix (arg, "--edges=") == 0)
 			{ if (edgesFilename != NULL) free (edgesFilename);  edgesFilename = copy_string (argVal);  continue; }
-		if (strcmp_prefix (arg, "--min=") == 0) { op->minAllowed = string_to_valtype (argVal);  continue; }
-		if (strcmp_prefix (arg, "--max=") == 0) { op->maxAllowed = string_to_valtype (argVal);  continue; }
 		if (strcmp_prefix (arg, "--output=") == 0)
 			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
-		if (strcmp_prefix (arg, "--precision=") == 0)
-			{
-			op->valPrecision = string_to_int (argVal);
-			if (op->valPrecision < 0) chastise ("[%s] precision can't be negative (\"%s\")\n", name, arg);
-			continue;
-			}
-		if ((strcmp (arg, "--quiet") == 0) || (strcmp (arg, "--silent") == 0)) { op->quiet = true;  continue; }
 		if (strcmp_prefix (arg, "--debug") == 0) continue;
 		chastise ("[%s] Can't understand \"%s\"\n", name, arg);
 		}
@@ -172,74 +151,52 @@ void op_histogram_free (dspop* _op)
 	free (op);
 	}
 
-static void put_edge (FILE* f, double e, int precision)
-	{
-	if (precision < 0) fprintf (f, "%.17g", e);
-	else               fprintf (f, valtypeFmtPrec, precision, e);
-	}
-
 void op_histogram_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
 	{
 	dspop_histogram* op = (dspop_histogram*) _op;
 	const u32 B = op->numBins;
-	sigpart* parts;
-	int nsrc = signal_parts (&parts);
-	gdsp_xsum_source* src = (gdsp_xsum_source*) calloc (nsrc? nsrc : 1, sizeof(gdsp_xsum_source));
+	gdsp_xsum_source* src;
+	int nsrc = signal_sources (_op->name, &src);
 	u64* words = (u64*) calloc ((size_t) B + 3, sizeof(u64));
-	if ((src == NULL) || (words == NULL)) { fprintf (stderr, "[%s] out of memory\n", _op->name);  exit (EXIT_FAILURE); }
-	sync_all_devices ();
-	for (int i=0 ; i<nsrc ; i++)
-		{
-		select_device_of (parts[i].s);
-		src[i].d_v = parts[i].v;  src[i].n = parts[i].n;  src[i].first = parts[i].first;
-		src[i].device = physical_device_of (parts[i].s);  src[i].stream = op_stream ();
-		}
+	if (words == NULL) { fprintf (stderr, "[%s] out of memory\n", _op->name);  exit (EXIT_FAILURE); }
 	void* reduceCtx = NULL;
 	gdsp_reduce_fn reduce = reduce_over_devices (&reduceCtx);    /* (NULL when the library's communicator does it) */
-	check_gdsp (gdsp_genome_histogram (src, nsrc, op->windowSize, op->minAllowed, op->maxAllowed, op->edges, B, op->uniform,
-	                                   reduce, reduceCtx, (uint64_t*) words), _op->name);
-	if (nsrc > 0) select_device_of (parts[0].s);
+	check_gdsp (gdsp_genome_histogram (src, nsrc, op->sample.window, op->sample.minAllowed, op->sample.maxAllowed, op->edges, B,
+	                                   op->uniform, reduce, reduceCtx, (uint64_t*) words), _op->name);
 	free (src);
 
 	const u64 below = words[B], above = words[B+1], n = words[B+2];
-	FILE* out = stdout;
-	if (op->outFilename != NULL)
-		{
-		out = fopen (op->outFilename, "wt");
-		if (out == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for writing\n", _op->name, op->outFilename);  exit (EXIT_FAILURE); }
-		}
+	FILE* out = open_table (_op->name, op->outFilename);
+	char  lo[400], hi[400], text[400];
 	fprintf (out, "# count %llu\n# below %llu\n# above %llu\n", (unsigned long long) n, (unsigned long long) below, (unsigned long long) above);
 	fprintf (out, "#lo\thi\tcount\tfraction\tatleast\n");
 	u64 atLeast = n - below;                                     /* sampled values at or above the bin's lower edge */
 	u32 mode = 0;
 	for (u32 k=0 ; k<B ; k++)
 		{
-		put_edge (out, op->edges[k], op->valPrecision);    fputc ('\t', out);
-		put_edge (out, op->edges[k+1], op->valPrecision);
-		fprintf (out, "\t%llu\t", (unsigned long long) words[k]);
+		format_value (lo, sizeof(lo), op->edges[k],   op->sample.precision);
+		format_value (hi, sizeof(hi), op->edges[k+1], op->sample.precision);
+		fprintf (out, "%s\t%s\t%llu\t", lo, hi, (unsigned long long) words[k]);
 		if (n == 0) fprintf (out, "NA\tNA\n");
 		else        fprintf (out, "%.17g\t%.17g\n", (double) words[k] / (double) n, (double) atLeast / (double) n);
 		atLeast -= words[k];
 		if (words[k] > words[mode]) mode = k;                      /* (the lowest bin on ties) */
 		}
-	if (out != stdout) fclose (out);  else fflush (stdout);
+	close_table (out);
 
 	/* count as stats sets and words it; mode only when some bin holds something */
-	char text[400];
 	set_named_global ("count", (valtype) n);
-	if (!op->quiet)
+	if (!op->sample.quiet)
 		{
-		if (op->valPrecision < 0) snprintf (text, sizeof(text), "%.17g", (double) n);
-		else                      snprintf (text, sizeof(text), valtypeFmtPrec, op->valPrecision, (double) n);
+		format_value (text, sizeof(text), (double) n, op->sample.precision);
 		fprintf (stderr, "count is %s\n", text);
 		}
 	if (n - below - above != 0)
 		{
 		set_named_global ("mode", (valtype) op->edges[mode]);
-		if (!op->quiet)
+		if (!op->sample.quiet)
 			{
-			if (op->valPrecision < 0) snprintf (text, sizeof(text), "%.17g", op->edges[mode]);
-			else                      snprintf (text, sizeof(text), valtypeFmtPrec, op->valPrecision, op->edges[mode]);
+			format_value (text, sizeof(text), op->edges[mode], op->sample.precision);
 			fprintf (stderr, "mode is %s\n", text);
 			}
 		}

@@ -24,12 +24,11 @@
 
 typedef struct dspop_percentile
 	{
-	dspop   common;
-	u32     percentileLo, percentileHi, percentileStep;
-	valtype minAllowed, maxAllowed;
-	u32     windowSize;
-	int     valPrecision, quiet, reportForBash;
-	char   *preserveFilename, *mapFilename;
+	dspop       common;
+	u32         percentileLo, percentileHi, percentileStep;
+	sample_opts sample;
+	int         reportForBash;
+	char       *preserveFilename, *mapFilename;
 	} dspop_percentile;
 
 OP_SHORT (op_percentile, "compute percentiles of the current set of interval values")
@@ -67,11 +66,8 @@ dspop* op_percentile_parse (char* name, int argc, char** argv)
 	dspop_percentile* op = (dspop_percentile*) new_op (name, sizeof(dspop_percentile), true);
 	int haveRange = false;
 	op->percentileStep = percentileStepUnits;
-	op->minAllowed     = -valtypeMax;
-	op->maxAllowed     =  valtypeMax;
-	op->windowSize     = (u32) get_named_global ("windowSize", 1);      /* percentile.c:153: the global --window= */
-	if (op->windowSize == 0) op->windowSize = 1;
-	op->valPrecision   = (int) get_named_global ("valPrecision", 0);
+	sample_opts_init (&op->sample);                                 /* percentile.c:153: the global --window= */
+	op->sample.precision = (int) get_named_global ("valPrecision", 0);
 
 	for ( ; argc > 0 ; argv++, argc--)
 		{
@@ -80,28 +76,12 @@ dspop* op_percentile_parse (char* name, int argc, char** argv)
 		char* stepText = NULL;
 
 		if (strcmp_prefix (arg, "--step=") == 0) { stepText = argVal;  goto set_step; }
-		if (is_opt3 (arg, "window", "W"))
-			{
-			int w = string_to_unitized_int (argVal, /*thousands*/ true);
-			if (w == 0) w = 1;
-			if (w < 0) chastise ("[%s] window size can't be negative (\"%s\")\n", name, arg);
-			op->windowSize = (u32) w;
-			continue;
-			}
-		if (strcmp_prefix (arg, "--min=") == 0) { op->minAllowed = string_to_valtype (argVal);  continue; }
-		if (strcmp_prefix (arg, "--max=") == 0) { op->maxAllowed = string_to_valtype (argVal);  continue; }
-		if (strcmp_prefix (arg, "--precision=") == 0)
-			{
-			op->valPrecision = string_to_int (argVal);
-			if (op->valPrecision < 0) chastise ("[%s] precision can't be negative (\"%s\")\n", name, arg);
-			continue;
-			}
+		if (sample_opts_take (&op->sample, name, arg, SAMPLE_OPT_WINDOW | SAMPLE_OPT_PRECISION | SAMPLE_OPT_QUIET)) continue;
 		if (strcmp_prefix (arg, "--preserve=") == 0)
 			{ if (op->preserveFilename == NULL) op->preserveFilename = copy_string (argVal);  continue; }
 		if ((strcmp_prefix (arg, "--map=") == 0) || (strcmp_prefix (arg, "--mapping=") == 0))
 			{ if (op->mapFilename == NULL) op->mapFilename = copy_string (argVal);  continue; }
 		if ((strcmp (arg, "--report:bash") == 0) || (strcmp (arg, "--bash") == 0)) { op->reportForBash = true;  continue; }
-		if ((strcmp (arg, "--quiet") == 0) || (strcmp (arg, "--silent") == 0))     { op->quiet = true;  continue; }
 		if (strcmp_prefix (arg, "--debug") == 0) continue;
 		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
 
@@ -146,7 +126,7 @@ dspop* op_percentile_parse (char* name, int argc, char** argv)
 			}
 		}
 	if (!haveRange) { fprintf (stderr, "[%s] no range of percentiles was provided\n", name);  exit (EXIT_FAILURE); }
-	if (op->reportForBash && op->quiet) chastise ("[%s] Can't use both --report:bash and --quiet\n", name);
+	if (op->reportForBash && op->sample.quiet) chastise ("[%s] Can't use both --report:bash and --quiet\n", name);
 	return (dspop*) op;
 	}
 
@@ -247,7 +227,7 @@ static int percentile_run (dspop* _op, dspop* binarize)
 		{
 		/* the sample is every windowSize-th base counted from the chromosome's first (percentile.c:560): a stretch
 		 * that starts at base `first` begins with the next multiple */
-		u32 skip = (op->windowSize - parts[i].first % op->windowSize) % op->windowSize;
+		u32 skip = (op->sample.window - parts[i].first % op->sample.window) % op->sample.window;
 		select_device_of (parts[i].s);
 		src[i].d_v = (skip < parts[i].n)? parts[i].v + skip : NULL;
 		src[i].n   = (skip < parts[i].n)? parts[i].n - skip : 0;
@@ -289,13 +269,13 @@ static int percentile_run (dspop* _op, dspop* binarize)
 			}
 		fuse.d_out = outs;
 		int onePass = 0;
-		check_gdsp (gdsp_percentiles_binarize (src, nsrc, op->windowSize, op->minAllowed, op->maxAllowed, pts, npct,
+		check_gdsp (gdsp_percentiles_binarize (src, nsrc, op->sample.window, op->sample.minAllowed, op->sample.maxAllowed, pts, npct,
 		                                       selectStrategy, 0, reduce, reduceCtx, vals, &numValues, &fuse, &onePass), "percentile");
 		free (outs);
 		fused = (numValues != 0);
 		}
 	else
-		check_gdsp (gdsp_percentiles (src, nsrc, op->windowSize, op->minAllowed, op->maxAllowed, pts, npct,
+		check_gdsp (gdsp_percentiles (src, nsrc, op->sample.window, op->sample.minAllowed, op->sample.maxAllowed, pts, npct,
 		                              selectStrategy, 0, reduce, reduceCtx, vals, &numValues), "percentile");
 	if (nsrc > 0) select_device_of (parts[0].s);
 	free (src);
@@ -325,10 +305,10 @@ static int percentile_run (dspop* _op, dspop* binarize)
 		set_named_global (varName, pVal);
 		if (extremesOnly) continue;
 		if (op->reportForBash)
-			fprintf (stdout, "%s=" valtypeFmtPrec " # bash command\n", varName, op->valPrecision, pVal);
-		else if (!op->quiet)
-			fprintf (stderr, "percentile %.3f is " valtypeFmtPrec "\n", pPct, op->valPrecision, pVal);
-		if (mapF != NULL) fprintf (mapF, valtypeFmtPrec " %.3f\n", op->valPrecision, pVal, pPct);
+			fprintf (stdout, "%s=" valtypeFmtPrec " # bash command\n", varName, op->sample.precision, pVal);
+		else if (!op->sample.quiet)
+			fprintf (stderr, "percentile %.3f is " valtypeFmtPrec "\n", pPct, op->sample.precision, pVal);
+		if (mapF != NULL) fprintf (mapF, valtypeFmtPrec " %.3f\n", op->sample.precision, pVal, pPct);
 		}
 	if (mapF != NULL) fclose (mapF);
 	free (pts);  free (vals);

@@ -27,35 +27,21 @@ dspprototypes(op_stats)  dspprototypes(op_normalize)  dspprototypes(op_multiply_
 /* ---------------------------------------------------------------------------------------- stats, normalize ---- */
 typedef struct dspop_stats
 	{
-	dspop   common;
-	u32     windowSize;
-	valtype minAllowed, maxAllowed;
-	int     valPrecision, quiet, reportForBash, zscore;
+	dspop       common;
+	sample_opts sample;                         /* (as percentile) */
+	int         reportForBash, zscore;
 	} dspop_stats;
 
 static dspop* stats_parse (char* name, int argc, char** argv, int isNormalize)
 	{
 	dspop_stats* op = (dspop_stats*) new_op (name, sizeof(dspop_stats), true);
-	op->minAllowed   = -valtypeMax;
-	op->maxAllowed   =  valtypeMax;
-	op->windowSize   = (u32) get_named_global ("windowSize", 1);       /* as percentile */
-	if (op->windowSize == 0) op->windowSize = 1;
-	op->valPrecision = -1;                                            /* -1: %.17g, every digit a double has */
+	const int accepts = SAMPLE_OPT_WINDOW | SAMPLE_OPT_QUIET | (isNormalize? 0 : SAMPLE_OPT_PRECISION);
+	sample_opts_init (&op->sample);
 	for ( ; argc > 0 ; argv++, argc--)
 		{
 		char* arg = argv[0];
 		char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
-		if (is_opt3 (arg, "window", "W"))
-			{
-			int w = string_to_unitized_int (argVal, /*thousands*/ true);
-			if (w == 0) w = 1;
-			if (w < 0) chastise ("[%s] window size can't be negative (\"%s\")\n", name, arg);
-			op->windowSize = (u32) w;
-			continue;
-			}
-		if (strcmp_prefix (arg, "--min=") == 0) { op->minAllowed = string_to_valtype (argVal);  continue; }
-		if (strcmp_prefix (arg, "--max=") == 0) { op->maxAllowed = string_to_valtype (argVal);  continue; }
-		if ((strcmp (arg, "--quiet") == 0) || (strcmp (arg, "--silent") == 0)) { op->quiet = true;  continue; }
+		if (sample_opts_take (&op->sample, name, arg, accepts)) continue;
 		if (isNormalize && (strcmp_prefix (arg, "--to=") == 0))
 			{
 			if      (strcmp (argVal, "mean")   == 0) op->zscore = false;
@@ -63,17 +49,11 @@ static dspop* stats_parse (char* name, int argc, char** argv, int isNormalize)
 			else chastise ("[%s] unknown --to=%s (mean or zscore)\n", name, argVal);
 			continue;
 			}
-		if (!isNormalize && (strcmp_prefix (arg, "--precision=") == 0))
-			{
-			op->valPrecision = string_to_int (argVal);
-			if (op->valPrecision < 0) chastise ("[%s] precision can't be negative (\"%s\")\n", name, arg);
-			continue;
-			}
 		if (!isNormalize && ((strcmp (arg, "--report:bash") == 0) || (strcmp (arg, "--bash") == 0))) { op->reportForBash = true;  continue; }
 		if (strcmp_prefix (arg, "--debug") == 0) continue;
 		chastise ("[%s] Can't understand \"%s\"\n", name, arg);
 		}
-	if (op->reportForBash && op->quiet) chastise ("[%s] Can't use both --report:bash and --quiet\n", name);
+	if (op->reportForBash && op->sample.quiet) chastise ("[%s] Can't use both --report:bash and --quiet\n", name);
 	return (dspop*) op;
 	}
 
@@ -107,32 +87,21 @@ static void stats_usage (char* name, FILE* f, char* indent, int isNormalize)
 /* the figures of the sampled genome, over every device (and every rank of the reduction hook); sets the variables */
 static void stats_compute (dspop_stats* op, double* fig)
 	{
-	sigpart* parts;
-	int nsrc = signal_parts (&parts);
-	gdsp_xsum_source* src = (gdsp_xsum_source*) calloc (nsrc? nsrc : 1, sizeof(gdsp_xsum_source));
-	if (src == NULL) { fprintf (stderr, "[%s] out of memory\n", op->common.name);  exit (EXIT_FAILURE); }
-	sync_all_devices ();
-	for (int i=0 ; i<nsrc ; i++)
-		{
-		select_device_of (parts[i].s);
-		src[i].d_v = parts[i].v;  src[i].n = parts[i].n;  src[i].first = parts[i].first;
-		src[i].device = physical_device_of (parts[i].s);  src[i].stream = op_stream ();
-		}
+	gdsp_xsum_source* src;
+	int nsrc = signal_sources (op->common.name, &src);
 	void* reduceCtx = NULL;
 	gdsp_reduce_fn reduce = reduce_over_devices (&reduceCtx);    /* (also hands the communicator to the library) */
-	check_gdsp (gdsp_genome_stats (src, nsrc, op->windowSize, op->minAllowed, op->maxAllowed, reduce, reduceCtx, fig),
+	check_gdsp (gdsp_genome_stats (src, nsrc, op->sample.window, op->sample.minAllowed, op->sample.maxAllowed, reduce, reduceCtx, fig),
 	            op->common.name);
-	if (nsrc > 0) select_device_of (parts[0].s);
 	free (src);
 	static char* names[5] = { "count", "sum", "mean", "variance", "stddev" };
 	for (int k=0 ; k<5 ; k++)
 		{
 		if ((fig[0] == 0) && (k >= 2)) continue;                 /* (no mean of nothing) */
 		set_named_global (names[k], fig[k]);
-		if (op->quiet) continue;
+		if (op->sample.quiet) continue;
 		char text[400];
-		if (op->valPrecision < 0) snprintf (text, sizeof(text), "%.17g", fig[k]);
-		else                      snprintf (text, sizeof(text), valtypeFmtPrec, op->valPrecision, fig[k]);
+		format_value (text, sizeof(text), fig[k], op->sample.precision);
 		if (op->reportForBash) fprintf (stdout, "%s=%s # bash command\n", names[k], text);
 		else                   fprintf (stderr, "%s is %s\n", names[k], text);
 		}

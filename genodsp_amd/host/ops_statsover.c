@@ -26,13 +26,13 @@ dspprototypes(op_statsover)
 
 typedef struct dspop_statsover
 	{
-	dspop   common;
-	char*   filename;
-	char*   outFilename;
-	valtype minAllowed, maxAllowed;
-	int     valPrecision, originOne;
-	u64     bases;                              /* summed length of the intervals (--report=gpu) */
-	double  msDevice, msFormat;                 /* GDSP_STATSOVER_TIMES=1: where a run's time went, on stderr */
+	dspop       common;
+	char*       filename;
+	char*       outFilename;
+	sample_opts sample;                         /* (its limits and precision; no window) */
+	int         originOne;
+	u64         bases;                          /* summed length of the intervals (--report=gpu) */
+	double      msDevice, msFormat;             /* GDSP_STATSOVER_TIMES=1: where a run's time went, on stderr */
 	} dspop_statsover;
 
 OP_SHORT (op_statsover, "print count, sum, mean, min, max and summit of the signal over each interval of a file (not in genodsp)")
@@ -55,24 +55,15 @@ void op_statsover_usage (char* name, FILE* f, char* indent)
 dspop* op_statsover_parse (char* name, int argc, char** argv)
 	{
 	dspop_statsover* op = (dspop_statsover*) new_op (name, sizeof(dspop_statsover), true);
-	op->minAllowed   = -valtypeMax;
-	op->maxAllowed   =  valtypeMax;
-	op->valPrecision = -1;                                            /* -1: %.17g, every digit a double has */
-	op->originOne    = (int) get_named_global ("originOne", false);
+	sample_opts_init (&op->sample);
+	op->originOne = (int) get_named_global ("originOne", false);
 	for ( ; argc > 0 ; argv++, argc--)
 		{
 		char* arg = argv[0];
 		char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
 		if (strcmp_prefix (arg, "--output=") == 0)
 			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
-		if (strcmp_prefix (arg, "--min=") == 0) { op->minAllowed = string_to_valtype (argVal);  continue; }
-		if (strcmp_prefix (arg, "--max=") == 0) { op->maxAllowed = string_to_valtype (argVal);  continue; }
-		if (strcmp_prefix (arg, "--precision=") == 0)
-			{
-			op->valPrecision = string_to_int (argVal);
-			if (op->valPrecision < 0) chastise ("[%s] precision can't be negative (\"%s\")\n", name, arg);
-			continue;
-			}
+		if (sample_opts_take (&op->sample, name, arg, SAMPLE_OPT_PRECISION)) continue;
 		if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { op->originOne = true;   continue; }
 		if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { op->originOne = false;  continue; }
 		if (strcmp (arg, "--debug") == 0) continue;
@@ -81,7 +72,7 @@ dspop* op_statsover_parse (char* name, int argc, char** argv)
 		chastise ("[%s] Can't understand \"%s\"\n", name, arg);
 		}
 	if (op->filename == NULL) { fprintf (stderr, "[%s] no filename was provided\n", name);  exit (EXIT_FAILURE); }
-	if (op->minAllowed > op->maxAllowed) chastise ("[%s] --min can't be above --max\n", name);
+	if (op->sample.minAllowed > op->sample.maxAllowed) chastise ("[%s] --min can't be above --max\n", name);
 	return (dspop*) op;
 	}
 
@@ -128,7 +119,7 @@ static char* put_unsigned (char* p, unsigned long long u)
 
 static int clipped (int written) { return (written > 399)? 399 : written; }     /* (what snprintf kept of a longer text) */
 
-/* "%.17g", or valtypeFmtPrec with a precision; at most 400 characters.  Integers below 10^15 (read depth, and its sums)
+/* format_value's text, at most 400 characters of it.  Integers below 10^15 (read depth, and its sums)
  * and fixed-point values take the hand-rolled forms: the same characters as printf's */
 static char* put_value (char* p, valtype v, int precision)
 	{
@@ -136,14 +127,14 @@ static char* put_value (char* p, valtype v, int precision)
 		{
 		char* q = put_value_fixed (p, v, precision);
 		if (q != NULL) return q;
-		return p + clipped (snprintf (p, 400, valtypeFmtPrec, precision, v));
+		return p + clipped (format_value (p, 400, v, precision));
 		}
 	if ((fabs (v) < 1e15) && (v == floor (v)) && ((v != 0) || !signbit (v)))
 		{
 		if (v < 0) *(p++) = '-';
 		return put_unsigned (p, (unsigned long long) fabs (v));
 		}
-	return p + clipped (snprintf (p, 400, "%.17g", v));
+	return p + clipped (format_value (p, 400, v, precision));
 	}
 
 /* the pending intervals' figures, device by device (one launch each), then their lines in file order */
@@ -190,7 +181,7 @@ static void flush_batch (dspop_statsover* op, batch* b, u64 pending, FILE* f)
 			m++;
 			}
 		select_device_of (first);
-		check_gdsp (gdsp_interval_stats_batch (items, m, b->vec, b->start, b->end, (u32) k, op->minAllowed, op->maxAllowed,
+		check_gdsp (gdsp_interval_stats_batch (items, m, b->vec, b->start, b->end, (u32) k, op->sample.minAllowed, op->sample.maxAllowed,
 		                                       b->out, op_stream ()), name);
 		for (size_t i=0 ; i<k ; i++) b->rec[b->serial[i]] = b->out[i];
 		}
@@ -218,13 +209,13 @@ static void flush_batch (dspop_statsover* op, batch* b, u64 pending, FILE* f)
 		p = put_unsigned (p, w->fileStart);  *(p++) = '\t';
 		p = put_unsigned (p, w->fileEnd);    *(p++) = '\t';
 		p = put_unsigned (p, g->count);      *(p++) = '\t';
-		p = put_value (p, g->sum, op->valPrecision);
+		p = put_value (p, g->sum, op->sample.precision);
 		if (g->count == 0) { memcpy (p, "\tNA\tNA\tNA\tNA\n", 13);  p += 13; }
 		else
 			{
-			*(p++) = '\t';  p = put_value (p, g->mean, op->valPrecision);
-			*(p++) = '\t';  p = put_value (p, g->min,  op->valPrecision);
-			*(p++) = '\t';  p = put_value (p, g->max,  op->valPrecision);
+			*(p++) = '\t';  p = put_value (p, g->mean, op->sample.precision);
+			*(p++) = '\t';  p = put_value (p, g->min,  op->sample.precision);
+			*(p++) = '\t';  p = put_value (p, g->max,  op->sample.precision);
 			*(p++) = '\t';  p = put_unsigned (p, (unsigned long long) w->s->start + g->maxpos + o);
 			*(p++) = '\n';
 			}
@@ -249,12 +240,7 @@ void op_statsover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_co
 	const double tStart = now_ms ();
 	FILE* f = fopen (op->filename, "rt");
 	if (f == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for reading\n", _op->name, op->filename);  exit (EXIT_FAILURE); }
-	FILE* out = stdout;
-	if (op->outFilename != NULL)
-		{
-		out = fopen (op->outFilename, "wt");
-		if (out == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for writing\n", _op->name, op->outFilename);  exit (EXIT_FAILURE); }
-		}
+	FILE* out = open_table (_op->name, op->outFilename);
 	for (int i=0 ; chromsSorted[i]!=NULL ; i++) chromsSorted[i]->flag = false;
 
 	ib_begin ();
@@ -301,7 +287,7 @@ void op_statsover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_co
 		}
 	fclose (f);
 	flush_batch (op, &b, ib_pending (), out);
-	if (out != stdout) fclose (out);  else fflush (stdout);
+	close_table (out);
 	if (getenv ("GDSP_STATSOVER_TIMES") != NULL)
 		{
 		const double all = now_ms () - tStart;
