@@ -654,6 +654,78 @@ def xsum_add_host(image, x):
     return image
 
 
+# ------------------------------------------------------ correlate (not in the reference) ----
+
+CORRELATION_FIGURES = ("count", "sumx", "sumy", "meanx", "meany", "varx", "vary", "sdx", "sdy", "covariance", "correlation",
+                       "slope", "intercept")          # the GDSP_CORR_* order of include/genodsp_hip.h
+
+
+class XsumPair(C.Structure):
+    """gdsp_xsum_pair of include/genodsp_hip.h"""
+    _fields_ = [("d_x", C.c_void_p), ("d_y", C.c_void_p), ("n", C.c_uint32), ("first", C.c_uint32), ("device", C.c_int),
+                ("stream", C.c_void_p)]
+
+
+def xsum_pair_tile():
+    """Pairs per tile of the pair kernel's walk."""
+    return int(lib().gdsp_xsum_pair_tile())
+
+
+def xsum_pairs(pairs, stream=None):
+    """The pair table of gdsp_genome_correlation / gdsp_xsum_pair_*: each item (x, y), x and y each as an item of
+    xsum_sources (a DeviceVector, or (vector, start, count[, first])) of equal counts; `first` is x's."""
+    device = current_device()
+    tab = (XsumPair * max(1, len(pairs)))()
+    for i, (x, y) in enumerate(pairs):
+        sx, sy = xsum_sources([x], stream)[0], xsum_sources([y], stream)[0]
+        assert sx.n == sy.n
+        tab[i].d_x, tab[i].d_y, tab[i].n, tab[i].first = sx.d_v, sy.d_v, sx.n, sx.first
+        tab[i].device, tab[i].stream = device, stream
+    return tab
+
+
+def genome_correlation(pairs, window=1, lo=-DBL_MAX, hi=DBL_MAX, ylo=-DBL_MAX, yhi=DBL_MAX, allreduce=None, stream=None):
+    """The figures of CORRELATION_FIGURES over the pair sample, each exact and rounded once or derived from such on the
+    host (gdsp_genome_correlation): every window-th position counted from each chromosome's first base with
+    lo <= x <= hi and ylo <= y <= yhi (never NaN or +-inf).  pairs: as xsum_pairs.  allreduce: genome_stats' hook.
+    count 0: sums 0.0 and the rest NaN."""
+    tab = xsum_pairs(pairs, stream)
+    out = (C.c_double * len(CORRELATION_FIGURES))()
+    failure = []
+    cb = _reduce_hook(allreduce, failure)
+    with _hook_failure_first(failure):
+        call("gdsp_genome_correlation", tab, len(pairs), int(window), float(lo), float(hi), float(ylo), float(yhi), cb, None, out)
+    return dict(zip(CORRELATION_FIGURES, [float(x) for x in out]))
+
+
+def genome_correlation_last():
+    """What the last genome_correlation did: n, lane flushes into LDS in pass 1 and pass 2, and the qxx, qyy, qxy that
+    were not finite."""
+    out = (C.c_uint64 * 8)()
+    lib().gdsp_genome_correlation_last(out)
+    return dict(zip(("count", "flushes1", "flushes2", "nonfinite_qxx", "nonfinite_qyy", "nonfinite_qxy"), [int(x) for x in out]))
+
+
+def xsum_pair_image(pairs, window=1, lo=-DBL_MAX, hi=DBL_MAX, ylo=-DBL_MAX, yhi=DBL_MAX, means=None, stream=None, fold=True):
+    """The (folded) accumulator images of one pass over pairs, as np.uint64[k, XSUM_WORDS]: k = 2 (the sums of x and of y)
+    or, with means = (meanx, meany), k = 3 (the sums of qxx, qyy, qxy)."""
+    k = 2 if means is None else 3
+    acc = DeviceBuffer(k * XSUM_WORDS * 8)
+    for i in range(k):
+        call("gdsp_xsum_init", C.c_void_p(acc.ptr + i * XSUM_WORDS * 8), _sp(stream))
+    tab = xsum_pairs(pairs, stream)
+    if means is None:
+        call("gdsp_xsum_pair_accumulate_batch", tab, len(pairs), int(window), float(lo), float(hi), float(ylo), float(yhi),
+             C.c_void_p(acc.ptr), _sp(stream))
+    else:
+        call("gdsp_xsum_pair_accumulate_dev_batch", tab, len(pairs), int(window), float(lo), float(hi), float(ylo), float(yhi),
+             float(means[0]), float(means[1]), C.c_void_p(acc.ptr), _sp(stream))
+    if fold:
+        for i in range(k):
+            call("gdsp_xsum_fold", C.c_void_p(acc.ptr + i * XSUM_WORDS * 8), _sp(stream))
+    return acc.download(np.uint64, k * XSUM_WORDS, stream=stream).reshape(k, XSUM_WORDS)
+
+
 # ------------------------------------------------------ histogram (not in the reference) ----
 
 HISTOGRAM_MAX_BINS = 65536

@@ -151,6 +151,13 @@ SIGNATURES = {
     "gdsp_genome_stats": (_int, [_vp, _int, _u32, _f64, _f64, _vp, _vp, _vp]),
     "gdsp_genome_stats_use_comm": (_int, [_vp]),
     "gdsp_genome_stats_last": (None, [_vp]),
+    # correlate (not in the reference)
+    "gdsp_xsum_pair_tile": (_u32, []),
+    "gdsp_xsum_pair_accumulate_batch": (_int, [_vp, _int, _u32, _f64, _f64, _f64, _f64, _vp, _vp]),
+    "gdsp_xsum_pair_accumulate_dev_batch": (_int, [_vp, _int, _u32, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp]),
+    "gdsp_genome_correlation": (_int, [_vp, _int, _u32, _f64, _f64, _f64, _f64, _vp, _vp, _vp]),
+    "gdsp_genome_correlation_use_comm": (_int, [_vp]),
+    "gdsp_genome_correlation_last": (None, [_vp]),
     # statsover (not in the reference)
     "gdsp_interval_stats_tile": (_u32, []),
     "gdsp_interval_stats": (_int, [_vp, _u32, _vp, _vp, _u32, _f64, _f64, _vp, _vp]),

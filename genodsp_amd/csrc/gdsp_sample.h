@@ -24,9 +24,9 @@ struct GdspSample
 // host: the next launch's table from sources[*i ..], for tiles of tileValues values and at most maxTiles of them in a
 // launch (one source may exceed that on its own); *i moves past what was taken or skipped (empty sources, and those
 // with nothing sampled).  -> how many sources the table holds (0: none were left), or -1 for a source that is not
-// 8-byte aligned
+// 8-byte aligned.  taken (when given): which source each entry of the table is
 static inline int gdsp_sample_next (GdspSample& B, const gdsp_xsum_source* sources, int nsources, int* i, uint32_t window,
-                                    uint32_t tileValues, uint64_t maxTiles)
+                                    uint32_t tileValues, uint64_t maxTiles, int* taken = NULL)
 	{
 	int k = 0;
 	B.tile0[0] = 0;
@@ -40,6 +40,7 @@ static inline int gdsp_sample_next (GdspSample& B, const gdsp_xsum_source* sourc
 		if (phase >= src.n) continue;                                  // nothing of it is sampled
 		const uint64_t t = (uint64_t) B.tile0[k] + ((uint64_t) src.n + lead + tileValues - 1) / tileValues;
 		if ((t > maxTiles) && (k > 0)) break;                          // the rest goes into the next launch
+		if (taken != NULL) taken[k] = *i;
 		B.base[k] = src.d_v - lead;  B.n[k] = src.n;  B.lead[k] = lead;  B.phase[k] = phase;
 		B.tile0[++k] = (uint32_t) t;
 		}
@@ -77,4 +78,47 @@ __device__ __forceinline__ bool gdsp_sampled (const GdspSampleTile& t, uint32_t 
 		in = in && (i >= t.phase) && ((i - t.phase) % window == 0);
 		}
 	return in;
+	}
+
+// ---- the pair form (gdsp_xsum_pair.hip: correlate): two signals walked together ----
+// A pair (gdsp_xsum_pair, include/genodsp_hip.h) is x = d_x[0 .. n) and y = d_y[0 .. n), both 8-byte aligned.  The table
+// and the frame are x's: y[i] goes with x[i], at frame index i + lead.  ybase[s] is d_y - lead[s] (frame index 0; when
+// lead is 1 that address is never read unless y shares x's alignment); bit s of `same` says that y is congruent to x
+// modulo 16 bytes, so that ybase[s] is 16-byte aligned like base[s] and both streams take 16-byte loads.
+struct GdspSamplePair
+	{
+	GdspSample    x;
+	const double* ybase[GDSP_BATCH_MAX];
+	uint32_t      same;
+	};
+
+// host: as gdsp_sample_next over the pairs' x (xs: the pairs as sources of their x, made once by the caller); -1 also for
+// a y that is not 8-byte aligned
+static inline int gdsp_sample_pair_next (GdspSamplePair& P, const gdsp_xsum_pair* pairs, const gdsp_xsum_source* xs, int npairs,
+                                         int* i, uint32_t window, uint32_t tileValues, uint64_t maxTiles)
+	{
+	int taken[GDSP_BATCH_MAX];
+	const int k = gdsp_sample_next (P.x, xs, npairs, i, window, tileValues, maxTiles, taken);
+	P.same = 0;
+	for (int j=0 ; j<GDSP_BATCH_MAX ; j++) P.ybase[j] = NULL;
+	for (int j=0 ; j<k ; j++)
+		{
+		const double* y = pairs[taken[j]].d_y;
+		if (!((y != NULL) && ((((uintptr_t) y) & 7) == 0))) return -1;
+		P.ybase[j] = y - P.x.lead[j];
+		if (gdsp_aligned16 (P.ybase[j])) P.same |= 1u << j;
+		}
+	return k;
+	}
+
+struct GdspSamplePairTile { GdspSampleTile x;  const double* ybase;  bool same; };
+
+template <uint32_t TILE>
+__device__ __forceinline__ GdspSamplePairTile gdsp_sample_pair_tile (const GdspSamplePair& P, uint32_t g, uint32_t v)
+	{
+	GdspSamplePairTile t;
+	t.x     = gdsp_sample_tile<TILE> (P.x, g, v);
+	t.ybase = P.ybase[t.x.v];
+	t.same  = ((P.same >> t.x.v) & 1u) != 0;
+	return t;
 	}

@@ -69,6 +69,9 @@ dspprototypes(op_statsover)
 #ifdef GDSP_HISTOGRAM                                  /* not in the reference: ops_histogram.c */
 dspprototypes(op_histogram)
 #endif
+#ifdef GDSP_CORRELATE                                  /* not in the reference: ops_correlate.c */
+dspprototypes(op_correlate)
+#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
@@ -129,6 +132,10 @@ static dspinfo dspTable[] =
 #endif
 #ifdef GDSP_HISTOGRAM                                  /* the genome-wide distribution of the values, after those */
 	 , dspinforecord("histogram"   , op_histogram)      , dspinfoalias ("hist")           , dspinfoalias ("distribution")
+#endif
+#ifdef GDSP_CORRELATE                                  /* the signal against a second track, after that */
+	 , dspinforecord("correlate"   , op_correlate)      , dspinfoalias ("correlation")    , dspinfoalias ("pearson")
+	 , dspinfoalias ("covariance")
 #endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS
@@ -636,6 +643,9 @@ static void ensure_device_comm (void)
 #endif
 #ifdef GDSP_HISTOGRAM
 	check_gdsp (gdsp_genome_histogram_use_comm (deviceComm), "hand the communicator to histogram");
+#endif
+#ifdef GDSP_CORRELATE
+	check_gdsp (gdsp_genome_correlation_use_comm (deviceComm), "hand the communicator to correlate");
 #endif
 	if (trackOperations)
 		{
@@ -1252,8 +1262,9 @@ static void stage_chromosome (int ci, staging** out)
 	}
 
 /* apply and forget the pending intervals; `everyChromosome` also visits chromosomes
- * without intervals (needed when clearing, or for multiply/divide's gap rule) */
-void ib_flush_apply (int overlapOp, int clearFlags, valtype missingVal, int everyChromosome)
+ * without intervals (needed when clearing, or for multiply/divide's gap rule).  toPartner: into each chromosome's
+ * partner buffer and not into the signal (correlate's second track) */
+static void ib_flush_apply_into (int toPartner, int overlapOp, int clearFlags, valtype missingVal, int everyChromosome)
 	{
 	for (int ci=0 ; ci<numChroms ; ci++)
 		{
@@ -1261,12 +1272,19 @@ void ib_flush_apply (int overlapOp, int clearFlags, valtype missingVal, int ever
 		staging* st;
 		stage_chromosome (ci, &st);
 		spec* s = chromsSorted[ci];
-		check_gdsp (gdsp_apply_intervals (s->valVector, s->length, st->d_start, st->d_end, st->d_val, st->d_off, st->d_list,
+		valtype* target = toPartner? partner_of (s) : s->valVector;
+		check_gdsp (gdsp_apply_intervals (target, s->length, st->d_start, st->d_end, st->d_val, st->d_off, st->d_list,
 		                                  overlapOp, clearFlags, missingVal, op_stream ()), "apply intervals");
 		pend[ci].count = 0;
 		}
 	pendTotal = 0;
 	}
+
+void ib_flush_apply (int overlapOp, int clearFlags, valtype missingVal, int everyChromosome)
+	{ ib_flush_apply_into (false, overlapOp, clearFlags, missingVal, everyChromosome); }
+
+void ib_flush_apply_partner (int overlapOp, int clearFlags, valtype missingVal, int everyChromosome)
+	{ ib_flush_apply_into (true, overlapOp, clearFlags, missingVal, everyChromosome); }
 
 void ib_flush_scale (int divide, valtype infinityVal)
 	{
@@ -2191,6 +2209,9 @@ int main (int argc, char** argv)
 #endif
 #ifdef GDSP_HISTOGRAM
 	if (deviceComm != NULL) gdsp_genome_histogram_use_comm (NULL);
+#endif
+#ifdef GDSP_CORRELATE
+	if (deviceComm != NULL) gdsp_genome_correlation_use_comm (NULL);
 #endif
 	if (deviceComm != NULL) { gdsp_percentiles_use_comm (NULL);  gdsp_comm_destroy (deviceComm); }
 	return EXIT_SUCCESS;

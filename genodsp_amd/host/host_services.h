@@ -15,6 +15,7 @@ void ib_begin       (void);
 void ib_add         (spec* s, u32 start, u32 end, valtype val);
 u64  ib_pending     (void);
 void ib_flush_apply (int overlapOp, int clearFlags, valtype missingVal, int everyChromosome);
+void ib_flush_apply_partner (int overlapOp, int clearFlags, valtype missingVal, int everyChromosome);   /* into partner_of() */
 void ib_flush_scale (int divide, valtype infinityVal);
 void ib_flush_mask  (int inside, valtype outsideVal, int binarizeFirst);
 void ib_flush_over  (int wantMax, valtype fillVal);
@@ -54,6 +55,7 @@ typedef struct sample_opts { u32 window;  valtype minAllowed, maxAllowed;  int p
 void  sample_opts_init  (sample_opts* o);
 int   sample_opts_take  (sample_opts* o, char* name, char* arg, int accepts);
 int   signal_sources    (char* name, gdsp_xsum_source** sources);   /* signal_parts() as the library's source table */
+int   place_interval    (char* name, char* filename, char* chrom, spec* s, u32 start, u32 end, u32* adjStart, u32* adjEnd);
 int   format_value      (char* text, size_t size, valtype v, int precision);   /* %.17g when precision < 0 */
 FILE* open_table        (char* name, char* filename);               /* --output=<file>, or stdout */
 void  close_table       (FILE* out);

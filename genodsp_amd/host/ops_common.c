@@ -106,6 +106,30 @@ int signal_sources (char* name, gdsp_xsum_source** sources)
 	return nsrc;
 	}
 
+/* where an interval of a file-driven operator (add, ..., correlate) lies in chromosome s's vector: [start, end) of the
+ * chromosome, the origin already taken off, as [*adjStart, *adjEnd) of the vector (add.c:245-270).  An interval beyond
+ * the end of a chromosome that begins at 0 ends the run with the complaint; false: no base of it is in the vector */
+int place_interval (char* name, char* filename, char* chrom, spec* s, u32 start, u32 end, u32* adjStart, u32* adjEnd)
+	{
+	*adjStart = start;  *adjEnd = end;
+	if (s->start == 0)
+		{
+		if (end > s->length)
+			{
+			fprintf (stderr, "[%s] in \"%s\", %s %d %d is beyond the end of the chromosome (L=%d)\n",
+			                 name, filename, chrom, start, end, s->length);
+			exit (EXIT_FAILURE);
+			}
+		return true;
+		}
+	if (end <= s->start) return false;
+	*adjEnd   = end - s->start;
+	*adjStart = (start <= s->start)? 0 : start - s->start;
+	if (*adjStart >= s->length) return false;
+	if (*adjEnd   >= s->length) *adjEnd = s->length;
+	return true;
+	}
+
 /* "%.17g", or valtypeFmtPrec with a precision (>= 0), into text[size]; -> what snprintf returns */
 int format_value (char* text, size_t size, valtype v, int precision)
 	{

@@ -136,24 +136,8 @@ static void fileop_apply (dspop* _op)
 		if (!s->flag) { if (trackOperations) fprintf (stderr, "%s(%s)\n", _op->name, chrom);  s->flag = true; }
 
 		start -= o;
-		u32 adjStart = start, adjEnd = end;
-		if (s->start == 0)
-			{
-			if (end > s->length)
-				{
-				fprintf (stderr, "[%s] in \"%s\", %s %d %d is beyond the end of the chromosome (L=%d)\n",
-				                 _op->name, op->filename, chrom, start, end, s->length);
-				exit (EXIT_FAILURE);
-				}
-			}
-		else
-			{
-			if (end <= s->start) continue;
-			adjEnd   = end - s->start;
-			adjStart = (start <= s->start)? 0 : start - s->start;
-			if (adjStart >= s->length) continue;
-			if (adjEnd   >= s->length) adjEnd = s->length;
-			}
+		u32 adjStart, adjEnd;
+		if (!place_interval (_op->name, op->filename, chrom, s, start, end, &adjStart, &adjEnd)) continue;
 		if (scaling)
 			{
 			if (adjStart < prevEnd)

@@ -386,6 +386,57 @@ int gdsp_genome_stats_use_comm (gdsp_comm* comm);     /* NULL switches back to h
 /* what the last gdsp_genome_stats did: [0] n, [1] lane flushes of pass 1, [2] of pass 2, [3] q that were +inf */
 void gdsp_genome_stats_last (uint64_t out[4]);
 
+/* ---- correlate (not in the reference): the signal against a second track -- covariance, Pearson r, regression ------
+ * A pair source is x = d_x[0 .. n) and y = d_y[0 .. n), with `first`, `device` and `stream` as in gdsp_xsum_source.  Both
+ * pointers are 8-byte aligned; their 16-byte alignment may differ (a y that is congruent to x modulo 16 bytes is read
+ * with the same 16-byte loads; any other y is read value by value: as exact, slower).
+ * The pair sample is every window-th position, counted from the chromosome's first base as for stats, that passes all of
+ *   !(x < lo) && !(x > hi), x finite, !(y < ylo) && !(y > yhi), y finite;          n is its size.
+ * Pass 1: the exact sums Sx, Sy over the pair sample.  sumx, sumy are those sums rounded once; meanx = Sx / n and
+ *   meany = Sy / n, each rounded once (gdsp_xsum_div_round).
+ * Pass 2: per pair dx = fl(x - meanx), dy = fl(y - meany), qxx = fl(dx dx), qyy = fl(dy dy), qxy = fl(dx dy), without
+ *   fma (the rule of stats' q), each of the three summed exactly.  A q that is not finite (qxx, qyy = +inf; qxy = +-inf,
+ *   or NaN from inf * 0) is counted in its image's GDSP_XSUM_WORD_INF and not added.
+ *   varx = (sum of qxx) / n rounded once, +inf when some qxx was not finite; vary likewise;
+ *   cov  = (sum of qxy) / n rounded once, NaN when some qxy was not finite;  sdx = sqrt (varx), sdy = sqrt (vary).
+ *   (The three overflow separately: x alternating +-DBL_MAX against y = 1, 2, 1, 2, ... has every qxx = +inf but every
+ *   qxy = fl(+-DBL_MAX * -+0.5) finite, so varx is +inf and cov is -DBL_MAX/2, not NaN; against y = 1, 5, 1, 5, ...
+ *   every qxy is -inf and cov is NaN.)
+ * The rest is derived on the host, in plain IEEE double, from those once-rounded figures, so it too is a function of
+ * the pair sample alone -- not of the cut into pairs, devices or ranks, of tiles, grid or dispatch order:
+ *   correlation: (mx, ex) = frexp (sdx), (my, ey) = frexp (sdy), r = ldexp (cov, -(ex + ey)) / fl(mx my), clamped to
+ *     [-1, 1]: symmetric in x and y, no spurious overflow or underflow.  NaN when n = 0, when varx or vary is 0 or not
+ *     finite, or when cov is NaN.
+ *   slope = fl(cov / varx), intercept = fl(meany - fl(slope meanx)): y regressed on x.  NaN when varx is 0 or not
+ *     finite, or when cov is NaN.
+ *   n = 0: both sums are +0.0 and everything else is NaN.
+ * Agreement with stats: when every sampled y is admitted (finite and within ylo, yhi), count, sumx, meanx, varx and sdx
+ *   are bit for bit what gdsp_genome_stats gives for x with the same window, lo and hi.
+ * Symmetry: swapping x and y, and their limits, swaps the x and y figures; cov and correlation keep the same bits.
+ *
+ * The accumulators are GDSP_XSUM_WORDS images side by side: 2 for pass 1 (Sx, Sy), 3 for pass 2 (qxx, qyy, qxy).  Each
+ * image's count word holds n, and each has its own INF and FLUSHES words.  gdsp_xsum_init and gdsp_xsum_fold act on
+ * one image: call them per image (d_acc + k * GDSP_XSUM_WORDS). */
+typedef struct gdsp_xsum_pair { const double* d_x; const double* d_y; uint32_t n; uint32_t first; int device; void* stream; } gdsp_xsum_pair;
+uint32_t gdsp_xsum_pair_tile (void);                  /* pairs per tile of the kernel's walk (what tests size their shapes by) */
+/* pass 1 into 2 images, pass 2 (means finite) into 3; one launch per 32 pairs, all on the current device */
+int gdsp_xsum_pair_accumulate_batch     (const gdsp_xsum_pair* pairs, int npairs, uint32_t window, double lo, double hi,
+                                         double ylo, double yhi, uint64_t* d_acc, void* stream);
+int gdsp_xsum_pair_accumulate_dev_batch (const gdsp_xsum_pair* pairs, int npairs, uint32_t window, double lo, double hi,
+                                         double ylo, double yhi, double meanx, double meany, uint64_t* d_acc, void* stream);
+/* end to end, like gdsp_genome_stats (several devices, the communicator of gdsp_genome_correlation_use_comm, or the
+ * `reduce` hook, called once per pass over the images side by side: 144 words, then 216).  The figure order: */
+enum { GDSP_CORR_COUNT = 0, GDSP_CORR_SUMX, GDSP_CORR_SUMY, GDSP_CORR_MEANX, GDSP_CORR_MEANY, GDSP_CORR_VARX, GDSP_CORR_VARY,
+       GDSP_CORR_SDX, GDSP_CORR_SDY, GDSP_CORR_COV, GDSP_CORR_CORRELATION, GDSP_CORR_SLOPE, GDSP_CORR_INTERCEPT,
+       GDSP_CORR_FIGURES };                           /* out[13]: count, sumx, sumy, meanx, meany, varx, vary, sdx, sdy,
+                                                         covariance, correlation, slope, intercept */
+int gdsp_genome_correlation (const gdsp_xsum_pair* pairs, int npairs, uint32_t window, double lo, double hi,
+                             double ylo, double yhi, gdsp_reduce_fn reduce, void* reduceCtx, double* out);
+int gdsp_genome_correlation_use_comm (gdsp_comm* comm);   /* NULL switches back to host sums */
+/* what the last gdsp_genome_correlation did: [0] n, [1] lane flushes of pass 1 (both images), [2] of pass 2 (all three),
+ * [3] qxx, [4] qyy, [5] qxy that were not finite, [6] and [7] zero */
+void gdsp_genome_correlation_last (uint64_t out[8]);
+
 /* ---- statsover (not in the reference): one signal quantified over many intervals, exact ---------------------------
  * For a vector v of n doubles, an interval [s, e) with 0 <= s < e <= n, and limits lo, hi:
  *   the sample of the interval is stats' sample restricted to it: the bases i in [s, e) with !(v[i] < lo) &&
