@@ -726,6 +726,63 @@ def xsum_pair_image(pairs, window=1, lo=-DBL_MAX, hi=DBL_MAX, ylo=-DBL_MAX, yhi=
     return acc.download(np.uint64, k * XSUM_WORDS, stream=stream).reshape(k, XSUM_WORDS)
 
 
+# ------------------------------------- crosscorrelate / autocorrelate (not in the reference) ----
+
+LAG_MAX_LAGS = 4096
+
+
+def lag_tile():
+    """Positions per tile of the lag kernel's walk."""
+    return int(lib().gdsp_lag_tile())
+
+
+def lag_block():
+    """Lags a workgroup of the lag kernel owns."""
+    return int(lib().gdsp_lag_block())
+
+
+def lag_products(pairs, lag_lo, nlags, meanx, meany, stream=None):
+    """The folded images of the lagged products of pairs (as xsum_pairs, whole chromosomes), np.uint64[nlags, XSUM_WORDS]:
+    image k sums fl(fl(x[i] - meanx) * fl(y[i + lag_lo + k] - meany)) exactly (gdsp_lag_products_batch); its count word
+    is the number of products taken, its INF word those that were not finite."""
+    nlags = int(nlags)
+    acc = DeviceBuffer(max(1, nlags) * XSUM_WORDS * 8)
+    acc.upload(np.zeros(max(1, nlags) * XSUM_WORDS, np.uint64), stream=stream)
+    tab = xsum_pairs(pairs, stream)
+    call("gdsp_lag_products_batch", tab, len(pairs), int(lag_lo), nlags, float(meanx), float(meany), C.c_void_p(acc.ptr), _sp(stream))
+    return acc.download(np.uint64, nlags * XSUM_WORDS, stream=stream).reshape(nlags, XSUM_WORDS)
+
+
+def genome_lag_correlation(pairs, lag_lo, nlags, allreduce=None, stream=None):
+    """Covariance and correlation of x against y shifted by each of the lags lag_lo .. lag_lo + nlags - 1, each exact and
+    rounded once (gdsp_genome_lag_correlation): the figures of CORRELATION_FIGURES over the bases where both are finite,
+    and under "lags", "pairs", "covariances", "correlations" one np array entry per lag.  pairs: as xsum_pairs, whole
+    chromosomes.  allreduce: genome_stats' hook."""
+    nlags = int(nlags)
+    tab = xsum_pairs(pairs, stream)
+    fig = (C.c_double * len(CORRELATION_FIGURES))()
+    count = np.zeros(max(1, nlags), np.uint64)
+    cov = np.zeros(max(1, nlags), np.float64)
+    corr = np.zeros(max(1, nlags), np.float64)
+    failure = []
+    cb = _reduce_hook(allreduce, failure)
+    with _hook_failure_first(failure):
+        call("gdsp_genome_lag_correlation", tab, len(pairs), int(lag_lo), nlags, cb, None, fig,
+             count.ctypes.data_as(C.c_void_p), cov.ctypes.data_as(C.c_void_p), corr.ctypes.data_as(C.c_void_p))
+    out = dict(zip(CORRELATION_FIGURES, [float(x) for x in fig]))
+    out["lags"] = np.arange(nlags, dtype=np.int64) + int(lag_lo)
+    out["pairs"], out["covariances"], out["correlations"] = count[:nlags], cov[:nlags], corr[:nlags]
+    return out
+
+
+def genome_lag_correlation_last():
+    """What the last genome_lag_correlation did: N, the products taken over all lags, lane flushes into the device images,
+    and the products that were not finite."""
+    out = (C.c_uint64 * 8)()
+    lib().gdsp_genome_lag_correlation_last(out)
+    return dict(zip(("count", "products", "flushes", "nonfinite_products"), [int(x) for x in out]))
+
+
 # ------------------------------------------------------ histogram (not in the reference) ----
 
 HISTOGRAM_MAX_BINS = 65536

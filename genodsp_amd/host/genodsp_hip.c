@@ -72,6 +72,10 @@ dspprototypes(op_histogram)
 #ifdef GDSP_CORRELATE                                  /* not in the reference: ops_correlate.c */
 dspprototypes(op_correlate)
 #endif
+#ifdef GDSP_LAGCORR                                    /* not in the reference: ops_lagcorr.c */
+dspprototypes(op_crosscorrelate)
+dspprototypes(op_autocorrelate)
+#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
@@ -136,6 +140,11 @@ static dspinfo dspTable[] =
 #ifdef GDSP_CORRELATE                                  /* the signal against a second track, after that */
 	 , dspinforecord("correlate"   , op_correlate)      , dspinfoalias ("correlation")    , dspinfoalias ("pearson")
 	 , dspinfoalias ("covariance")
+#endif
+#ifdef GDSP_LAGCORR                                    /* the same at every lag of a range, and the signal against itself */
+	 , dspinforecord("crosscorrelate", op_crosscorrelate) , dspinfoalias ("cross_correlate") , dspinfoalias ("xcorr")
+	 , dspinfoalias ("ccf")
+	 , dspinforecord("autocorrelate" , op_autocorrelate)  , dspinfoalias ("autocorrelation") , dspinfoalias ("acf")
 #endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS
@@ -647,6 +656,9 @@ static void ensure_device_comm (void)
 #ifdef GDSP_CORRELATE
 	check_gdsp (gdsp_genome_correlation_use_comm (deviceComm), "hand the communicator to correlate");
 #endif
+#ifdef GDSP_LAGCORR
+	check_gdsp (gdsp_genome_lag_correlation_use_comm (deviceComm), "hand the communicator to crosscorrelate");
+#endif
 	if (trackOperations)
 		{
 		int version = 0;
@@ -878,6 +890,9 @@ static int pipeline_wants_partners (void)
 #endif
 #ifdef GDSP_HISTOGRAM
 		  op_histogram_apply,
+#endif
+#ifdef GDSP_LAGCORR
+		  op_autocorrelate_apply,                                  /* (the signal against itself: no partner is touched) */
 #endif
 		};
 	if (shardBases) return true;                               /* (stretches and their runs: not worth a second rule) */
@@ -2212,6 +2227,9 @@ int main (int argc, char** argv)
 #endif
 #ifdef GDSP_CORRELATE
 	if (deviceComm != NULL) gdsp_genome_correlation_use_comm (NULL);
+#endif
+#ifdef GDSP_LAGCORR
+	if (deviceComm != NULL) gdsp_genome_lag_correlation_use_comm (NULL);
 #endif
 	if (deviceComm != NULL) { gdsp_percentiles_use_comm (NULL);  gdsp_comm_destroy (deviceComm); }
 	return EXIT_SUCCESS;

@@ -107,6 +107,9 @@ int   op_histogram_is_stop (dspop* op);      /* whole-genome, on the signal's pa
 int   ib_chromosomes      (void);
 u32   ib_pending_of       (int ci, spec** s, u32** start, u32** end, valtype** val);
 char* put_value_fixed     (char* p, valtype v, int precision);
+/* ops_correlate.c (correlate; compiled in with -DGDSP_CORRELATE), shared with ops_lagcorr.c: the intervals of a file, read
+ * by the rules of `add <file>`, into every chromosome's partner -- what `add <file>` would leave on an all-zero genome */
+void  load_track_into_partners (char* name, char* filename, int valColumn, int originOne);
 
 /* argument helpers used by every operator's parse function */
 #define OP_SHORT(fn, text)                                                            \

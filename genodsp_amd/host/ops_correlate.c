@@ -104,22 +104,21 @@ void op_correlate_free (dspop* _op)
 
 /* y, into every chromosome's partner: what `add <file>` (ops_intervals.c) would leave on zeros.  The first batch starts
  * every base of every chromosome from 0, the later ones add to what is there, as the main ingest does */
-static void load_track (dspop_correlate* op)
+void load_track_into_partners (char* name, char* filename, int valColumn, int originOne)
 	{
 	char    line[1001], prevChrom[1001];
 	char*   chrom;
 	spec*   s = NULL;
-	u32     start, end, o = op->originOne? 1 : 0;
+	u32     start, end, o = originOne? 1 : 0;
 	valtype val;
 	int     clearFlags = GDSP_CLEAR_FILL;
-	char*   name = op->common.name;
 
-	FILE* f = fopen (op->filename, "rt");
-	if (f == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for reading\n", name, op->filename);  exit (EXIT_FAILURE); }
+	FILE* f = fopen (filename, "rt");
+	if (f == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for reading\n", name, filename);  exit (EXIT_FAILURE); }
 	for (int i=0 ; chromsSorted[i]!=NULL ; i++) chromsSorted[i]->flag = false;
 	ib_begin ();
 	prevChrom[0] = 0;
-	while (read_interval (f, line, sizeof(line), op->valColumn, &chrom, &start, &end, &val))
+	while (read_interval (f, line, sizeof(line), valColumn, &chrom, &start, &end, &val))
 		{
 		if (val == 0.0) continue;                              /* (as add: add.c:235) */
 		if (strcmp (chrom, prevChrom) != 0)
@@ -128,7 +127,7 @@ static void load_track (dspop_correlate* op)
 		if (!s->flag) { if (trackOperations) fprintf (stderr, "%s(%s)\n", name, chrom);  s->flag = true; }
 		start -= o;
 		u32 adjStart, adjEnd;
-		if (!place_interval (name, op->filename, chrom, s, start, end, &adjStart, &adjEnd)) continue;
+		if (!place_interval (name, filename, chrom, s, start, end, &adjStart, &adjEnd)) continue;
 		ib_add (s, adjStart, adjEnd, val);
 		if (ib_pending () >= ib_batch_limit ())
 			{
@@ -145,7 +144,7 @@ void op_correlate_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_co
 	dspop_correlate* op = (dspop_correlate*) _op;
 	char* name = _op->name;
 	to_whole ();                                               /* the file addresses whole chromosomes */
-	load_track (op);
+	load_track_into_partners (name, op->filename, op->valColumn, op->originOne);
 
 	/* the signal's parts, each with the partner at the same offset */
 	sigpart* parts;

@@ -437,6 +437,46 @@ int gdsp_genome_correlation_use_comm (gdsp_comm* comm);   /* NULL switches back 
  * [3] qxx, [4] qyy, [5] qxy that were not finite, [6] and [7] zero */
 void gdsp_genome_correlation_last (uint64_t out[8]);
 
+/* ---- crosscorrelate / autocorrelate (not in the reference): the covariance and correlation at every lag of a range ---
+ * A genome is a list of pairs (x_c, y_c) of WHOLE chromosome vectors of length L_c (gdsp_xsum_pair; `first` is ignored).
+ * Lagged pairs never cross a chromosome's end or join two chromosomes.
+ * N, meanx, meany, varx, vary, sdx, sdy are exactly gdsp_genome_correlation's figures for these pairs with window 1 and
+ *   no limits: the sample is the bases where x and y are both finite.
+ * For an integer lag d, with dx = fl(x - meanx) and dy = fl(y - meany):
+ *   Q(d) = sum over c, and over the i with 0 <= i < L_c, 0 <= i+d < L_c, x_c[i] and y_c[i+d] both finite, of
+ *          fl(dx_c[i] * dy_c[i+d]):  each product one rounding, never contracted; the sum exact.
+ *   A product that is not finite is counted in that lag's GDSP_XSUM_WORD_INF word and not added.  The count word of lag
+ *   d's image holds the number of products taken, n(d) (those that were not finite included).
+ *   covariance(d) = Q(d) / N rounded once (gdsp_xsum_div_round); NaN when some product of that lag was not finite.  The
+ *     division is by N, not by n(d): the estimator of time-series software (R's acf / ccf), which needs no per-lag means,
+ *     and whose curve is a positive semi-definite sequence for y = x.  A lag no chromosome is long enough for gives +0.0.
+ *   correlation(d): from covariance(d), sdx, sdy by the frexp / ldexp rule of correlate, clamped to [-1, 1]; NaN when
+ *     varx or vary is 0 or not finite, or when covariance(d) is NaN.
+ *   N = 0: every count is 0 and every covariance and correlation is NaN.
+ * Consequences, bit for bit: lag 0 gives correlate's covariance and correlation; swapping x and y maps lag d to -d; with
+ *   y = x the curve is symmetric in d, and lag 0 is the variance and 1 (or NaN).  Nothing depends on chromosome order, on
+ *   which device holds which chromosome, on grid, tile, lag block or dispatch order.
+ *
+ * gdsp_lag_products_batch adds every pair's products into nlags images of GDSP_XSUM_WORDS words side by side, lag
+ * lagLo + k in image k, and leaves the images in canonical digits (they add as plain u64 sums).  nlags is 1 .. 4096, the
+ * lags any int32; the means are finite; the pairs are on the current device, one launch per 32 of them.  d_acc is zeroed
+ * by the caller.  gdsp_lag_tile () positions by gdsp_lag_block () lags are staged at a time (what tests size their shapes
+ * by).  The cost is N * nlags products of 13 rounded operations each: a genome at a few hundred lags takes on the order
+ * of a second. */
+uint32_t gdsp_lag_tile  (void);
+uint32_t gdsp_lag_block (void);
+int gdsp_lag_products_batch (const gdsp_xsum_pair* pairs, int npairs, int32_t lagLo, uint32_t nlags, double meanx, double meany,
+                             uint64_t* d_acc, void* stream);
+/* end to end: fig[GDSP_CORR_FIGURES] by gdsp_genome_correlation (its hook calls, then one more over the nlags * 72 words
+ * of the lag images), then count[k] = n(lagLo + k), cov[k], corr[k].  Devices, communicator and hook as for
+ * gdsp_genome_correlation. */
+int gdsp_genome_lag_correlation (const gdsp_xsum_pair* pairs, int npairs, int32_t lagLo, uint32_t nlags, gdsp_reduce_fn reduce,
+                                 void* reduceCtx, double* fig, uint64_t* count, double* cov, double* corr);
+int gdsp_genome_lag_correlation_use_comm (gdsp_comm* comm);   /* NULL switches back to host sums */
+/* what the last gdsp_genome_lag_correlation did: [0] N, [1] products taken (all lags), [2] lane flushes into the device
+ * images, [3] products that were not finite, [4] .. [7] zero */
+void gdsp_genome_lag_correlation_last (uint64_t out[8]);
+
 /* ---- statsover (not in the reference): one signal quantified over many intervals, exact ---------------------------
  * For a vector v of n doubles, an interval [s, e) with 0 <= s < e <= n, and limits lo, hi:
  *   the sample of the interval is stats' sample restricted to it: the bases i in [s, e) with !(v[i] < lo) &&
