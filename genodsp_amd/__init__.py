@@ -879,13 +879,7 @@ def interval_stats(v, start, end, lo=-DBL_MAX, hi=DBL_MAX, stream=None, vec=None
     numpy arrays in the caller's order.  v: a DeviceVector or a (vector, first, count) stretch of one; or a LIST of
     them with vec[i] naming interval i's vector (gdsp_interval_stats_batch: one launch for all of them).  Waits."""
     vecs = v if isinstance(v, list) else [v]
-    items = (BatchItem * max(1, len(vecs)))()
-    for k, item in enumerate(vecs):
-        if isinstance(item, DeviceVector):
-            items[k].d_in, items[k].n = item.ptr.value, item.n
-        else:
-            assert 0 <= int(item[1]) and int(item[1]) + int(item[2]) <= item[0].n
-            items[k].d_in, items[k].n = item[0].ptr.value + 8 * int(item[1]), int(item[2])
+    items = _read_only_items(vecs)
     start = np.ascontiguousarray(start, dtype=np.uint32)
     end = np.ascontiguousarray(end, dtype=np.uint32)
     assert start.shape == end.shape and start.ndim == 1
@@ -919,6 +913,133 @@ def interval_stats_last():
     lib().gdsp_interval_stats_times(ms)
     d = dict(zip(("intervals", "pieces", "flagged", "imaged"), [int(x) for x in out]))
     d.update(zip(("ms_cut", "ms_kernel", "ms_copy", "ms_combine"), [float(x) for x in ms]))
+    return d
+
+
+# ------------------------------------------------------- segments (not in the reference) ----
+
+RUN_PIECE = np.dtype([("vec", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32),
+                      ("piece", INTERVAL_PIECE)])                                                   # gdsp_run_piece
+SEGMENT = np.dtype([("vec", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32),
+                    ("stat", INTERVAL_STAT)])                                                       # gdsp_segment
+RUN_PIECES_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p)
+SEGMENTS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32)
+
+
+def segments_tile():
+    """The tile the piece kernel cuts runs at (values of the 16-byte aligned frame a vector lies in)."""
+    return int(lib().gdsp_segments_tile())
+
+
+def _read_only_items(vecs):
+    items = (BatchItem * max(1, len(vecs)))()
+    for k, item in enumerate(vecs):
+        if isinstance(item, DeviceVector):
+            items[k].d_in, items[k].n = item.ptr.value, item.n
+        else:                                                       # a (vector, first, count) stretch of one
+            assert 0 <= int(item[1]) and int(item[1]) + int(item[2]) <= item[0].n
+            items[k].d_in, items[k].n = item[0].ptr.value + 8 * int(item[1]), int(item[2])
+    return items
+
+
+def _copy_records(ptr, count, dtype):
+    if count == 0:
+        return np.zeros(0, dtype)
+    return np.frombuffer(C.string_at(ptr, count * dtype.itemsize), dtype=dtype).copy()
+
+
+def _segment_collector(out, failure):
+    def take(_ctx, segs, count):
+        try:
+            out.append(_copy_records(segs, count, SEGMENT))
+            return 0
+        except Exception as e:
+            failure.append(e)
+            return 1
+    return SEGMENTS_FN(take)
+
+
+def _segment_arrays(chunks):
+    rec = np.concatenate(chunks) if chunks else np.zeros(0, SEGMENT)
+    out = {"vec": rec["vec"].copy(), "start": rec["start"].copy(), "end": rec["end"].copy()}
+    out.update(_interval_figures(rec["stat"]))
+    return out
+
+
+def run_pieces(vecs, T, ties_above=False, stream=None):
+    """The device half of segments (gdsp_run_pieces_batch): every maximal stretch of members (v > T, or v >= T with
+    ties_above) inside a tile of every vector, in (vector, position) order.  -> [(records, images), ...], one pair per
+    call the library made: records an array of RUN_PIECE, images (flagged pieces, XSUM_WORDS) uint64 or None.  Waits."""
+    vecs = vecs if isinstance(vecs, list) else [vecs]
+    items = _read_only_items(vecs)
+    chunks, failure = [], []
+
+    def take(_ctx, recs, count, images):
+        try:
+            r = _copy_records(recs, count, RUN_PIECE)
+            nflag = int(np.count_nonzero(r["piece"]["flag"]))
+            img = None
+            if nflag:
+                img = np.frombuffer(C.string_at(images, nflag * XSUM_WORDS * 8), dtype=np.uint64).reshape(nflag, XSUM_WORDS).copy()
+            chunks.append((r, img))
+            return 0
+        except Exception as e:
+            failure.append(e)
+            return 1
+
+    cb = RUN_PIECES_FN(take)
+    with _hook_failure_first(failure):
+        call("gdsp_run_pieces_batch", items, len(vecs), float(T), 1 if ties_above else 0, cb, None, _sp(stream))
+    return chunks
+
+
+def segments_from_pieces(chunks, merge_gap=0, min_length=1, min_height=None):
+    """The host half of segments, no GPU (gdsp_segments_feed / gdsp_segments_finish): chunks is a list of (records,
+    images) pairs as run_pieces gives them, each fed on its own.  -> (dict of arrays: vec, start, end, count, sum, mean,
+    min, max, maxpos; dict of counts: runs, pieces, flagged, kept)."""
+    out, failure = [], []
+    cb = _segment_collector(out, failure)
+    b = C.c_void_p()
+    call("gdsp_segments_create", C.byref(b), int(merge_gap), int(min_length), 0 if min_height is None else 1,
+         0.0 if min_height is None else float(min_height), cb, None)
+    try:
+        with _hook_failure_first(failure):
+            for recs, images in chunks:
+                recs = np.ascontiguousarray(recs, dtype=RUN_PIECE)
+                img = None if images is None else np.ascontiguousarray(images, dtype=np.uint64)
+                call("gdsp_segments_feed", b, recs.ctypes.data_as(C.c_void_p), recs.size,
+                     None if img is None else img.ctypes.data_as(C.c_void_p))
+            call("gdsp_segments_finish", b)
+        counts = (C.c_uint64 * 4)()
+        lib().gdsp_segments_counts(b, counts)
+    finally:
+        lib().gdsp_segments_destroy(b)
+    return _segment_arrays(out), dict(zip(("runs", "pieces", "flagged", "kept"), [int(x) for x in counts]))
+
+
+def segments(vecs, T, ties_above=False, merge_gap=0, min_length=1, min_height=None, stream=None):
+    """The thresholded regions of the vectors with statsover's figures (gdsp_segments_batch): runs of members joined
+    across gaps of at most merge_gap bases, those shorter than min_length or (with min_height) lower than it dropped.
+    -> dict of numpy arrays: vec, start, end, count, sum, mean, min, max, maxpos (-1 where the sample is empty), in
+    (vector, position) order.  The vectors are only read.  Waits."""
+    vecs = vecs if isinstance(vecs, list) else [vecs]
+    items = _read_only_items(vecs)
+    out, failure = [], []
+    cb = _segment_collector(out, failure)
+    with _hook_failure_first(failure):
+        call("gdsp_segments_batch", items, len(vecs), float(T), 1 if ties_above else 0, int(merge_gap), int(min_length),
+             0 if min_height is None else 1, 0.0 if min_height is None else float(min_height), cb, None, _sp(stream))
+    return _segment_arrays(out)
+
+
+def segments_last():
+    """What the last segments call did: runs, pieces, flagged pieces (summed again), kept segments; and ms spent in the
+    counting pass, in the piece kernel, copying and waiting, consuming the pieces."""
+    out, ms = (C.c_uint64 * 4)(), (C.c_double * 4)()
+    lib().gdsp_segments_last(out)
+    lib().gdsp_segments_times(ms)
+    d = dict(zip(("runs", "pieces", "flagged", "kept"), [int(x) for x in out]))
+    d.update(zip(("ms_count", "ms_kernel", "ms_copy", "ms_consume"), [float(x) for x in ms]))
     return d
 
 

@@ -172,6 +172,17 @@ SIGNATURES = {
     "gdsp_interval_stats_combine": (_int, [_vp, _u32, _vp, _vp]),
     "gdsp_interval_stats_last": (None, [_vp]),
     "gdsp_interval_stats_times": (None, [_vp]),
+    # segments (not in the reference)
+    "gdsp_segments_tile": (_u32, []),
+    "gdsp_run_pieces_batch": (_int, [_vp, _int, _f64, _int, _vp, _vp, _vp]),
+    "gdsp_segments_create": (_int, [C.POINTER(_vp), _u32, _u32, _int, _f64, _vp, _vp]),
+    "gdsp_segments_feed": (_int, [_vp, _vp, _u32, _vp]),
+    "gdsp_segments_finish": (_int, [_vp]),
+    "gdsp_segments_counts": (None, [_vp, _vp]),
+    "gdsp_segments_destroy": (None, [_vp]),
+    "gdsp_segments_batch": (_int, [_vp, _int, _f64, _int, _u32, _u32, _int, _f64, _vp, _vp, _vp]),
+    "gdsp_segments_last": (None, [_vp]),
+    "gdsp_segments_times": (None, [_vp]),
     # histogram (not in the reference)
     "gdsp_histogram_uniform_edges": (_int, [_f64, _f64, _u32, _vp]),
     "gdsp_histogram_init": (_int, [_vp, _u32, _vp]),

@@ -76,6 +76,9 @@ dspprototypes(op_correlate)
 dspprototypes(op_crosscorrelate)
 dspprototypes(op_autocorrelate)
 #endif
+#ifdef GDSP_SEGMENTS                                   /* not in the reference: ops_segments.c */
+dspprototypes(op_segments)
+#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
@@ -145,6 +148,10 @@ static dspinfo dspTable[] =
 	 , dspinforecord("crosscorrelate", op_crosscorrelate) , dspinfoalias ("cross_correlate") , dspinfoalias ("xcorr")
 	 , dspinfoalias ("ccf")
 	 , dspinforecord("autocorrelate" , op_autocorrelate)  , dspinfoalias ("autocorrelation") , dspinfoalias ("acf")
+#endif
+#ifdef GDSP_SEGMENTS                                   /* the signal's own regions above a threshold, quantified, after those */
+	 , dspinforecord("segments"    , op_segments)       , dspinfoalias ("callpeaks")      , dspinfoalias ("call_peaks")
+	 , dspinfoalias ("islands")
 #endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS
@@ -893,6 +900,9 @@ static int pipeline_wants_partners (void)
 #endif
 #ifdef GDSP_LAGCORR
 		  op_autocorrelate_apply,                                  /* (the signal against itself: no partner is touched) */
+#endif
+#ifdef GDSP_SEGMENTS
+		  op_segments_apply,
 #endif
 		};
 	if (shardBases) return true;                               /* (stretches and their runs: not worth a second rule) */
@@ -2189,6 +2199,9 @@ int main (int argc, char** argv)
 #endif
 #ifdef GDSP_HISTOGRAM
 					if (op_histogram_is_stop (stopOp)) bpb = 8;              /* one read of the signal */
+#endif
+#ifdef GDSP_SEGMENTS
+					if (op_segments_is (stopOp)) bpb = 8;                    /* one read of the signal (and of the tiles that hold regions) */
 #endif
 					wall_phase (stopOp, stopOp->name, now_ms () - t0, total, "bases", bpb);
 					}

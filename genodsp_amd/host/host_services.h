@@ -59,6 +59,10 @@ int   place_interval    (char* name, char* filename, char* chrom, spec* s, u32 s
 int   format_value      (char* text, size_t size, valtype v, int precision);   /* %.17g when precision < 0 */
 FILE* open_table        (char* name, char* filename);               /* --output=<file>, or stdout */
 void  close_table       (FILE* out);
+/* the numbers of a table (statsover, segments), written at p; -> behind what was written.  put_value: format_value's text,
+ * at most 400 characters of it, by hand where that gives printf's characters (integers below 10^15, fixed point) */
+char* put_unsigned      (char* p, unsigned long long u);
+char* put_value         (char* p, valtype v, int precision);
 
 /* ops_fused.c: run op (and the operators after it, up to stopOp) as one fused kernel when
  * the chain is one the device library fuses; returns how many operators were consumed (0 = none) */
@@ -104,6 +108,8 @@ int   op_statsover_is     (dspop* op);
 u64   op_statsover_bases  (dspop* op);       /* summed length of the intervals since the last call (--report=gpu) */
 /* ops_histogram.c (histogram; compiled in with -DGDSP_HISTOGRAM) */
 int   op_histogram_is_stop (dspop* op);      /* whole-genome, on the signal's parts as they are; the signal is only read */
+/* ops_segments.c (segments; compiled in with -DGDSP_SEGMENTS) */
+int   op_segments_is      (dspop* op);       /* whole-genome, on whole chromosomes; the signal is only read */
 int   ib_chromosomes      (void);
 u32   ib_pending_of       (int ci, spec** s, u32** start, u32** end, valtype** val);
 char* put_value_fixed     (char* p, valtype v, int precision);

@@ -3,6 +3,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <float.h>
+#include <math.h>
 #include "genodsp_interface.h"
 #include "utilities.h"
 #include "host_services.h"
@@ -147,3 +148,34 @@ FILE* open_table (char* name, char* filename)
 	}
 
 void close_table (FILE* out) { if (out != stdout) fclose (out);  else fflush (stdout); }
+
+/* ---- the hand-rolled number formatting of the tables (statsover, segments) ---- */
+
+char* put_unsigned (char* p, unsigned long long u)
+	{
+	char digits[24];
+	int  n = 0;
+	do { digits[n++] = (char) ('0' + u % 10);  u /= 10; } while (u != 0);
+	while (n > 0) *(p++) = digits[--n];
+	return p;
+	}
+
+static int clipped (int written) { return (written > 399)? 399 : written; }     /* (what snprintf kept of a longer text) */
+
+/* format_value's text, at most 400 characters of it.  Integers below 10^15 (read depth, and its sums)
+ * and fixed-point values take the hand-rolled forms: the same characters as printf's */
+char* put_value (char* p, valtype v, int precision)
+	{
+	if (precision >= 0)
+		{
+		char* q = put_value_fixed (p, v, precision);
+		if (q != NULL) return q;
+		return p + clipped (format_value (p, 400, v, precision));
+		}
+	if ((fabs (v) < 1e15) && (v == floor (v)) && ((v != 0) || !signbit (v)))
+		{
+		if (v < 0) *(p++) = '-';
+		return put_unsigned (p, (unsigned long long) fabs (v));
+		}
+	return p + clipped (format_value (p, 400, v, precision));
+	}

@@ -1,0 +1,282 @@
+/* ops_segments.c -- segments (device shim).  Not an operator of the reference: the table every peak caller ends in --
+ * one line per region of the signal above a threshold, with its count, sum (area), mean, min, max (height) and the
+ * position of the maximum (summit).  Regions can be joined across short gaps, and dropped when they are short or never
+ * reach a second, higher threshold (hysteresis calling).  The signal is not modified; the variables segments, covered
+ * and longest are set.
+ *
+ * A genome-wide operator like statsover: the driver brings stretches back to whole chromosomes first.  Each device in
+ * use gets one gdsp_segments_batch (include/genodsp_hip.h) over its chromosomes in the order of the chromosomes file:
+ * the signal is read on the device, the regions and their exact figures arrive here a bounded number at a time, and
+ * their lines are written as they arrive.  The table follows the chromosomes file (the order of the final report),
+ * positions ascending; a chromosome whose turn has not come yet -- it lives on a device that is served before that of
+ * an earlier chromosome -- waits as text (a single device never waits).
+ *
+ * The driver's table rows and branches that name this operator are compiled only with -DGDSP_SEGMENTS
+ * (genodsp_amd/host/Makefile); every call into the device library for it stays in this file. */
+#include <stdlib.h>
+#include <stdio.h>
+#include <string.h>
+#include <math.h>
+#include <float.h>
+#include "genodsp_interface.h"
+#include "genodsp_hip.h"
+#include "utilities.h"
+#include "host_services.h"
+
+dspprototypes(op_segments)
+
+typedef struct dspop_segments
+	{
+	dspop   common;
+	char*   thresholdVarName;  valtype threshold;  int tiesAbove;           /* (as binarize) */
+	u32     mergeGap, minLength;
+	int     haveMinHeight;  char* minHeightVarName;  valtype minHeight;
+	char*   outFilename;
+	int     precision, originOne, quiet;
+	} dspop_segments;
+
+OP_SHORT (op_segments, "print the regions above a threshold with their count, sum, mean, min, max and summit (not in genodsp)")
+
+void op_segments_usage (char* name, FILE* f, char* indent)
+	{
+	if (indent == NULL) indent = "";
+	fprintf (f, "%sPrint one line per region of consecutive bases above a threshold: chromosome, start, end,\n", indent);
+	fprintf (f, "%sthen the count, sum, mean, min and max of the signal inside the region and the position of\n", indent);
+	fprintf (f, "%sthe (first) maximum; sum and mean are exact and rounded once. Regions can be joined across\n", indent);
+	fprintf (f, "%sshort gaps (whose bases are not counted) and dropped when they are short or low. Sets the\n", indent);
+	fprintf (f, "%svariables segments, covered and longest. The signal is not modified. Not in genodsp.\n\n", indent);
+	fprintf (f, "%susage: %s [<threshold>] [options]\n", indent, name);
+	fprintf (f, "%s  <threshold>              numeric threshold (default 0.0)\n", indent);
+	fprintf (f, "%s  --threshold=<variable>   (T=) threshold from a named variable, e.g. percentile99\n", indent);
+	fprintf (f, "%s  --ties:below|above       whether values equal to the threshold count as below (default) or above\n", indent);
+	fprintf (f, "%s  --mergegap=<bases>       join regions no more than this many bases apart (default 0)\n", indent);
+	fprintf (f, "%s  --minlength=<bases>      drop regions shorter than this, after joining (default 1)\n", indent);
+	fprintf (f, "%s  --minheight=<value|variable>  drop regions whose maximum is below this\n", indent);
+	fprintf (f, "%s  --output=<file>          write the table there (default: stdout, when the operator runs)\n", indent);
+	fprintf (f, "%s  --precision=<number>     digits after the point (default: all of them)\n", indent);
+	fprintf (f, "%s  --origin=one|zero        coordinate convention of the positions printed\n", indent);
+	fprintf (f, "%s  --quiet                  print no table (the variables are still set)\n", indent);
+	}
+
+static u32 bases_arg (char* name, char* arg, char* argVal, const char* what)
+	{
+	u32 v;
+	if (*skip_whitespace (argVal) == '-') chastise ("[%s] %s can't be negative (\"%s\")\n", name, what, arg);
+	if (!try_string_to_u32 (argVal, &v)) chastise ("[%s] %s must be a number of bases (\"%s\")\n", name, what, arg);
+	return v;
+	}
+
+dspop* op_segments_parse (char* name, int argc, char** argv)
+	{
+	dspop_segments* op = (dspop_segments*) new_op (name, sizeof(dspop_segments), true);
+	int haveThreshold = false;
+	op->minLength = 1;
+	op->precision = -1;
+	op->originOne = (int) get_named_global ("originOne", false);
+	for ( ; argc > 0 ; argv++, argc--)
+		{
+		char* arg = argv[0];
+		char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
+		if (is_opt3 (arg, "threshold", "T"))                 /* a variable NAME only, as binarize */
+			{
+			if (haveThreshold) { fprintf (stderr, "[%s] threshold specified more than once (at \"%s\")\n", name, arg);  exit (EXIT_FAILURE); }
+			op->thresholdVarName = copy_string (argVal);
+			haveThreshold = true;
+			continue;
+			}
+		if ((strcmp (arg, "--ties:below") == 0) || (strcmp (arg, "--ties=below") == 0)) { op->tiesAbove = false;  continue; }
+		if ((strcmp (arg, "--ties:above") == 0) || (strcmp (arg, "--ties=above") == 0)) { op->tiesAbove = true;   continue; }
+		if (strcmp_prefix (arg, "--mergegap=") == 0)  { op->mergeGap  = bases_arg (name, arg, argVal, "--mergegap");   continue; }
+		if (strcmp_prefix (arg, "--minlength=") == 0) { op->minLength = bases_arg (name, arg, argVal, "--minlength");  continue; }
+		if (strcmp_prefix (arg, "--minheight=") == 0)
+			{
+			if (op->minHeightVarName != NULL) { free (op->minHeightVarName);  op->minHeightVarName = NULL; }
+			value_or_variable (argVal, &op->minHeight, &op->minHeightVarName);
+			op->haveMinHeight = true;
+			continue;
+			}
+		if (strcmp_prefix (arg, "--output=") == 0)
+			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
+		if (strcmp_prefix (arg, "--precision=") == 0)
+			{
+			op->precision = string_to_int (argVal);
+			if (op->precision < 0) chastise ("[%s] precision can't be negative (\"%s\")\n", name, arg);
+			continue;
+			}
+		if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { op->originOne = true;   continue; }
+		if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { op->originOne = false;  continue; }
+		if ((strcmp (arg, "--quiet") == 0) || (strcmp (arg, "--silent") == 0)) { op->quiet = true;  continue; }
+		if (strcmp (arg, "--debug") == 0) continue;
+		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
+		if (!haveThreshold) { op->threshold = string_to_valtype (arg);  haveThreshold = true;  continue; }
+		valtype again;
+		if (try_string_to_valtype (arg, &again))
+			{ fprintf (stderr, "[%s] threshold specified more than once (at \"%s\")\n", name, arg);  exit (EXIT_FAILURE); }
+		chastise ("[%s] Can't understand \"%s\"\n", name, arg);
+		}
+	return (dspop*) op;
+	}
+
+void op_segments_free (dspop* _op)
+	{
+	dspop_segments* op = (dspop_segments*) _op;
+	if (op->thresholdVarName != NULL) free (op->thresholdVarName);
+	if (op->minHeightVarName != NULL) free (op->minHeightVarName);
+	if (op->outFilename      != NULL) free (op->outFilename);
+	free (op);
+	}
+
+/* ------------------------------------------------------------------------------------------- the table ---- */
+/* a chromosome of the table, in the order of the chromosomes file */
+typedef struct chromtext { spec* s;  int done;  char* text;  size_t len, cap; } chromtext;
+
+typedef struct tablestate
+	{
+	dspop_segments* op;
+	FILE*      out;
+	chromtext* chroms;  int numChroms, next;                  /* chroms[next] is the one whose lines go straight out */
+	int*       mine;    int numMine, upTo;                    /* this device's vectors as indices into chroms; those before upTo are complete */
+	char*      text;    size_t textCap;
+	u64        kept, covered, longest;
+	} tablestate;
+
+static void* must (void* p, const char* name)
+	{
+	if (p == NULL) { fprintf (stderr, "[%s] out of memory\n", name);  exit (EXIT_FAILURE); }
+	return p;
+	}
+
+/* every chromosome whose turn has come and that is complete leaves; so does what the next one has waiting */
+static void advance (tablestate* t)
+	{
+	while (t->next < t->numChroms)
+		{
+		chromtext* c = &t->chroms[t->next];
+		if (c->len != 0) { fwrite (c->text, 1, c->len, t->out);  c->len = 0; }
+		if (c->text != NULL) { free (c->text);  c->text = NULL;  c->cap = 0; }
+		if (!c->done) break;
+		t->next++;
+		}
+	}
+
+/* this device's vectors before `vec` have given all their segments */
+static void complete_before (tablestate* t, int vec)
+	{
+	if (vec <= t->upTo) return;
+	for ( ; t->upTo<vec ; t->upTo++) t->chroms[t->mine[t->upTo]].done = true;
+	advance (t);
+	}
+
+static int take_segments (void* ctx, const gdsp_segment* segs, uint32_t count)
+	{
+	tablestate* t = (tablestate*) ctx;
+	const dspop_segments* op = t->op;
+	const char* name = op->common.name;
+	const u32   o = op->originOne? 1 : 0;
+	size_t len = 0;
+	int    held = -1;                                         /* the chromosome the lines in t->text belong to */
+	for (uint32_t k=0 ; k<=count ; k++)
+		{
+		const int ci = (k < count)? t->mine[segs[k].vec] : -1;
+		if ((len != 0) && ((ci != held) || (len + 2400 > t->textCap)))
+			{
+			chromtext* c = &t->chroms[held];
+			if (held == t->next) fwrite (t->text, 1, len, t->out);
+			else
+				{
+				if (c->len + len > c->cap)
+					{
+					c->cap  = 2 * (c->len + len) + 4096;
+					c->text = (char*) must (realloc (c->text, c->cap), name);
+					}
+				memcpy (c->text + c->len, t->text, len);  c->len += len;
+				}
+			len = 0;
+			}
+		if (k == count) break;
+		complete_before (t, (int) segs[k].vec);
+		held = ci;
+		const gdsp_segment*       g = &segs[k];
+		const gdsp_interval_stat* r = &g->stat;
+		spec* s = t->chroms[ci].s;
+		t->kept++;  t->covered += g->end - g->start;
+		if (g->end - g->start > t->longest) t->longest = g->end - g->start;
+		if (op->quiet) continue;
+		const size_t chromLen = strlen (s->chrom);
+		if (chromLen + 2400 > t->textCap)
+			{
+			t->textCap = (1u << 20) + chromLen + 2400;
+			t->text = (char*) must (realloc (t->text, t->textCap), name);
+			}
+		char* p = t->text + len;
+		memcpy (p, s->chrom, chromLen);  p += chromLen;  *(p++) = '\t';
+		p = put_unsigned (p, (unsigned long long) s->start + g->start + o);  *(p++) = '\t';
+		p = put_unsigned (p, (unsigned long long) s->start + g->end);        *(p++) = '\t';
+		p = put_unsigned (p, r->count);      *(p++) = '\t';
+		p = put_value (p, r->sum, op->precision);
+		if (r->count == 0) { memcpy (p, "\tNA\tNA\tNA\tNA\n", 13);  p += 13; }
+		else
+			{
+			*(p++) = '\t';  p = put_value (p, r->mean, op->precision);
+			*(p++) = '\t';  p = put_value (p, r->min,  op->precision);
+			*(p++) = '\t';  p = put_value (p, r->max,  op->precision);
+			*(p++) = '\t';  p = put_unsigned (p, (unsigned long long) s->start + r->maxpos + o);
+			*(p++) = '\n';
+			}
+		len = (size_t) (p - t->text);
+		}
+	return 0;
+	}
+
+void op_segments_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
+	{
+	dspop_segments* op = (dspop_segments*) _op;
+	char* name = _op->name;
+	resolve_variable (_op, &op->thresholdVarName, &op->threshold, "threshold");
+	if (op->haveMinHeight) resolve_variable (_op, &op->minHeightVarName, &op->minHeight, "minimum height");
+	if (op->threshold != op->threshold) { fprintf (stderr, "[%s] the threshold is not a number\n", name);  exit (EXIT_FAILURE); }
+	if (op->haveMinHeight && (op->minHeight != op->minHeight)) { fprintf (stderr, "[%s] the minimum height is not a number\n", name);  exit (EXIT_FAILURE); }
+
+	tablestate t;
+	memset (&t, 0, sizeof(t));
+	t.op = op;
+	for (spec* s=chromsOfInterest ; s!=NULL ; s=s->next) t.numChroms++;
+	t.chroms = (chromtext*) must (calloc (t.numChroms + 1, sizeof(chromtext)), name);
+	t.mine   = (int*) must (calloc (t.numChroms + 1, sizeof(int)), name);
+	gdsp_batch_item* items = (gdsp_batch_item*) must (calloc (t.numChroms + 1, sizeof(gdsp_batch_item)), name);
+		{
+		int ci = 0;
+		for (spec* s=chromsOfInterest ; s!=NULL ; s=s->next) t.chroms[ci++].s = s;
+		}
+	t.out = op->quiet? NULL : open_table (name, op->outFilename);
+
+	sync_all_devices ();
+	for (int d=0 ; d<device_count_in_use () ; d++)            /* one launch sequence per device, its chromosomes in file order */
+		{
+		t.numMine = 0;  t.upTo = 0;
+		for (int ci=0 ; ci<t.numChroms ; ci++)
+			{
+			spec* s = t.chroms[ci].s;
+			if (device_index_of (s) != d) continue;
+			if (trackOperations) fprintf (stderr, "%s(%s)\n", name, s->chrom);
+			items[t.numMine].d_in = s->valVector;  items[t.numMine].d_out = NULL;  items[t.numMine].n = s->length;
+			t.mine[t.numMine++] = ci;
+			}
+		if (t.numMine == 0) continue;
+		select_device_of (t.chroms[t.mine[0]].s);
+		check_gdsp (gdsp_segments_batch (items, t.numMine, op->threshold, op->tiesAbove, op->mergeGap, op->minLength,
+		                                 op->haveMinHeight, op->minHeight, take_segments, &t, op_stream ()), name);
+		if (t.out != NULL) complete_before (&t, t.numMine);
+		}
+	select_device_of (chromsSorted[0]);
+	if (t.out != NULL) close_table (t.out);
+
+	set_named_global ("segments", (valtype) t.kept);
+	set_named_global ("covered",  (valtype) t.covered);
+	set_named_global ("longest",  (valtype) t.longest);
+	for (int ci=0 ; ci<t.numChroms ; ci++) free (t.chroms[ci].text);
+	free (t.chroms);  free (t.mine);  free (items);  free (t.text);
+	}
+
+/* the driver: what it needs to know */
+int op_segments_is (dspop* op) { return op->funcApply == op_segments_apply; }

@@ -514,6 +514,61 @@ int gdsp_interval_stats_combine (const gdsp_interval_piece* pieces, uint32_t npi
 void gdsp_interval_stats_last  (uint64_t out[4]);
 void gdsp_interval_stats_times (double ms[4]);
 
+/* ---- segments (not in the reference): the signal's own thresholded regions, each with statsover's figures, exact ------
+ * For a vector v of n doubles, a threshold T and tiesAbove:
+ *   member   base i is a member iff v[i] > T, or v[i] >= T with ties above: binarize's test.  A NaN is never a member
+ *            and splits a run; +inf (and -inf against T = -inf with ties above) is a member when the test says so.
+ *   run      a maximal stretch [s, e) of consecutive members.
+ *   segment  the runs of one vector, in position order, joined while next.s - prev.e <= mergeGap (0: nothing is joined);
+ *            it spans [first.s, last.e).  Its sample is statsover's sample restricted to its member bases: the finite
+ *            members.  The bases of the gaps are not sampled.
+ *   filters  applied after joining: a segment is dropped when end - start < minLength (1: none is), and, when a minimum
+ *            height is given, when its sample is empty or its max < minHeight.
+ *   figures  of a kept segment: count, sum and mean (exact, rounded once), min, max, maxpos (the lowest position of the
+ *            maximum) exactly as statsover defines them: a zero result is +0.0, and an empty sample (a segment of +inf
+ *            only) has sum +0.0, NaN for mean, min and max, and maxpos UINT32_MAX.
+ * The set of segments and every figure are functions of the signal and the five parameters alone: nothing depends on
+ * tiles, grid, dispatch order, how many records a launch may hold, devices or the order of the vectors.
+ *
+ * Device half, gdsp_run_pieces_batch: every vector of the table (d_in and n of an item are read; 8-byte aligned; on the
+ * current device) is cut at multiples of gdsp_segments_tile() values of the 16-byte aligned frame it lies in, and every
+ * maximal stretch of members inside a tile becomes one record: where it lies, and a gdsp_interval_piece for its sample
+ * (a0 + a1 is the exact sum unless `flag`).  Pieces of neighbouring tiles that touch are one run.  The records reach
+ * `emit` as HOST arrays in (vector, position) order, at most a bounded number per call -- 2^21, or what the environment
+ * variable GDSP_SEGMENTS_RECORDS says when that is less, down to the gdsp_segments_tile() / 2 a single tile can give --
+ * together with one GDSP_XSUM_WORDS image per flagged piece, in order (NULL when none is flagged).  The arrays are the
+ * library's and valid during the call; a nonzero return from `emit` ends the pass with GDSP_EINVAL.  The signal is only
+ * read.  Waits for the device.
+ *
+ * Host half, no GPU: a builder takes such records in (vector, position) order in any number of feeds, joins touching
+ * pieces and runs within mergeGap, carries the open segment from one feed to the next, applies the filters, and hands
+ * the kept segments to its callback in order (gdsp_interval_stats_combine gives the figures).  gdsp_segments_finish
+ * closes the open segment; the builder can then be fed again or destroyed.  Its memory does not grow with the length of
+ * a segment. */
+typedef struct gdsp_run_piece { uint32_t vec, start, end, reserved;  gdsp_interval_piece piece; } gdsp_run_piece;   /* [start, end) of items[vec] */
+typedef struct gdsp_segment   { uint32_t vec, start, end, reserved;  gdsp_interval_stat  stat;  } gdsp_segment;
+typedef int (*gdsp_run_pieces_fn) (void* ctx, const gdsp_run_piece* pieces, uint32_t count, const uint64_t* images);
+typedef int (*gdsp_segments_fn)   (void* ctx, const gdsp_segment* segments, uint32_t count);
+typedef struct gdsp_segments_builder gdsp_segments_builder;
+uint32_t gdsp_segments_tile (void);
+int gdsp_run_pieces_batch (const gdsp_batch_item* items, int nitems, double T, int tiesAbove, gdsp_run_pieces_fn emit, void* ctx,
+                           void* stream);
+int gdsp_segments_create  (gdsp_segments_builder** builder, uint32_t mergeGap, uint32_t minLength, int haveMinHeight,
+                           double minHeight, gdsp_segments_fn emit, void* ctx);
+int gdsp_segments_feed    (gdsp_segments_builder* builder, const gdsp_run_piece* pieces, uint32_t count, const uint64_t* images);
+int gdsp_segments_finish  (gdsp_segments_builder* builder);
+/* what the builder has seen so far: [0] runs, [1] pieces, [2] flagged pieces, [3] kept segments */
+void gdsp_segments_counts (const gdsp_segments_builder* builder, uint64_t out[4]);
+void gdsp_segments_destroy (gdsp_segments_builder* builder);
+/* end to end on the current device: the device half feeding a builder; waits for the pass */
+int gdsp_segments_batch (const gdsp_batch_item* items, int nitems, double T, int tiesAbove, uint32_t mergeGap, uint32_t minLength,
+                         int haveMinHeight, double minHeight, gdsp_segments_fn emit, void* ctx, void* stream);
+/* what the last gdsp_segments_batch did: [0] runs, [1] pieces, [2] flagged pieces (summed again), [3] kept segments; and
+ * where the last gdsp_run_pieces_batch spent its time, in ms: [0] the counting pass, [1] the piece kernel (HIP events),
+ * [2] copies, waiting and flagged pieces, [3] inside `emit` */
+void gdsp_segments_last  (uint64_t out[4]);
+void gdsp_segments_times (double ms[4]);
+
 /* ---- histogram (not in the reference): the genome-wide distribution of the values, exact, in one pass ---------------
  * The sample is stats': every window-th value counted from each chromosome's first base (a source carries `first`) whose
  * value v satisfies !(v < lo) && !(v > hi), finite values only (never NaN, never +-inf); n is its size.
