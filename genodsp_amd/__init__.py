@@ -1043,6 +1043,85 @@ def segments_last():
     return d
 
 
+# --------------------------------------------------- keepsegments (not in the reference) ----
+
+PAINT_SPAN = np.dtype([("vec", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32),
+                       ("value", np.float64)])                                                      # gdsp_paint_span
+KEEP_MODES = ("one", "value", "count", "length", "sum", "mean", "min", "max")                       # GDSP_KEEP_*
+
+
+def paint_tile():
+    """The tile the paint kernel cuts an output at (values of the 16-byte aligned frame it lies in)."""
+    return int(lib().gdsp_paint_tile())
+
+
+def _in_out_items(vecs, outs):
+    """vecs (None: nothing is read), outs: DeviceVectors or (vector, first, count) stretches, pairwise of equal length"""
+    items = _read_only_items(outs)
+    for k in range(len(outs)):
+        items[k].d_out, items[k].d_in = items[k].d_in, None
+    if vecs is not None:
+        assert len(vecs) == len(outs)
+        ins = _read_only_items(vecs)
+        for k in range(len(outs)):
+            assert ins[k].n == items[k].n
+            items[k].d_in = ins[k].d_in
+    return items
+
+
+def paint_spans(vecs, outs, spans, mode="figure", outside=0.0, start=(0, 0), stop=None, stream=None):
+    """Paint disjoint spans into the outputs (gdsp_paint_spans_batch).  spans: (vec, start, end, value) rows in
+    (vector, position) order, or an array of PAINT_SPAN.  Every base from `start` = (vector, position) up to `stop`
+    (None: the end of the last vector) is written once: the span's value inside a span -- with mode "value" the base of
+    vecs itself -- and `outside` elsewhere.  vecs may be None unless mode is "value".  -> dict: bases painted inside and
+    outside, ms in the launches and around them.  Waits."""
+    outs = outs if isinstance(outs, list) else [outs]
+    vecs = vecs if (vecs is None or isinstance(vecs, list)) else [vecs]
+    assert mode in ("figure", "value")
+    items = _in_out_items(vecs, outs)
+    if isinstance(spans, np.ndarray) and spans.dtype == PAINT_SPAN:
+        rec = np.ascontiguousarray(spans)
+    else:
+        rec = np.zeros(len(spans), PAINT_SPAN)
+        for k, (v, s, e, x) in enumerate(spans):
+            rec[k] = (v, s, e, 0, x)
+    stop = (len(outs), 0) if stop is None else stop
+    call("gdsp_paint_spans_batch", items, len(outs), rec.ctypes.data_as(C.c_void_p), rec.size, 1 if mode == "value" else 0,
+         float(outside), int(start[0]), int(start[1]), int(stop[0]), int(stop[1]), _sp(stream))
+    painted, ms = (C.c_uint64 * 2)(), (C.c_double * 2)()
+    lib().gdsp_paint_spans_last(painted, ms)
+    return {"inside": int(painted[0]), "outside": int(painted[1]), "ms_paint": float(ms[0]), "ms_around": float(ms[1])}
+
+
+def keep_segments(vecs, outs, T, ties_above=False, merge_gap=0, min_length=1, min_height=None, as_="one", one=1.0, zero=0.0,
+                  stream=None):
+    """The kept segments of segments(vecs, T, ...) written into outs (gdsp_keep_segments_batch): `zero` outside every
+    kept segment; inside one -- its whole span, joined gaps included -- by as_: `one`, the signal's own "value", or the
+    segment's "count", "length", "sum", "mean", "min" or "max".  outs are other buffers than vecs, which are only read.
+    -> the dict of arrays segments() returns.  Waits."""
+    vecs = vecs if isinstance(vecs, list) else [vecs]
+    outs = outs if isinstance(outs, list) else [outs]
+    items = _in_out_items(vecs, outs)
+    out, failure = [], []
+    cb = _segment_collector(out, failure)
+    with _hook_failure_first(failure):
+        call("gdsp_keep_segments_batch", items, len(vecs), float(T), 1 if ties_above else 0, int(merge_gap), int(min_length),
+             0 if min_height is None else 1, 0.0 if min_height is None else float(min_height), KEEP_MODES.index(as_),
+             float(one), float(zero), cb, None, _sp(stream))
+    return _segment_arrays(out)
+
+
+def keep_segments_last():
+    """What the last keep_segments did: segments_last's counts, the bases painted inside and outside kept segments, and
+    ms spent in the paint launches and around them."""
+    out, ms = (C.c_uint64 * 6)(), (C.c_double * 2)()
+    lib().gdsp_keep_segments_last(out)
+    lib().gdsp_keep_segments_times(ms)
+    d = dict(zip(("runs", "pieces", "flagged", "kept", "inside", "outside"), [int(x) for x in out]))
+    d.update(zip(("ms_paint", "ms_around"), [float(x) for x in ms]))
+    return d
+
+
 def _each(name, vecs, *params, stream=None):
     if isinstance(vecs, DeviceVector):
         call(name, vecs.ptr, vecs.n, *params, _sp(stream))

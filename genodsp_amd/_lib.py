@@ -183,6 +183,13 @@ SIGNATURES = {
     "gdsp_segments_batch": (_int, [_vp, _int, _f64, _int, _u32, _u32, _int, _f64, _vp, _vp, _vp]),
     "gdsp_segments_last": (None, [_vp]),
     "gdsp_segments_times": (None, [_vp]),
+    # keepsegments (not in the reference)
+    "gdsp_paint_tile": (_u32, []),
+    "gdsp_paint_spans_batch": (_int, [_vp, _int, _vp, _u32, _int, _f64, _u32, _u32, _u32, _u32, _vp]),
+    "gdsp_paint_spans_last": (None, [_vp, _vp]),
+    "gdsp_keep_segments_batch": (_int, [_vp, _int, _f64, _int, _u32, _u32, _int, _f64, _int, _f64, _f64, _vp, _vp, _vp]),
+    "gdsp_keep_segments_last": (None, [_vp]),
+    "gdsp_keep_segments_times": (None, [_vp]),
     # histogram (not in the reference)
     "gdsp_histogram_uniform_edges": (_int, [_f64, _f64, _u32, _vp]),
     "gdsp_histogram_init": (_int, [_vp, _u32, _vp]),

@@ -76,8 +76,9 @@ dspprototypes(op_correlate)
 dspprototypes(op_crosscorrelate)
 dspprototypes(op_autocorrelate)
 #endif
-#ifdef GDSP_SEGMENTS                                   /* not in the reference: ops_segments.c */
+#ifdef GDSP_SEGMENTS                                   /* not in the reference: ops_segments.c, ops_keepsegments.c */
 dspprototypes(op_segments)
+dspprototypes(op_keepsegments)
 #endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
@@ -152,6 +153,8 @@ static dspinfo dspTable[] =
 #ifdef GDSP_SEGMENTS                                   /* the signal's own regions above a threshold, quantified, after those */
 	 , dspinforecord("segments"    , op_segments)       , dspinfoalias ("callpeaks")      , dspinfoalias ("call_peaks")
 	 , dspinfoalias ("islands")
+	 , dspinforecord("keepsegments", op_keepsegments)   , dspinfoalias ("keep_segments")  , dspinfoalias ("hysteresis")
+	 , dspinfoalias ("paintsegments")
 #endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS
@@ -2202,6 +2205,7 @@ int main (int argc, char** argv)
 #endif
 #ifdef GDSP_SEGMENTS
 					if (op_segments_is (stopOp)) bpb = 8;                    /* one read of the signal (and of the tiles that hold regions) */
+					if (op_keepsegments_is (stopOp)) bpb = op_keepsegments_copies (stopOp)? 24 : 16;   /* that read, a store per base, and the signal again inside the regions */
 #endif
 					wall_phase (stopOp, stopOp->name, now_ms () - t0, total, "bases", bpb);
 					}

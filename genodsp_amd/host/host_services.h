@@ -110,6 +110,28 @@ u64   op_statsover_bases  (dspop* op);       /* summed length of the intervals s
 int   op_histogram_is_stop (dspop* op);      /* whole-genome, on the signal's parts as they are; the signal is only read */
 /* ops_segments.c (segments; compiled in with -DGDSP_SEGMENTS) */
 int   op_segments_is      (dspop* op);       /* whole-genome, on whole chromosomes; the signal is only read */
+/* what segments and keepsegments (ops_keepsegments.c) share: the options that select the segments and shape their
+ * table, parsed in one place, and the pass itself.  take: true when `arg` was one of them; take_other: --debug, the
+ * complaint about an unknown option, the threshold as a bare number.  segments_run with `paint`: every chromosome's
+ * partner is painted from the kept segments (gdsp_keep_segments_batch) and becomes the signal; the table is written
+ * when wantTable (to o->outFilename, else stdout); the variables segments, covered and longest are set either way */
+typedef struct segments_opts
+	{
+	char*   thresholdVarName;  valtype threshold;  int haveThreshold, tiesAbove;           /* (as binarize) */
+	u32     mergeGap, minLength;
+	int     haveMinHeight;  char* minHeightVarName;  valtype minHeight;
+	char*   outFilename;
+	int     precision, originOne;
+	} segments_opts;
+typedef struct segments_paint { int mode;  valtype one, zero; } segments_paint;       /* mode: GDSP_KEEP_* */
+void  segments_opts_init       (segments_opts* o);
+int   segments_opts_take       (segments_opts* o, char* name, char* arg);
+void  segments_opts_take_other (segments_opts* o, char* name, char* arg);
+void  segments_opts_free       (segments_opts* o);
+void  segments_run             (dspop* op, segments_opts* o, int wantTable, const segments_paint* paint);
+/* ops_keepsegments.c (keepsegments; with -DGDSP_SEGMENTS too) */
+int   op_keepsegments_is  (dspop* op);       /* whole-genome, on whole chromosomes; rewrites them through their partners */
+int   op_keepsegments_copies (dspop* op);    /* --as=value: the signal is read a second time, inside the kept segments */
 int   ib_chromosomes      (void);
 u32   ib_pending_of       (int ci, spec** s, u32** start, u32** end, valtype** val);
 char* put_value_fixed     (char* p, valtype v, int precision);

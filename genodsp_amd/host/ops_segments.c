@@ -11,6 +11,9 @@
  * positions ascending; a chromosome whose turn has not come yet -- it lives on a device that is served before that of
  * an earlier chromosome -- waits as text (a single device never waits).
  *
+ * keepsegments (ops_keepsegments.c) selects its segments by the same options and writes them back into the signal: the
+ * options' parser (segments_opts_*) and the pass (segments_run) are here for both.
+ *
  * The driver's table rows and branches that name this operator are compiled only with -DGDSP_SEGMENTS
  * (genodsp_amd/host/Makefile); every call into the device library for it stays in this file. */
 #include <stdlib.h>
@@ -28,11 +31,8 @@ dspprototypes(op_segments)
 typedef struct dspop_segments
 	{
 	dspop   common;
-	char*   thresholdVarName;  valtype threshold;  int tiesAbove;           /* (as binarize) */
-	u32     mergeGap, minLength;
-	int     haveMinHeight;  char* minHeightVarName;  valtype minHeight;
-	char*   outFilename;
-	int     precision, originOne, quiet;
+	segments_opts o;                                               /* (shared with keepsegments: host_services.h) */
+	int     quiet;
 	} dspop_segments;
 
 OP_SHORT (op_segments, "print the regions above a threshold with their count, sum, mean, min, max and summit (not in genodsp)")
@@ -66,53 +66,78 @@ static u32 bases_arg (char* name, char* arg, char* argVal, const char* what)
 	return v;
 	}
 
+void segments_opts_init (segments_opts* o)
+	{
+	memset (o, 0, sizeof(*o));
+	o->minLength = 1;
+	o->precision = -1;
+	o->originOne = (int) get_named_global ("originOne", false);
+	}
+
+/* the options that select the segments and shape their table; true: `arg` was one of them */
+int segments_opts_take (segments_opts* o, char* name, char* arg)
+	{
+	char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
+	if (is_opt3 (arg, "threshold", "T"))                 /* a variable NAME only, as binarize */
+		{
+		if (o->haveThreshold) { fprintf (stderr, "[%s] threshold specified more than once (at \"%s\")\n", name, arg);  exit (EXIT_FAILURE); }
+		o->thresholdVarName = copy_string (argVal);
+		o->haveThreshold = true;
+		return true;
+		}
+	if ((strcmp (arg, "--ties:below") == 0) || (strcmp (arg, "--ties=below") == 0)) { o->tiesAbove = false;  return true; }
+	if ((strcmp (arg, "--ties:above") == 0) || (strcmp (arg, "--ties=above") == 0)) { o->tiesAbove = true;   return true; }
+	if (strcmp_prefix (arg, "--mergegap=") == 0)  { o->mergeGap  = bases_arg (name, arg, argVal, "--mergegap");   return true; }
+	if (strcmp_prefix (arg, "--minlength=") == 0) { o->minLength = bases_arg (name, arg, argVal, "--minlength");  return true; }
+	if (strcmp_prefix (arg, "--minheight=") == 0)
+		{
+		if (o->minHeightVarName != NULL) { free (o->minHeightVarName);  o->minHeightVarName = NULL; }
+		value_or_variable (argVal, &o->minHeight, &o->minHeightVarName);
+		o->haveMinHeight = true;
+		return true;
+		}
+	if (strcmp_prefix (arg, "--output=") == 0)
+		{ if (o->outFilename != NULL) free (o->outFilename);  o->outFilename = copy_string (argVal);  return true; }
+	if (strcmp_prefix (arg, "--precision=") == 0)
+		{
+		o->precision = string_to_int (argVal);
+		if (o->precision < 0) chastise ("[%s] precision can't be negative (\"%s\")\n", name, arg);
+		return true;
+		}
+	if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { o->originOne = true;   return true; }
+	if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { o->originOne = false;  return true; }
+	return false;
+	}
+
+/* what is left when the operator's own options have had their turn: --debug, an option nobody knows, the threshold */
+void segments_opts_take_other (segments_opts* o, char* name, char* arg)
+	{
+	if (strcmp (arg, "--debug") == 0) return;
+	if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
+	if (!o->haveThreshold) { o->threshold = string_to_valtype (arg);  o->haveThreshold = true;  return; }
+	valtype again;
+	if (try_string_to_valtype (arg, &again))
+		{ fprintf (stderr, "[%s] threshold specified more than once (at \"%s\")\n", name, arg);  exit (EXIT_FAILURE); }
+	chastise ("[%s] Can't understand \"%s\"\n", name, arg);
+	}
+
+void segments_opts_free (segments_opts* o)
+	{
+	if (o->thresholdVarName != NULL) free (o->thresholdVarName);
+	if (o->minHeightVarName != NULL) free (o->minHeightVarName);
+	if (o->outFilename      != NULL) free (o->outFilename);
+	}
+
 dspop* op_segments_parse (char* name, int argc, char** argv)
 	{
 	dspop_segments* op = (dspop_segments*) new_op (name, sizeof(dspop_segments), true);
-	int haveThreshold = false;
-	op->minLength = 1;
-	op->precision = -1;
-	op->originOne = (int) get_named_global ("originOne", false);
+	segments_opts_init (&op->o);
 	for ( ; argc > 0 ; argv++, argc--)
 		{
 		char* arg = argv[0];
-		char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
-		if (is_opt3 (arg, "threshold", "T"))                 /* a variable NAME only, as binarize */
-			{
-			if (haveThreshold) { fprintf (stderr, "[%s] threshold specified more than once (at \"%s\")\n", name, arg);  exit (EXIT_FAILURE); }
-			op->thresholdVarName = copy_string (argVal);
-			haveThreshold = true;
-			continue;
-			}
-		if ((strcmp (arg, "--ties:below") == 0) || (strcmp (arg, "--ties=below") == 0)) { op->tiesAbove = false;  continue; }
-		if ((strcmp (arg, "--ties:above") == 0) || (strcmp (arg, "--ties=above") == 0)) { op->tiesAbove = true;   continue; }
-		if (strcmp_prefix (arg, "--mergegap=") == 0)  { op->mergeGap  = bases_arg (name, arg, argVal, "--mergegap");   continue; }
-		if (strcmp_prefix (arg, "--minlength=") == 0) { op->minLength = bases_arg (name, arg, argVal, "--minlength");  continue; }
-		if (strcmp_prefix (arg, "--minheight=") == 0)
-			{
-			if (op->minHeightVarName != NULL) { free (op->minHeightVarName);  op->minHeightVarName = NULL; }
-			value_or_variable (argVal, &op->minHeight, &op->minHeightVarName);
-			op->haveMinHeight = true;
-			continue;
-			}
-		if (strcmp_prefix (arg, "--output=") == 0)
-			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
-		if (strcmp_prefix (arg, "--precision=") == 0)
-			{
-			op->precision = string_to_int (argVal);
-			if (op->precision < 0) chastise ("[%s] precision can't be negative (\"%s\")\n", name, arg);
-			continue;
-			}
-		if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { op->originOne = true;   continue; }
-		if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { op->originOne = false;  continue; }
+		if (segments_opts_take (&op->o, name, arg)) continue;
 		if ((strcmp (arg, "--quiet") == 0) || (strcmp (arg, "--silent") == 0)) { op->quiet = true;  continue; }
-		if (strcmp (arg, "--debug") == 0) continue;
-		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
-		if (!haveThreshold) { op->threshold = string_to_valtype (arg);  haveThreshold = true;  continue; }
-		valtype again;
-		if (try_string_to_valtype (arg, &again))
-			{ fprintf (stderr, "[%s] threshold specified more than once (at \"%s\")\n", name, arg);  exit (EXIT_FAILURE); }
-		chastise ("[%s] Can't understand \"%s\"\n", name, arg);
+		segments_opts_take_other (&op->o, name, arg);
 		}
 	return (dspop*) op;
 	}
@@ -120,9 +145,7 @@ dspop* op_segments_parse (char* name, int argc, char** argv)
 void op_segments_free (dspop* _op)
 	{
 	dspop_segments* op = (dspop_segments*) _op;
-	if (op->thresholdVarName != NULL) free (op->thresholdVarName);
-	if (op->minHeightVarName != NULL) free (op->minHeightVarName);
-	if (op->outFilename      != NULL) free (op->outFilename);
+	segments_opts_free (&op->o);
 	free (op);
 	}
 
@@ -132,7 +155,7 @@ typedef struct chromtext { spec* s;  int done;  char* text;  size_t len, cap; } 
 
 typedef struct tablestate
 	{
-	dspop_segments* op;
+	const segments_opts* op;  const char* name;
 	FILE*      out;
 	chromtext* chroms;  int numChroms, next;                  /* chroms[next] is the one whose lines go straight out */
 	int*       mine;    int numMine, upTo;                    /* this device's vectors as indices into chroms; those before upTo are complete */
@@ -170,8 +193,8 @@ static void complete_before (tablestate* t, int vec)
 static int take_segments (void* ctx, const gdsp_segment* segs, uint32_t count)
 	{
 	tablestate* t = (tablestate*) ctx;
-	const dspop_segments* op = t->op;
-	const char* name = op->common.name;
+	const segments_opts* op = t->op;
+	const char* name = t->name;
 	const u32   o = op->originOne? 1 : 0;
 	size_t len = 0;
 	int    held = -1;                                         /* the chromosome the lines in t->text belong to */
@@ -201,7 +224,7 @@ static int take_segments (void* ctx, const gdsp_segment* segs, uint32_t count)
 		spec* s = t->chroms[ci].s;
 		t->kept++;  t->covered += g->end - g->start;
 		if (g->end - g->start > t->longest) t->longest = g->end - g->start;
-		if (op->quiet) continue;
+		if (t->out == NULL) continue;                         /* (no table: the variables are still set) */
 		const size_t chromLen = strlen (s->chrom);
 		if (chromLen + 2400 > t->textCap)
 			{
@@ -228,9 +251,10 @@ static int take_segments (void* ctx, const gdsp_segment* segs, uint32_t count)
 	return 0;
 	}
 
-void op_segments_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
+/* the pass of `segments`, and of keepsegments when `paint` is given: then every chromosome's partner is painted from the
+ * kept segments and becomes the signal */
+void segments_run (dspop* _op, segments_opts* op, int wantTable, const segments_paint* paint)
 	{
-	dspop_segments* op = (dspop_segments*) _op;
 	char* name = _op->name;
 	resolve_variable (_op, &op->thresholdVarName, &op->threshold, "threshold");
 	if (op->haveMinHeight) resolve_variable (_op, &op->minHeightVarName, &op->minHeight, "minimum height");
@@ -239,7 +263,7 @@ void op_segments_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_com
 
 	tablestate t;
 	memset (&t, 0, sizeof(t));
-	t.op = op;
+	t.op = op;  t.name = name;
 	for (spec* s=chromsOfInterest ; s!=NULL ; s=s->next) t.numChroms++;
 	t.chroms = (chromtext*) must (calloc (t.numChroms + 1, sizeof(chromtext)), name);
 	t.mine   = (int*) must (calloc (t.numChroms + 1, sizeof(int)), name);
@@ -248,7 +272,7 @@ void op_segments_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_com
 		int ci = 0;
 		for (spec* s=chromsOfInterest ; s!=NULL ; s=s->next) t.chroms[ci++].s = s;
 		}
-	t.out = op->quiet? NULL : open_table (name, op->outFilename);
+	t.out = wantTable? open_table (name, op->outFilename) : NULL;
 
 	sync_all_devices ();
 	for (int d=0 ; d<device_count_in_use () ; d++)            /* one launch sequence per device, its chromosomes in file order */
@@ -259,13 +283,21 @@ void op_segments_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_com
 			spec* s = t.chroms[ci].s;
 			if (device_index_of (s) != d) continue;
 			if (trackOperations) fprintf (stderr, "%s(%s)\n", name, s->chrom);
-			items[t.numMine].d_in = s->valVector;  items[t.numMine].d_out = NULL;  items[t.numMine].n = s->length;
+			items[t.numMine].d_in = s->valVector;  items[t.numMine].d_out = (paint != NULL)? partner_of (s) : NULL;  items[t.numMine].n = s->length;
 			t.mine[t.numMine++] = ci;
 			}
 		if (t.numMine == 0) continue;
 		select_device_of (t.chroms[t.mine[0]].s);
-		check_gdsp (gdsp_segments_batch (items, t.numMine, op->threshold, op->tiesAbove, op->mergeGap, op->minLength,
-		                                 op->haveMinHeight, op->minHeight, take_segments, &t, op_stream ()), name);
+		if (paint == NULL)
+			check_gdsp (gdsp_segments_batch (items, t.numMine, op->threshold, op->tiesAbove, op->mergeGap, op->minLength,
+			                                 op->haveMinHeight, op->minHeight, take_segments, &t, op_stream ()), name);
+		else
+			{
+			check_gdsp (gdsp_keep_segments_batch (items, t.numMine, op->threshold, op->tiesAbove, op->mergeGap, op->minLength,
+			                                      op->haveMinHeight, op->minHeight, paint->mode, paint->one, paint->zero,
+			                                      take_segments, &t, op_stream ()), name);
+			for (int k=0 ; k<t.numMine ; k++) flip_vector (t.chroms[t.mine[k]].s->chrom);     /* what was painted is the signal now */
+			}
 		if (t.out != NULL) complete_before (&t, t.numMine);
 		}
 	select_device_of (chromsSorted[0]);
@@ -276,6 +308,12 @@ void op_segments_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_com
 	set_named_global ("longest",  (valtype) t.longest);
 	for (int ci=0 ; ci<t.numChroms ; ci++) free (t.chroms[ci].text);
 	free (t.chroms);  free (t.mine);  free (items);  free (t.text);
+	}
+
+void op_segments_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
+	{
+	dspop_segments* op = (dspop_segments*) _op;
+	segments_run (_op, &op->o, !op->quiet, NULL);
 	}
 
 /* the driver: what it needs to know */

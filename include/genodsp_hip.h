@@ -569,6 +569,52 @@ int gdsp_segments_batch (const gdsp_batch_item* items, int nitems, double T, int
 void gdsp_segments_last  (uint64_t out[4]);
 void gdsp_segments_times (double ms[4]);
 
+/* ---- keepsegments (not in the reference): the kept segments of `segments` written back into the signal ---------------
+ * For vectors v (d_in) and outputs w (d_out, another buffer: an output never overlaps its input), the selection
+ * parameters of `segments`, a mode and two values `one` and `zero`:
+ *   every base of w outside every kept segment becomes `zero`;
+ *   a kept segment is its whole span [start, end), the gap bases that mergeGap joined included (as after a `close`), and
+ *   every base of it becomes, by mode:
+ *     GDSP_KEEP_ONE     `one`;
+ *     GDSP_KEEP_VALUE   v's own base, bit for bit (a gap base keeps whatever it holds, a NaN and its payload included);
+ *     GDSP_KEEP_COUNT, _LENGTH, _SUM, _MEAN, _MIN, _MAX   that figure of the segment: the very double of its
+ *                       gdsp_interval_stat (count and end - start converted, both exact), so a segment with an empty
+ *                       sample writes NaN for mean, min and max and +0.0 for sum.
+ * `one` and `zero` are stored as given (a -0.0 stays -0.0).  Every base of every w is written exactly once; v is only
+ * read.  The result is a function of the signal and the parameters alone, as the segments are.
+ *
+ * Device half, gdsp_paint_spans_batch: `spans` is a HOST array of disjoint spans in (vector, position) order (start < end
+ * <= n of items[vec], a span may begin where the one before ends; anything else is GDSP_EINVAL).  Every base (vector,
+ * position) with (fromVec, fromPos) <= it < (toVec, toPos) -- (nitems, 0) is the end of the last vector -- is written
+ * once: a base inside a span gets the span's value, or with `copy` d_in's own base; any other base gets `outside`.  Spans
+ * or parts of spans outside that range are passed over, so a cursor or a limit may lie inside a span, and two calls that
+ * split the range anywhere write what one call writes.  Figure painting (copy == 0) reads nothing of d_in (it may be
+ * NULL).  Vectors are 8-byte aligned; the outputs are cut at multiples of gdsp_paint_tile() values of the 16-byte aligned
+ * frame each lies in; all vectors of the current device go into one launch per 32 of them, and at most 2^21 spans are
+ * staged at a time.  Waits for the device.
+ *
+ * End to end, gdsp_keep_segments_batch: gdsp_segments_batch's pass over d_in; each time kept segments arrive (a bounded
+ * number at a time, see GDSP_SEGMENTS_RECORDS) their spans are painted into d_out from where the last paint ended to the
+ * end of the last segment received, and the rest is painted after the pass: neither host nor device memory grows with
+ * the number of segments.  `emit` (may be NULL) then receives the same segments gdsp_segments_batch would hand it.  Waits. */
+enum { GDSP_KEEP_ONE = 0, GDSP_KEEP_VALUE = 1, GDSP_KEEP_COUNT = 2, GDSP_KEEP_LENGTH = 3, GDSP_KEEP_SUM = 4, GDSP_KEEP_MEAN = 5,
+       GDSP_KEEP_MIN = 6, GDSP_KEEP_MAX = 7 };
+typedef struct gdsp_paint_span { uint32_t vec, start, end, reserved;  double value; } gdsp_paint_span;   /* [start, end) of items[vec] */
+uint32_t gdsp_paint_tile (void);
+int gdsp_paint_spans_batch (const gdsp_batch_item* items, int nitems, const gdsp_paint_span* spans, uint32_t nspans, int copy,
+                            double outside, uint32_t fromVec, uint32_t fromPos, uint32_t toVec, uint32_t toPos, void* stream);
+/* what the last gdsp_paint_spans_batch did (either may be NULL): bases painted [0] inside spans, [1] outside; ms spent
+ * [0] in the paint launches (HIP events), [1] around them (the tiles' index, copies, waiting) */
+void gdsp_paint_spans_last (uint64_t painted[2], double ms[2]);
+int gdsp_keep_segments_batch (const gdsp_batch_item* items, int nitems, double T, int tiesAbove, uint32_t mergeGap, uint32_t minLength,
+                              int haveMinHeight, double minHeight, int mode, double one, double zero, gdsp_segments_fn emit, void* ctx,
+                              void* stream);
+/* what the last gdsp_keep_segments_batch did: [0] .. [3] as gdsp_segments_last, [4] bases painted inside kept segments,
+ * [5] bases painted outside; and the time of its paints as gdsp_paint_spans_last gives it, summed.  (gdsp_segments_last
+ * and gdsp_segments_times describe its pass.) */
+void gdsp_keep_segments_last  (uint64_t out[6]);
+void gdsp_keep_segments_times (double ms[2]);
+
 /* ---- histogram (not in the reference): the genome-wide distribution of the values, exact, in one pass ---------------
  * The sample is stats': every window-th value counted from each chromosome's first base (a source carries `first`) whose
  * value v satisfies !(v < lo) && !(v > hi), finite values only (never NaN, never +-inf); n is its size.
