@@ -281,6 +281,28 @@ def median(v, W, out=None, stream=None):
     return sliding_percentile(v, W, 50000, out=out, stream=stream)
 
 
+# ------------------------------------------------- prominence (not in the reference) ----
+
+PROMINENCE_MAX_WINDOW = 4095                  # GDSP_PROMINENCE_MAX_WINDOW
+PROMINENCE_WHAT = {"prominence": 0, "base": 1}    # GDSP_PROMINENCE_VALUE, GDSP_PROMINENCE_BASE
+
+
+def _prominence_what(as_):
+    if as_ not in PROMINENCE_WHAT:
+        raise ValueError("as_ must be 'prominence' or 'base', not %r" % (as_,))
+    return PROMINENCE_WHAT[as_]
+
+
+def prominence(v, W, as_="prominence", out=None, stream=None):
+    """out[i] = how far v[i] stands above the higher of the two lowest values met while walking left and right from i,
+    inside bestmax's window, up to the first strictly greater value (gdsp_prominence in include/genodsp_hip.h; for odd
+    W scipy.signal.peak_prominences with wlen=W at every base).  as_="base" writes that level instead."""
+    what = _prominence_what(as_)
+    out = out if out is not None else v.like()
+    call("gdsp_prominence", v.ptr, out.ptr, v.n, int(W), what, _sp(stream))
+    return out
+
+
 # ---------------------------------------------------------- morphology.c ----
 
 def split_length(length):
@@ -1394,6 +1416,10 @@ def best_extrema_batch(vecs, W, want_max, outs=None, stream=None):
 
 def sliding_percentile_batch(vecs, W, p_thousandths, outs=None, stream=None):
     return _batch("gdsp_sliding_percentile_batch", vecs, outs, int(W), int(p_thousandths), stream=stream)
+
+
+def prominence_batch(vecs, W, as_="prominence", outs=None, stream=None):
+    return _batch("gdsp_prominence_batch", vecs, outs, int(W), _prominence_what(as_), stream=stream)
 
 
 def dilate_batch(vecs, left, right, T=0.0, one=1.0, zero=0.0, outs=None, stream=None):

@@ -80,6 +80,9 @@ dspprototypes(op_autocorrelate)
 dspprototypes(op_segments)
 dspprototypes(op_keepsegments)
 #endif
+#ifdef GDSP_PROMINENCE                                 /* not in the reference: ops_prominence.c */
+dspprototypes(op_prominence)
+#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
@@ -155,6 +158,9 @@ static dspinfo dspTable[] =
 	 , dspinfoalias ("islands")
 	 , dspinforecord("keepsegments", op_keepsegments)   , dspinfoalias ("keep_segments")  , dspinfoalias ("hysteresis")
 	 , dspinfoalias ("paintsegments")
+#endif
+#ifdef GDSP_PROMINENCE                                 /* how far each base stands above its surroundings, after those */
+	 , dspinforecord("prominence"  , op_prominence)     , dspinfoalias ("peakprominence")
 #endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS

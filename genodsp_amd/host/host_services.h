@@ -96,6 +96,10 @@ u32   to_thousandths      (valtype pct);
 int   op_rankfilt_is      (dspop* op);
 u32   op_rankfilt_window  (dspop* op);
 int   op_rankfilt_batch   (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
+/* ops_prominence.c (prominence; compiled in with -DGDSP_PROMINENCE): likewise */
+int   op_prominence_is     (dspop* op);
+u32   op_prominence_window (dspop* op);
+int   op_prominence_batch  (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
 /* ops_stats.c (stats, normalize, multiplyconst, divideconst; compiled in with -DGDSP_GENOME_STATS) */
 int   op_const_is         (dspop* op);       /* multiplyconst / divideconst: per-base, in place */
 int   op_const_batch      (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);

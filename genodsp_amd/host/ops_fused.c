@@ -41,6 +41,10 @@ int op_reach (dspop* op, u32* left, u32* right)
 	if (op_rankfilt_is (op))                               /* bestmax's window: [i-wL, i+wR] */
 		{ u32 W = op_rankfilt_window (op);  *left = (W - 1) / 2;  *right = W - 1 - *left;  return true; }
 #endif
+#ifdef GDSP_PROMINENCE
+	if (op_prominence_is (op))                             /* the same window: neither walk leaves [i-wL, i+wR] */
+		{ u32 W = op_prominence_window (op);  *left = (W - 1) / 2;  *right = W - 1 - *left;  return true; }
+#endif
 	return false;                                          /* sum, slidingsum, cumulativesum, clump, anticlump, plugins */
 	}
 
@@ -90,6 +94,9 @@ int op_batchable (dspop* op)
 	opfunc_apply f = op->funcApply;
 #ifdef GDSP_RANK_FILTER
 	if (op_rankfilt_is (op)) return true;
+#endif
+#ifdef GDSP_PROMINENCE
+	if (op_prominence_is (op)) return true;
 #endif
 #ifdef GDSP_GENOME_STATS
 	if (op_const_is (op)) return true;
@@ -173,6 +180,10 @@ int batch_apply_on_device (dspop* op, dspop* stopOp, spec** units, int nunits, i
 #ifdef GDSP_RANK_FILTER
 	else if (op_rankfilt_is (op))
 		rc = op_rankfilt_batch (op, items, nunits, st);       /* (windows above the maximum were refused at parse time) */
+#endif
+#ifdef GDSP_PROMINENCE
+	else if (op_prominence_is (op))
+		rc = op_prominence_batch (op, items, nunits, st);     /* (likewise) */
 #endif
 	else
 		{

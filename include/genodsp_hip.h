@@ -218,6 +218,35 @@ uint32_t gdsp_sliding_percentile_tile (uint32_t W);
 int gdsp_sliding_percentile       (const double* d_in, double* d_out, uint32_t n, uint32_t W, uint32_t pThousandths, void* stream);
 int gdsp_sliding_percentile_batch (const gdsp_batch_item* items, int nitems, uint32_t W, uint32_t pThousandths, void* stream);
 
+/* ---- prominence (not in the reference): how far each base stands above its surroundings -------------------------
+ * Take a vector v of n values and a window W with 1 <= W <= GDSP_PROMINENCE_MAX_WINDOW.  Let wL = (W-1)/2 and
+ * wR = W-1-wL, which is bestmax's centring: for even W the extra base is on the right.
+ * For base i, with x = v[i] and plain IEEE comparisons on doubles:
+ *   Left walk:  j = i-1, i-2, ... while j >= max(0, i-wL) and not v[j] > x.
+ *   mL starts as x and is replaced by v[j] whenever v[j] < mL (strictly).
+ *   Right walk: the same over j = i+1 ... min(n-1, i+wR), giving mR.
+ *   base = mL if mL >= mR, else mR.
+ *   prominence = +0.0 if x == base, else x - base.  That is one rounded subtraction.
+ * So the result is never negative and never -0.0; no NaN arises from NaN-free input (inf - inf cannot happen because
+ * of the x == base rule); a base with a strictly higher neighbour gets 0; every base of a plateau gets the plateau's
+ * prominence; a base at a chromosome end gets 0, because the missing side contributes x.  For odd W this is the
+ * prominence with window length W of scipy.signal.peak_prominences, evaluated at every base.
+ * If the window [i-wL, i+wR] of a base contains a NaN, the result at that base is unspecified (some double); every
+ * other base gets the defined result.
+ * what: GDSP_PROMINENCE_VALUE writes prominence, GDSP_PROMINENCE_BASE writes base (an input value; the sign of a zero
+ * is whichever of the equal candidates was met).  Out-of-place; GDSP_EINVAL for d_in == d_out, W == 0, W above the
+ * maximum or an unknown `what`; n == 0 is a no-op.  One kernel launch covers every vector of a batch
+ * (gdsp_prominence.hip: per tile a max / min summary of every aligned block of 8, 64 and 512 staged positions in LDS;
+ * the bases without a higher neighbour walk outwards over single values, then blocks of 8, 64 and 512, and down again
+ * towards the end of the window: under 50 LDS reads per side whatever the data). */
+#define GDSP_PROMINENCE_MAX_WINDOW 4095
+#define GDSP_PROMINENCE_VALUE 0
+#define GDSP_PROMINENCE_BASE  1
+/* Host: outputs per workgroup tile of the kernel for window W (0 outside 1..the maximum); results never depend on it */
+uint32_t gdsp_prominence_tile  (uint32_t W);
+int gdsp_prominence       (const double* d_in, double* d_out, uint32_t n, uint32_t W, int what, void* stream);
+int gdsp_prominence_batch (const gdsp_batch_item* items, int nitems, uint32_t W, int what, void* stream);
+
 /* ---- logical.c, mask.c, add.c (in place) ---------------------------------------- */
 int gdsp_binarize     (double* d_v, uint32_t n, double T, int tiesAbove, double one, double zero,
                        void* stream);                                 /* logical.c:216-268 */
