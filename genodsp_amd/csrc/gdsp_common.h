@@ -70,6 +70,11 @@ static inline hipStream_t gdsp_stream (void* s) { return (hipStream_t) s; }
 
 __host__ __device__ static inline bool gdsp_aligned16 (const void* p) { return (((uintptr_t) p) & 15) == 0; }
 
+// the 16-byte aligned frame an 8-byte aligned vector p[0 .. n) lies in: `lead` values in front of p[0] (the one before a
+// vector that is not 16-byte aligned), and the tiles of `tile` values that cover lead + n of them
+__host__ __device__ __forceinline__ uint32_t gdsp_frame_lead (const void* p) { return gdsp_aligned16 (p)? 0 : 1; }
+__host__ __device__ __forceinline__ uint64_t gdsp_frame_tiles (uint64_t n, uint32_t lead, uint32_t tile) { return (n + lead + tile - 1) / tile; }
+
 // 16-byte accesses of data this kernel touches once: non-temporal, so the streams do not sweep the L2 for each other
 // (measured on hann_blocks_kernel<101>: 383 -> 400 Gbases/s with both; loads alone +2.5 %, stores alone +0 %).  Only for
 // accesses where the lanes of a wave cover whole lines between them: a lane that walks a strip of its own (the select

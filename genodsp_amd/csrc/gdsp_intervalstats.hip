@@ -18,22 +18,24 @@
 // integer image (gdsp_xsum_add_host) and gdsp_xsum_round / gdsp_xsum_div_round round it once.  A flagged piece (huge
 // cancelling values, residuals across hundreds of binades) is summed again by gdsp_xsum_accumulate_batch with that piece
 // as its one source: adversarial data stays exact and gets slower.
+//
+// The staging buffers, the timing events, that second sum and the arithmetic on pieces are gdsp_pieces.h's, shared with
+// segments and keepsegments.
 
 #include <float.h>
 #include <math.h>
 #include <string.h>
 #include <vector>
 #include <algorithm>
-#include <chrono>
 #include "gdsp_common.h"
 #include "gdsp_xsum_dev.h"
+#include "gdsp_pieces.h"
 
 #define IS_THREADS      256
 #define IS_WAVES        (IS_THREADS / 64)
 #define IS_TILE         4096                          // values: 32 KiB of LDS, five workgroups on a CU
 #define IS_ITEM_PIECES  64                            // pieces of one tile a workgroup takes
 #define IS_CHUNK_PIECES (1u << 22)                    // pieces of one launch (records: 192 MiB); one interval has at most 2^20 + 1
-#define IS_FLAG_BATCH   1024                          // flagged pieces summed again per read-back
 
 static_assert (sizeof(gdsp_interval_piece) == 48 && sizeof(gdsp_interval_stat) == 48, "the records of the header");
 static_assert (IS_TILE <= 65536 && IS_ITEM_PIECES <= 65535 && GDSP_BATCH_MAX <= 65535, "16-bit fields below");
@@ -141,45 +143,24 @@ void interval_stats_kernel (IsBatch B, const uint4* __restrict__ items, const ui
 // per device: staging and result buffers, grown on demand and kept
 struct IsBuffers
 	{
-	uint32_t *h_pieces, *d_pieces;  size_t capPieces;
-	IsItem   *h_items,  *d_items;   size_t capItems;
-	gdsp_interval_piece *h_out, *d_out;  size_t capOut;
-	uint64_t *h_img, *d_img;
+	GdspStaged<uint32_t> pieces;
+	GdspStaged<IsItem>   items;
+	GdspStaged<gdsp_interval_piece> out;
+	GdspStaged<uint64_t> img;
 	};
 static IsBuffers isBuffers[64];
 static uint64_t  isLast[4];
 static double    isTimes[4];
 
-static int is_grow (void** h, void** d, size_t* cap, size_t want, size_t elem)
-	{
-	if (want <= *cap) return GDSP_OK;
-	size_t n = (*cap == 0)? 65536 : *cap;
-	while (n < want) n *= 2;
-	if (*h != NULL) { (void) hipHostFree (*h);  *h = NULL; }
-	if (*d != NULL) { (void) hipFree (*d);  *d = NULL; }
-	*cap = 0;
-	if (hipHostMalloc (h, n * elem, hipHostMallocDefault) != hipSuccess) { *h = NULL;  gdsp_set_error ("gdsp_interval_stats: no pinned memory");  return GDSP_ENOMEM; }
-	if (hipMalloc (d, n * elem) != hipSuccess) { *d = NULL;  gdsp_set_error ("gdsp_interval_stats: no device memory");  return GDSP_ENOMEM; }
-	*cap = n;
-	return GDSP_OK;
-	}
-
-static inline double is_ms_since (std::chrono::steady_clock::time_point t0)
-	{ return std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now () - t0).count (); }
-
 struct IsVector { const double* v;  uint32_t n, lead, tile0; };      // tile0: its first tile in the launch's numbering
 
 // the intervals sel[0 .. nsel) (indices into the caller's arrays; all on the vectors vecs[0 .. nvec) of this launch,
 // vector `vecBase + k` of the caller being vecs[k]), at most IS_CHUNK_PIECES pieces or one interval
-static int is_launch (const IsVector* vecs, int nvec, int vecBase, uint32_t tiles, const uint32_t* sel, uint32_t nsel,
+static int is_launch (IsBuffers& W, const IsVector* vecs, int nvec, int vecBase, uint32_t tiles, const uint32_t* sel, uint32_t nsel,
                       const uint32_t* h_vec, const uint32_t* h_start, const uint32_t* h_end, double lo, double hi,
-                      gdsp_interval_stat* h_out, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+                      gdsp_interval_stat* h_out, int dev, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 	{
-	auto tBin = std::chrono::steady_clock::now ();
-	int dev = 0;
-	GDSP_HIP_TRY (hipGetDevice (&dev));
-	GDSP_REQUIRE ((dev >= 0) && (dev < 64), "device index beyond 63");
-	IsBuffers& W = isBuffers[dev];
+	const GdspTimer tBin;
 
 	// pieces per tile and per interval
 	std::vector<uint32_t> tileFirst ((size_t) tiles + 1, 0), ivFirst ((size_t) nsel + 1, 0);
@@ -205,9 +186,9 @@ static int is_launch (const IsVector* vecs, int nvec, int vecBase, uint32_t tile
 		nitems += (tileFirst[g+1] + IS_ITEM_PIECES - 1) / IS_ITEM_PIECES;
 		tileFirst[g+1] += tileFirst[g];
 		}
-	int rc = is_grow ((void**) &W.h_pieces, (void**) &W.d_pieces, &W.capPieces, P, sizeof(uint32_t));
-	if (rc == GDSP_OK) rc = is_grow ((void**) &W.h_items, (void**) &W.d_items, &W.capItems, nitems, sizeof(IsItem));
-	if (rc == GDSP_OK) rc = is_grow ((void**) &W.h_out, (void**) &W.d_out, &W.capOut, P, sizeof(gdsp_interval_piece));
+	int rc = W.pieces.grow (P, "gdsp_interval_stats");
+	if (rc == GDSP_OK) rc = W.items.grow (nitems, "gdsp_interval_stats");
+	if (rc == GDSP_OK) rc = W.out.grow (P, "gdsp_interval_stats");
 	if (rc != GDSP_OK) return rc;
 
 	// the items of every tile that has pieces, their hulls still empty
@@ -220,7 +201,7 @@ static int is_launch (const IsVector* vecs, int nvec, int vecBase, uint32_t tile
 			while ((v+1 < nvec) && (vecs[v+1].tile0 <= g)) v++;
 			for (uint32_t k=0 ; k<c ; k+=IS_ITEM_PIECES)
 				{
-				IsItem& it = W.h_items[itemBase[g] + k / IS_ITEM_PIECES];
+				IsItem& it = W.items.h[itemBase[g] + k / IS_ITEM_PIECES];
 				it.first = tileFirst[g] + k;  it.tile = g - vecs[v].tile0;
 				it.count = (uint16_t) std::min<uint32_t> (c - k, IS_ITEM_PIECES);  it.vec = (uint16_t) v;
 				it.h0 = 0xFFFF;  it.h1m1 = 0;
@@ -240,78 +221,58 @@ static int is_launch (const IsVector* vecs, int nvec, int vecBase, uint32_t tile
 			const uint64_t t0 = (uint64_t) t * IS_TILE;
 			const uint32_t a = (uint32_t) (std::max (fs, t0) - t0), b = (uint32_t) (std::min (fe, t0 + IS_TILE) - t0);
 			const uint32_t pos = cursor[g]++;
-			W.h_pieces[pos] = a | ((b - 1) << 16);
+			W.pieces.h[pos] = a | ((b - 1) << 16);
 			ivPiece[ivFirst[j] + (t - ts)] = pos;
-			IsItem& it = W.h_items[itemBase[g] + (pos - tileFirst[g]) / IS_ITEM_PIECES];
+			IsItem& it = W.items.h[itemBase[g] + (pos - tileFirst[g]) / IS_ITEM_PIECES];
 			it.h0   = (uint16_t) std::min<uint32_t> (it.h0, a);
 			it.h1m1 = (uint16_t) std::max<uint32_t> (it.h1m1, b - 1);
 			}
 		}
-	isTimes[0] += is_ms_since (tBin);
+	isTimes[0] += tBin.ms ();
 
-	auto tDev = std::chrono::steady_clock::now ();
+	const GdspTimer tDev;
 	IsBatch B;
 	for (int k=0 ; k<GDSP_BATCH_MAX ; k++)
 		{
 		B.base[k] = (k < nvec)? vecs[k].v - vecs[k].lead : NULL;
 		B.lead[k] = (k < nvec)? vecs[k].lead : 0;
 		}
-	GDSP_HIP_TRY (hipMemcpyAsync (W.d_pieces, W.h_pieces, (size_t) P * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (W.d_items, W.h_items, (size_t) nitems * sizeof(IsItem), hipMemcpyHostToDevice, s));
+	GDSP_HIP_TRY (hipMemcpyAsync (W.pieces.d, W.pieces.h, (size_t) P * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+	GDSP_HIP_TRY (hipMemcpyAsync (W.items.d, W.items.h, (size_t) nitems * sizeof(IsItem), hipMemcpyHostToDevice, s));
 	GDSP_HIP_TRY (hipEventRecord (ev0, s));
-	hipLaunchKernelGGL (interval_stats_kernel, dim3(nitems), dim3(IS_THREADS), 0, s, B, reinterpret_cast<const uint4*> (W.d_items),
-	                    W.d_pieces, lo, hi, W.d_out);
+	hipLaunchKernelGGL (interval_stats_kernel, dim3(nitems), dim3(IS_THREADS), 0, s, B, reinterpret_cast<const uint4*> (W.items.d),
+	                    W.pieces.d, lo, hi, W.out.d);
 	GDSP_LAUNCH_CHECK ();
 	GDSP_HIP_TRY (hipEventRecord (ev1, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (W.h_out, W.d_out, (size_t) P * sizeof(gdsp_interval_piece), hipMemcpyDeviceToHost, s));
+	GDSP_HIP_TRY (hipMemcpyAsync (W.out.h, W.out.d, (size_t) P * sizeof(gdsp_interval_piece), hipMemcpyDeviceToHost, s));
 	GDSP_HIP_TRY (hipStreamSynchronize (s));
 	float kernelMs = 0;
 	GDSP_HIP_TRY (hipEventElapsedTime (&kernelMs, ev0, ev1));
 
 	// flagged pieces: each is summed again as the one source of an exact pass
 	std::vector<uint32_t> flagged;
-	for (uint32_t p=0 ; p<P ; p++) { if (W.h_out[p].flag != 0) flagged.push_back (p); }
-	std::vector<uint64_t> images (flagged.size () * GDSP_XSUM_WORDS);
-	if (!flagged.empty ())
+	std::vector<uint64_t> images;
+	auto stretchOf = [&] (uint32_t p)
 		{
-		if (W.h_img == NULL)
-			{
-			const size_t bytes = (size_t) IS_FLAG_BATCH * GDSP_XSUM_WORDS * sizeof(uint64_t);
-			if (hipHostMalloc ((void**) &W.h_img, bytes, hipHostMallocDefault) != hipSuccess) { W.h_img = NULL;  gdsp_set_error ("gdsp_interval_stats: no pinned memory");  return GDSP_ENOMEM; }
-			if (hipMalloc ((void**) &W.d_img, bytes) != hipSuccess) { W.d_img = NULL;  gdsp_set_error ("gdsp_interval_stats: no device memory");  return GDSP_ENOMEM; }
-			}
-		for (size_t f0=0 ; f0<flagged.size () ; f0+=IS_FLAG_BATCH)
-			{
-			const size_t m = std::min<size_t> (IS_FLAG_BATCH, flagged.size () - f0);
-			GDSP_HIP_TRY (hipMemsetAsync (W.d_img, 0, m * GDSP_XSUM_WORDS * sizeof(uint64_t), s));
-			for (size_t f=0 ; f<m ; f++)
-				{
-				const uint32_t p = flagged[f0 + f];
-				const uint32_t g = (uint32_t) (std::upper_bound (tileFirst.begin (), tileFirst.end (), p) - tileFirst.begin ()) - 1;
-				int v = 0;
-				while ((v+1 < nvec) && (vecs[v+1].tile0 <= g)) v++;
-				const uint32_t a = W.h_pieces[p] & 0xFFFF, b = (W.h_pieces[p] >> 16) + 1;
-				gdsp_xsum_source src;
-				src.d_v = B.base[v] + (uint64_t) (g - vecs[v].tile0) * IS_TILE + a;  src.n = b - a;  src.first = 0;
-				src.device = dev;  src.stream = (void*) s;
-				rc = gdsp_xsum_accumulate_batch (&src, 1, 1, lo, hi, W.d_img + f * GDSP_XSUM_WORDS, (void*) s);
-				if (rc != GDSP_OK) return rc;
-				}
-			GDSP_HIP_TRY (hipMemcpyAsync (W.h_img, W.d_img, m * GDSP_XSUM_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-			GDSP_HIP_TRY (hipStreamSynchronize (s));
-			memcpy (&images[f0 * GDSP_XSUM_WORDS], W.h_img, m * GDSP_XSUM_WORDS * sizeof(uint64_t));
-			}
-		}
+		const uint32_t g = (uint32_t) (std::upper_bound (tileFirst.begin (), tileFirst.end (), p) - tileFirst.begin ()) - 1;
+		int v = 0;
+		while ((v+1 < nvec) && (vecs[v+1].tile0 <= g)) v++;
+		const uint32_t a = W.pieces.h[p] & 0xFFFF, b = (W.pieces.h[p] >> 16) + 1;
+		return std::make_pair (B.base[v] + (uint64_t) (g - vecs[v].tile0) * IS_TILE + a, b - a);
+		};
+	rc = gdsp_flagged_images ("gdsp_interval_stats", P, [&] (uint32_t p) { return W.out.h[p].flag != 0; }, stretchOf, lo, hi,
+	                          W.img, dev, s, flagged, images);
+	if (rc != GDSP_OK) return rc;
 	isTimes[1] += kernelMs;
-	isTimes[2] += is_ms_since (tDev) - kernelMs;
+	isTimes[2] += tDev.ms () - kernelMs;
 
-	auto tCombine = std::chrono::steady_clock::now ();
+	const GdspTimer tCombine;
 	std::vector<gdsp_interval_piece> mine;
 	std::vector<uint64_t> mineImages;
 	for (uint32_t j=0 ; j<nsel ; j++)
 		{
 		const uint32_t np = ivFirst[j+1] - ivFirst[j];
-		const gdsp_interval_piece* pc = &W.h_out[ivPiece[ivFirst[j]]];
+		const gdsp_interval_piece* pc = &W.out.h[ivPiece[ivFirst[j]]];
 		const uint64_t* im = NULL;
 		if ((np > 1) || (pc->flag != 0))
 			{
@@ -319,8 +280,8 @@ static int is_launch (const IsVector* vecs, int nvec, int vecBase, uint32_t tile
 			for (uint32_t k=0 ; k<np ; k++)
 				{
 				const uint32_t p = ivPiece[ivFirst[j] + k];
-				mine.push_back (W.h_out[p]);
-				if (W.h_out[p].flag == 0) continue;
+				mine.push_back (W.out.h[p]);
+				if (W.out.h[p].flag == 0) continue;
 				const size_t f = (size_t) (std::lower_bound (flagged.begin (), flagged.end (), p) - flagged.begin ());
 				mineImages.insert (mineImages.end (), &images[f * GDSP_XSUM_WORDS], &images[(f+1) * GDSP_XSUM_WORDS]);
 				}
@@ -331,7 +292,7 @@ static int is_launch (const IsVector* vecs, int nvec, int vecBase, uint32_t tile
 		if (rc != GDSP_OK) return rc;
 		isLast[3] += h_out[sel[j]].image;
 		}
-	isTimes[3] += is_ms_since (tCombine);
+	isTimes[3] += tCombine.ms ();
 	isLast[0] += nsel;  isLast[1] += P;  isLast[2] += flagged.size ();
 	return GDSP_OK;
 	}
@@ -383,69 +344,31 @@ int gdsp_interval_stats_combine (const gdsp_interval_piece* pieces, uint32_t npi
 	{
 	GDSP_REQUIRE (out != NULL, "NULL result");
 	GDSP_REQUIRE ((npieces == 0) || (pieces != NULL), "NULL pieces");
-	uint64_t count = 0;
-	double   mn = HUGE_VAL, mx = -HUGE_VAL;
-	uint32_t pos = UINT32_MAX;
-	bool     anyFlag = false;
-	for (uint32_t k=0 ; k<npieces ; k++)
+	const GdspPiecesMerge m = gdsp_pieces_merge (pieces, npieces);
+	GDSP_REQUIRE (!m.anyFlag || (images != NULL), "a flagged piece without its image");
+	out->count = m.count;  out->image = 0;
+	if (m.count == 0) { out->sum = 0.0;  out->mean = out->min = out->max = NAN;  out->maxpos = UINT32_MAX;  return GDSP_OK; }
+	out->min = m.min + 0.0;  out->max = m.max + 0.0;  out->maxpos = m.maxpos;         // (-0.0 + 0.0 is +0.0)
+	double a[2];
+	if (!m.anyFlag && gdsp_pieces_two_terms (pieces, npieces, a))
 		{
-		const gdsp_interval_piece& p = pieces[k];
-		anyFlag |= (p.flag != 0);
-		if (p.count == 0) continue;
-		count += p.count;
-		if (p.min < mn) mn = p.min;
-		if ((p.max > mx) || ((p.max == mx) && (p.maxpos < pos))) { mx = p.max;  pos = p.maxpos; }
-		}
-	GDSP_REQUIRE (!anyFlag || (images != NULL), "a flagged piece without its image");
-	out->count = count;  out->image = 0;
-	if (count == 0) { out->sum = 0.0;  out->mean = out->min = out->max = NAN;  out->maxpos = UINT32_MAX;  return GDSP_OK; }
-	out->min = mn + 0.0;  out->max = mx + 0.0;  out->maxpos = pos;         // (-0.0 + 0.0 is +0.0)
-	if (!anyFlag)
-		{
-		// the pieces' terms into two terms with TwoSum; exact while every residual is zero (an overflow leaves a NaN)
-		double a[2] = { 0.0, 0.0 }, left = 0.0;
-		for (uint32_t k=0 ; (k<npieces) && (left == 0.0) ; k++)
+		const double s  = a[0] + a[1];
+		const double bp = s - a[0];
+		const double e  = (a[0] - (s - bp)) + (a[1] - bp);
+		// the exact sum is s + e and s is it rounded once; the mean is one IEEE division when e is zero, else a
+		// 128-bit one (is_mean_of_two) unless e lies too far below s for that
+		if (xs_finite (s) && ((e == 0.0) || is_mean_of_two (s, e, m.count, &out->mean)))
 			{
-			const double term[2] = { pieces[k].a0, pieces[k].a1 };
-			for (int j=0 ; (j<2) && (left == 0.0) ; j++)
-				{
-				double r = term[j];
-				for (int i=0 ; i<2 ; i++)
-					{
-					const double s  = a[i] + r;
-					const double bp = s - a[i];
-					r    = (a[i] - (s - bp)) + (r - bp);
-					a[i] = s;
-					}
-				left = r;
-				}
-			}
-		if (left == 0.0)
-			{
-			const double s  = a[0] + a[1];
-			const double bp = s - a[0];
-			const double e  = (a[0] - (s - bp)) + (a[1] - bp);
-			// the exact sum is s + e and s is it rounded once; the mean is one IEEE division when e is zero, else a
-			// 128-bit one (is_mean_of_two) unless e lies too far below s for that
-			if (xs_finite (s) && ((e == 0.0) || is_mean_of_two (s, e, count, &out->mean)))
-				{
-				out->sum = s + 0.0;
-				if (e == 0.0) out->mean = s / (double) count;
-				return GDSP_OK;
-				}
+			out->sum = s + 0.0;
+			if (e == 0.0) out->mean = s / (double) m.count;
+			return GDSP_OK;
 			}
 		}
 	uint64_t img[GDSP_XSUM_WORDS];
-	memset (img, 0, sizeof(img));
-	for (uint32_t k=0 ; k<npieces ; k++)
-		{
-		if (pieces[k].flag == 0) { gdsp_xsum_add_host (img, pieces[k].a0);  gdsp_xsum_add_host (img, pieces[k].a1);  continue; }
-		for (int w=0 ; w<GDSP_XSUM_DIGITS ; w++) img[w] += images[w];
-		images += GDSP_XSUM_WORDS;
-		}
+	gdsp_pieces_image (pieces, npieces, images, img);
 	img[GDSP_XSUM_WORD_INF] = 0;
 	out->sum  = gdsp_xsum_round (img);
-	out->mean = gdsp_xsum_div_round (img, count);
+	out->mean = gdsp_xsum_div_round (img, m.count);
 	out->image = 1;
 	return GDSP_OK;
 	}
@@ -469,10 +392,10 @@ int gdsp_interval_stats_batch (const gdsp_batch_item* items, int nitems, const u
 		GDSP_REQUIRE (h_end[i] <= items[v].n, "an interval ends beyond its vector");
 		}
 	hipStream_t s = gdsp_stream (stream);
-	hipEvent_t ev0, ev1;
-	GDSP_HIP_TRY (hipEventCreate (&ev0));
-	if (hipEventCreate (&ev1) != hipSuccess) { (void) hipEventDestroy (ev0);  gdsp_set_error ("gdsp_interval_stats: no event");  return GDSP_EHIP; }
-	int rc = GDSP_OK;
+	int dev = 0, rc = gdsp_device_slot (&dev);
+	if (rc != GDSP_OK) return rc;
+	GdspEventPair ev;
+	rc = ev.create ("gdsp_interval_stats");
 	std::vector<uint32_t> sel;
 	for (int v0=0 ; (v0<nitems) && (rc == GDSP_OK) ; v0+=GDSP_BATCH_MAX)         // a table of vectors at a time
 		{
@@ -482,9 +405,9 @@ int gdsp_interval_stats_batch (const gdsp_batch_item* items, int nitems, const u
 		for (int k=0 ; k<nvec ; k++)
 			{
 			vecs[k].v = items[v0+k].d_in;  vecs[k].n = items[v0+k].n;
-			vecs[k].lead  = ((items[v0+k].n != 0) && !gdsp_aligned16 (items[v0+k].d_in))? 1 : 0;
+			vecs[k].lead  = (items[v0+k].n != 0)? gdsp_frame_lead (items[v0+k].d_in) : 0;
 			vecs[k].tile0 = tiles;
-			tiles += (uint32_t) (((uint64_t) vecs[k].n + vecs[k].lead + IS_TILE - 1) / IS_TILE);
+			tiles += (uint32_t) gdsp_frame_tiles (vecs[k].n, vecs[k].lead, IS_TILE);
 			}
 		// the caller's order, cut where a launch is full
 		uint64_t pieces = 0;
@@ -501,13 +424,13 @@ int gdsp_interval_stats_batch (const gdsp_batch_item* items, int nitems, const u
 				}
 			if (!sel.empty () && ((i == count) || (pieces + mine > IS_CHUNK_PIECES)))
 				{
-				rc = is_launch (vecs, nvec, v0, tiles, sel.data (), (uint32_t) sel.size (), h_vec, h_start, h_end, lo, hi, h_out, s, ev0, ev1);
+				rc = is_launch (isBuffers[dev], vecs, nvec, v0, tiles, sel.data (), (uint32_t) sel.size (), h_vec, h_start, h_end, lo, hi,
+				                h_out, dev, s, ev.ev0, ev.ev1);
 				sel.clear ();  pieces = 0;
 				}
 			if (i < count) { sel.push_back (i);  pieces += mine; }
 			}
 		}
-	(void) hipEventDestroy (ev0);  (void) hipEventDestroy (ev1);
 	return rc;
 	}
 

@@ -18,14 +18,15 @@
 // wave read neighbouring records the tile has just read), or, in copy mode, from the input's own base.  Figure modes read
 // nothing of the signal: 8 B per base.
 // No workgroup reads what another wrote and there is no atomic on global memory.
+// The staging buffers, the per-device slot and the timing events are gdsp_pieces.h's, shared with statsover and segments.
 
 #include <stdlib.h>
 #include <string.h>
 #include <string>
 #include <vector>
 #include <algorithm>
-#include <chrono>
 #include "gdsp_common.h"
+#include "gdsp_pieces.h"
 
 #define PN_THREADS      256
 #define PN_PAIRS        8                             // 16-byte words a thread stores
@@ -146,27 +147,10 @@ void pn_paint_kernel (GdspBatch B, const uint2* __restrict__ index, const PnSpan
 
 // ---------------------------------------------------------------------------------------------- host ----
 // per device: staging and device buffers, grown on demand and kept
-struct PnBuffers { PnSpan *h_spans, *d_spans;  size_t capSpans;  uint2 *h_index, *d_index;  size_t capIndex; };
+struct PnBuffers { GdspStaged<PnSpan> spans;  GdspStaged<uint2> index; };
 static PnBuffers pnBuffers[64];
 static double    pnTimes[2];
 static uint64_t  pnPainted[2];
-
-static int pn_grow (void** h, void** d, size_t* cap, size_t want, size_t elem)
-	{
-	if (want <= *cap) return GDSP_OK;
-	size_t n = (*cap == 0)? 65536 : *cap;
-	while (n < want) n *= 2;
-	if (*h != NULL) { (void) hipHostFree (*h);  *h = NULL; }
-	if (*d != NULL) { (void) gdsp_free (*d);  *d = NULL; }
-	*cap = 0;
-	if (hipHostMalloc (h, n * elem, hipHostMallocDefault) != hipSuccess) { *h = NULL;  gdsp_set_error ("gdsp_paint_spans: no pinned memory");  return GDSP_ENOMEM; }
-	if (gdsp_malloc (d, n * elem) != GDSP_OK) { *d = NULL;  return GDSP_ENOMEM; }      // (poisoned under GDSP_POISON: nothing here is read before it is written)
-	*cap = n;
-	return GDSP_OK;
-	}
-
-static inline double pn_ms_since (std::chrono::steady_clock::time_point t0)
-	{ return std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now () - t0).count (); }
 
 struct PnPos { uint32_t vec, pos; };
 static inline bool pn_before (const PnPos& a, const PnPos& b) { return (a.vec < b.vec) || ((a.vec == b.vec) && (a.pos < b.pos)); }
@@ -179,8 +163,8 @@ struct PnPart { uint32_t vec, lo, hi;  size_t s0, s1; };
 static int pn_paint_range (PnBuffers& W, const gdsp_batch_item* items, int nitems, const gdsp_paint_span* spans, uint32_t nspans,
                            int copy, double outside, PnPos from, PnPos to, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 	{
-	auto tAll = std::chrono::steady_clock::now ();
-	int rc = pn_grow ((void**) &W.h_spans, (void**) &W.d_spans, &W.capSpans, std::max<size_t> (nspans, 1), sizeof(PnSpan));
+	const GdspTimer tAll;
+	int rc = W.spans.grow (std::max<size_t> (nspans, 1), "gdsp_paint_spans");
 	if (rc != GDSP_OK) return rc;
 
 	std::vector<PnPart> parts;
@@ -197,38 +181,37 @@ static int pn_paint_range (PnBuffers& W, const gdsp_batch_item* items, int nitem
 			{
 			const uint32_t a = std::max (spans[k].start, lo), e = std::min (spans[k].end, hi);
 			if (a >= e) { if (spans[k].start >= hi) break;  continue; }
-			W.h_spans[ns].start = a - lo;  W.h_spans[ns].end = e - lo;  W.h_spans[ns].value = spans[k].value;
+			W.spans.h[ns].start = a - lo;  W.spans.h[ns].end = e - lo;  W.spans.h[ns].value = spans[k].value;
 			ns++;  inside += e - a;
 			}
 		p.s1 = ns;
-		const uint32_t lead = gdsp_aligned16 (items[v].d_out + lo)? 0 : 1;
-		tiles += (size_t) (((uint64_t) (hi - lo) + lead + PN_TILE - 1) / PN_TILE);
+		tiles += (size_t) gdsp_frame_tiles (hi - lo, gdsp_frame_lead (items[v].d_out + lo), PN_TILE);
 		total += hi - lo;
 		parts.push_back (p);
 		}
 	if (parts.empty ()) return GDSP_OK;
-	rc = pn_grow ((void**) &W.h_index, (void**) &W.d_index, &W.capIndex, tiles, sizeof(uint2));
+	rc = W.index.grow (tiles, "gdsp_paint_spans");
 	if (rc != GDSP_OK) return rc;
 
 	// the tiles' spans: both ends only ever move forward
 	size_t g = 0;
 	for (const PnPart& p : parts)
 		{
-		const uint32_t lead = gdsp_aligned16 (items[p.vec].d_out + p.lo)? 0 : 1;
-		const uint64_t nt   = ((uint64_t) (p.hi - p.lo) + lead + PN_TILE - 1) / PN_TILE;
+		const uint32_t lead = gdsp_frame_lead (items[p.vec].d_out + p.lo);
+		const uint64_t nt   = gdsp_frame_tiles (p.hi - p.lo, lead, PN_TILE);
 		size_t jf = p.s0, je = p.s0;
 		for (uint64_t t=0 ; t<nt ; t++)
 			{
 			const int64_t ts = (int64_t) (t * PN_TILE) - lead, te = ts + PN_TILE;
-			while ((jf < p.s1) && ((int64_t) W.h_spans[jf].end <= ts)) jf++;
+			while ((jf < p.s1) && ((int64_t) W.spans.h[jf].end <= ts)) jf++;
 			if (je < jf) je = jf;
-			while ((je < p.s1) && ((int64_t) W.h_spans[je].start < te)) je++;
-			W.h_index[g++] = make_uint2 ((uint32_t) jf, (uint32_t) (je - jf));
+			while ((je < p.s1) && ((int64_t) W.spans.h[je].start < te)) je++;
+			W.index.h[g++] = make_uint2 ((uint32_t) jf, (uint32_t) (je - jf));
 			}
 		}
 
-	if (ns != 0) GDSP_HIP_TRY (hipMemcpyAsync (W.d_spans, W.h_spans, ns * sizeof(PnSpan), hipMemcpyHostToDevice, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (W.d_index, W.h_index, tiles * sizeof(uint2), hipMemcpyHostToDevice, s));
+	if (ns != 0) GDSP_HIP_TRY (hipMemcpyAsync (W.spans.d, W.spans.h, ns * sizeof(PnSpan), hipMemcpyHostToDevice, s));
+	GDSP_HIP_TRY (hipMemcpyAsync (W.index.d, W.index.h, tiles * sizeof(uint2), hipMemcpyHostToDevice, s));
 	GDSP_HIP_TRY (hipEventRecord (ev0, s));
 	size_t g0 = 0;
 	for (size_t q0=0 ; q0<parts.size () ; )                              // a table of vectors at a time
@@ -239,8 +222,7 @@ static int pn_paint_range (PnBuffers& W, const gdsp_batch_item* items, int nitem
 		for ( ; (q0<parts.size ()) && (nvec<GDSP_BATCH_MAX) ; q0++, nvec++)
 			{
 			const PnPart& p = parts[q0];
-			const uint32_t lead = gdsp_aligned16 (items[p.vec].d_out + p.lo)? 0 : 1;
-			const uint64_t tl   = (uint64_t) B.tile0[nvec] + ((uint64_t) (p.hi - p.lo) + lead + PN_TILE - 1) / PN_TILE;
+			const uint64_t tl = (uint64_t) B.tile0[nvec] + gdsp_frame_tiles (p.hi - p.lo, gdsp_frame_lead (items[p.vec].d_out + p.lo), PN_TILE);
 			if ((tl > 0x7FFFFFFFull) && (nvec > 0)) break;                   // grid limit: the rest goes into the next launch
 			B.in[nvec]  = copy? items[p.vec].d_in + p.lo : NULL;
 			B.out[nvec] = items[p.vec].d_out + p.lo;  B.n[nvec] = p.hi - p.lo;
@@ -249,8 +231,8 @@ static int pn_paint_range (PnBuffers& W, const gdsp_batch_item* items, int nitem
 		for (int j=nvec ; j<GDSP_BATCH_MAX ; j++) { B.in[j] = NULL;  B.out[j] = NULL;  B.n[j] = 0;  B.tile0[j+1] = B.tile0[nvec]; }
 		B.nvec = (uint32_t) nvec;
 		const uint32_t grid = B.tile0[nvec];
-		if (copy) hipLaunchKernelGGL ((pn_paint_kernel<true>),  dim3(grid), dim3(PN_THREADS), 0, s, B, W.d_index + g0, W.d_spans, outside);
-		else      hipLaunchKernelGGL ((pn_paint_kernel<false>), dim3(grid), dim3(PN_THREADS), 0, s, B, W.d_index + g0, W.d_spans, outside);
+		if (copy) hipLaunchKernelGGL ((pn_paint_kernel<true>),  dim3(grid), dim3(PN_THREADS), 0, s, B, W.index.d + g0, W.spans.d, outside);
+		else      hipLaunchKernelGGL ((pn_paint_kernel<false>), dim3(grid), dim3(PN_THREADS), 0, s, B, W.index.d + g0, W.spans.d, outside);
 		GDSP_LAUNCH_CHECK ();
 		g0 += grid;
 		}
@@ -259,7 +241,7 @@ static int pn_paint_range (PnBuffers& W, const gdsp_batch_item* items, int nitem
 	float kernelMs = 0;
 	GDSP_HIP_TRY (hipEventElapsedTime (&kernelMs, ev0, ev1));
 	pnTimes[0] += kernelMs;
-	pnTimes[1] += pn_ms_since (tAll) - kernelMs;
+	pnTimes[1] += tAll.ms () - kernelMs;
 	pnPainted[0] += inside;  pnPainted[1] += total - inside;
 	return GDSP_OK;
 	}
@@ -346,16 +328,13 @@ int gdsp_paint_spans_batch (const gdsp_batch_item* items, int nitems, const gdsp
 		              "the spans are not disjoint and in (vector, position) order");
 		}
 	if (!pn_before (from, to)) return GDSP_OK;
-	int dev = 0;
-	GDSP_HIP_TRY (hipGetDevice (&dev));
-	GDSP_REQUIRE ((dev >= 0) && (dev < 64), "device index beyond 63");
+	int dev = 0, rc = gdsp_device_slot (&dev);
+	if (rc != GDSP_OK) return rc;
 	hipStream_t s = gdsp_stream (stream);
-	hipEvent_t ev0, ev1;
-	GDSP_HIP_TRY (hipEventCreate (&ev0));
-	if (hipEventCreate (&ev1) != hipSuccess) { (void) hipEventDestroy (ev0);  gdsp_set_error ("gdsp_paint_spans_batch: no event");  return GDSP_EHIP; }
+	GdspEventPair ev;
+	rc = ev.create ("gdsp_paint_spans_batch");
 
 	// PN_CHUNK_SPANS spans at a time, each time up to the end of the last of them
-	int rc = GDSP_OK;
 	uint32_t a = 0;
 	while ((rc == GDSP_OK) && pn_before (from, to))
 		{
@@ -366,11 +345,10 @@ int gdsp_paint_spans_batch (const gdsp_batch_item* items, int nitems, const gdsp
 			const PnPos last = { spans[b-1].vec, spans[b-1].end };
 			if (pn_before (last, to)) upTo = last;
 			}
-		if (pn_before (from, upTo)) rc = pn_paint_range (pnBuffers[dev], items, nitems, spans + a, b - a, copy, outside, from, upTo, s, ev0, ev1);
+		if (pn_before (from, upTo)) rc = pn_paint_range (pnBuffers[dev], items, nitems, spans + a, b - a, copy, outside, from, upTo, s, ev.ev0, ev.ev1);
 		if (pn_before (from, upTo)) from = upTo;
 		a = b;
 		}
-	(void) hipEventDestroy (ev0);  (void) hipEventDestroy (ev1);
 	return rc;
 	}
 

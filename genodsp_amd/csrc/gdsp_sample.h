@@ -35,10 +35,10 @@ static inline int gdsp_sample_next (GdspSample& B, const gdsp_xsum_source* sourc
 		const gdsp_xsum_source& src = sources[*i];
 		if (src.n == 0) continue;
 		if (!((src.d_v != NULL) && ((((uintptr_t) src.d_v) & 7) == 0))) return -1;
-		const uint32_t lead  = gdsp_aligned16 (src.d_v)? 0 : 1;
+		const uint32_t lead  = gdsp_frame_lead (src.d_v);
 		const uint32_t phase = (uint32_t) ((window - src.first % window) % window);
 		if (phase >= src.n) continue;                                  // nothing of it is sampled
-		const uint64_t t = (uint64_t) B.tile0[k] + ((uint64_t) src.n + lead + tileValues - 1) / tileValues;
+		const uint64_t t = (uint64_t) B.tile0[k] + gdsp_frame_tiles (src.n, lead, tileValues);
 		if ((t > maxTiles) && (k > 0)) break;                          // the rest goes into the next launch
 		if (taken != NULL) taken[k] = *i;
 		B.base[k] = src.d_v - lead;  B.n[k] = src.n;  B.lead[k] = lead;  B.phase[k] = phase;

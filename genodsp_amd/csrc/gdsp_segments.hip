@@ -31,7 +31,8 @@
 // the pieces of a long segment as they come (into two TwoSum terms while that is exact, else into a 72-word integer
 // image: its memory does not grow with the segment), applies the filters and hands the kept segments on, their figures
 // from gdsp_interval_stats_combine.  A flagged piece is summed again by gdsp_xsum_accumulate_batch with that piece as its
-// one source, as statsover does: adversarial data stays exact and gets slower.
+// one source, as statsover does: adversarial data stays exact and gets slower.  That second sum, the arithmetic that folds
+// pieces, the staging buffers and the timing events are gdsp_pieces.h's, shared with statsover and keepsegments.
 
 #include <float.h>
 #include <math.h>
@@ -39,9 +40,9 @@
 #include <string.h>
 #include <vector>
 #include <algorithm>
-#include <chrono>
 #include "gdsp_common.h"
 #include "gdsp_xsum_dev.h"
+#include "gdsp_pieces.h"
 
 #define SG_THREADS      256
 #define SG_WAVES        (SG_THREADS / 64)
@@ -51,7 +52,6 @@
 #define SG_PAIRS        (SG_TILE / 2 / SG_THREADS)    // 16-byte words a thread stages
 #define SG_TILE_PIECES  (SG_TILE / 2)                 // what one tile can hold: an alternating signal
 #define SG_CHUNK_PIECES (1u << 21)                    // records of one launch (128 MiB)
-#define SG_FLAG_BATCH   1024                          // flagged pieces summed again per read-back
 #define SG_FOLD_PIECES  4096                          // pieces of an open segment the builder keeps before it folds them
 
 static_assert (sizeof(gdsp_run_piece) == 64 && sizeof(gdsp_segment) == 64, "the records of the header");
@@ -273,31 +273,14 @@ void sg_piece_kernel (SgTable B, const uint4* __restrict__ work, double T, int t
 // per device: staging and result buffers, grown on demand and kept
 struct SgBuffers
 	{
-	uint32_t *h_counts, *d_counts;  size_t capCounts;
-	uint4    *h_work,   *d_work;    size_t capWork;
-	gdsp_run_piece *h_rec, *d_rec;  size_t capRec;
-	uint64_t *h_img, *d_img;
+	GdspStaged<uint32_t> counts;
+	GdspStaged<uint4>    work;
+	GdspStaged<gdsp_run_piece> rec;
+	GdspStaged<uint64_t> img;
 	};
 static SgBuffers sgBuffers[64];
 static uint64_t  sgLast[4];
 static double    sgTimes[4];
-
-static int sg_grow (void** h, void** d, size_t* cap, size_t want, size_t elem)
-	{
-	if (want <= *cap) return GDSP_OK;
-	size_t n = (*cap == 0)? 65536 : *cap;
-	while (n < want) n *= 2;
-	if (*h != NULL) { (void) hipHostFree (*h);  *h = NULL; }
-	if (*d != NULL) { (void) gdsp_free (*d);  *d = NULL; }
-	*cap = 0;
-	if (hipHostMalloc (h, n * elem, hipHostMallocDefault) != hipSuccess) { *h = NULL;  gdsp_set_error ("gdsp_run_pieces: no pinned memory");  return GDSP_ENOMEM; }
-	if (gdsp_malloc (d, n * elem) != GDSP_OK) { *d = NULL;  return GDSP_ENOMEM; }      // (poisoned under GDSP_POISON: nothing here is read before it is written)
-	*cap = n;
-	return GDSP_OK;
-	}
-
-static inline double sg_ms_since (std::chrono::steady_clock::time_point t0)
-	{ return std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now () - t0).count (); }
 
 // records one launch may hold: SG_CHUNK_PIECES, or what GDSP_SEGMENTS_RECORDS says when that is less, never below what
 // one tile can give.  Read at every call, so a test can make every tile its own launch.
@@ -313,58 +296,35 @@ static uint32_t sg_record_bound (void)
 
 static int sg_feed_hook (void* ctx, const gdsp_run_piece* pieces, uint32_t count, const uint64_t* images);    // gdsp_segments_batch's consumer
 
-// the `nwork` tiles of W.h_work, `P` records in all: reduce, read back, sum the flagged pieces again, hand them on
+// the `nwork` tiles of W.work.h, `P` records in all: reduce, read back, sum the flagged pieces again, hand them on
 static int sg_launch (SgBuffers& W, const SgTable& B, const gdsp_batch_item* items, int vecBase, uint32_t nwork, uint32_t P,
                       double T, int tiesAbove, gdsp_run_pieces_fn emit, void* ctx, int dev, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 	{
-	auto tDev = std::chrono::steady_clock::now ();
-	int rc = sg_grow ((void**) &W.h_rec, (void**) &W.d_rec, &W.capRec, P, sizeof(gdsp_run_piece));
+	const GdspTimer tDev;
+	int rc = W.rec.grow (P, "gdsp_run_pieces");
 	if (rc != GDSP_OK) return rc;
-	GDSP_HIP_TRY (hipMemcpyAsync (W.d_work, W.h_work, (size_t) nwork * sizeof(uint4), hipMemcpyHostToDevice, s));
+	GDSP_HIP_TRY (hipMemcpyAsync (W.work.d, W.work.h, (size_t) nwork * sizeof(uint4), hipMemcpyHostToDevice, s));
 	GDSP_HIP_TRY (hipEventRecord (ev0, s));
-	hipLaunchKernelGGL (sg_piece_kernel, dim3(nwork), dim3(SG_THREADS), 0, s, B, W.d_work, T, tiesAbove, (uint32_t) vecBase, W.d_rec);
+	hipLaunchKernelGGL (sg_piece_kernel, dim3(nwork), dim3(SG_THREADS), 0, s, B, W.work.d, T, tiesAbove, (uint32_t) vecBase, W.rec.d);
 	GDSP_LAUNCH_CHECK ();
 	GDSP_HIP_TRY (hipEventRecord (ev1, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (W.h_rec, W.d_rec, (size_t) P * sizeof(gdsp_run_piece), hipMemcpyDeviceToHost, s));
+	GDSP_HIP_TRY (hipMemcpyAsync (W.rec.h, W.rec.d, (size_t) P * sizeof(gdsp_run_piece), hipMemcpyDeviceToHost, s));
 	GDSP_HIP_TRY (hipStreamSynchronize (s));
 	float kernelMs = 0;
 	GDSP_HIP_TRY (hipEventElapsedTime (&kernelMs, ev0, ev1));
 
 	std::vector<uint32_t> flagged;
-	for (uint32_t p=0 ; p<P ; p++) { if (W.h_rec[p].piece.flag != 0) flagged.push_back (p); }
-	std::vector<uint64_t> images (flagged.size () * GDSP_XSUM_WORDS);
-	if (!flagged.empty ())
-		{
-		if (W.h_img == NULL)
-			{
-			const size_t bytes = (size_t) SG_FLAG_BATCH * GDSP_XSUM_WORDS * sizeof(uint64_t);
-			if (hipHostMalloc ((void**) &W.h_img, bytes, hipHostMallocDefault) != hipSuccess) { W.h_img = NULL;  gdsp_set_error ("gdsp_run_pieces: no pinned memory");  return GDSP_ENOMEM; }
-			if (hipMalloc ((void**) &W.d_img, bytes) != hipSuccess) { W.d_img = NULL;  gdsp_set_error ("gdsp_run_pieces: no device memory");  return GDSP_ENOMEM; }
-			}
-		for (size_t f0=0 ; f0<flagged.size () ; f0+=SG_FLAG_BATCH)
-			{
-			const size_t m = std::min<size_t> (SG_FLAG_BATCH, flagged.size () - f0);
-			GDSP_HIP_TRY (hipMemsetAsync (W.d_img, 0, m * GDSP_XSUM_WORDS * sizeof(uint64_t), s));
-			for (size_t f=0 ; f<m ; f++)
-				{
-				const gdsp_run_piece& r = W.h_rec[flagged[f0 + f]];
-				gdsp_xsum_source src;
-				src.d_v = items[r.vec].d_in + r.start;  src.n = r.end - r.start;  src.first = 0;
-				src.device = dev;  src.stream = (void*) s;
-				rc = gdsp_xsum_accumulate_batch (&src, 1, 1, -DBL_MAX, DBL_MAX, W.d_img + f * GDSP_XSUM_WORDS, (void*) s);
-				if (rc != GDSP_OK) return rc;
-				}
-			GDSP_HIP_TRY (hipMemcpyAsync (W.h_img, W.d_img, m * GDSP_XSUM_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-			GDSP_HIP_TRY (hipStreamSynchronize (s));
-			memcpy (&images[f0 * GDSP_XSUM_WORDS], W.h_img, m * GDSP_XSUM_WORDS * sizeof(uint64_t));
-			}
-		}
+	std::vector<uint64_t> images;
+	auto stretchOf = [&] (uint32_t p) { const gdsp_run_piece& r = W.rec.h[p];  return std::make_pair (items[r.vec].d_in + r.start, r.end - r.start); };
+	rc = gdsp_flagged_images ("gdsp_run_pieces", P, [&] (uint32_t p) { return W.rec.h[p].piece.flag != 0; }, stretchOf, -DBL_MAX, DBL_MAX,
+	                          W.img, dev, s, flagged, images);
+	if (rc != GDSP_OK) return rc;
 	sgTimes[1] += kernelMs;
-	sgTimes[2] += sg_ms_since (tDev) - kernelMs;
+	sgTimes[2] += tDev.ms () - kernelMs;
 
-	auto tEmit = std::chrono::steady_clock::now ();
-	const int stop = emit (ctx, W.h_rec, P, images.empty ()? NULL : images.data ());
-	sgTimes[3] += sg_ms_since (tEmit);
+	const GdspTimer tEmit;
+	const int stop = emit (ctx, W.rec.h, P, images.empty ()? NULL : images.data ());
+	sgTimes[3] += tEmit.ms ();
 	if (stop != 0)
 		{
 		if (emit != sg_feed_hook) gdsp_set_error ("gdsp_run_pieces_batch: the consumer of the pieces failed");     // (the builder has said why)
@@ -389,50 +349,16 @@ struct gdsp_segments_builder
 // the open segment's pieces into one: two TwoSum terms while that is exact, else an image
 static void sg_fold (gdsp_segments_builder* b)
 	{
+	const GdspPiecesMerge m = gdsp_pieces_merge (b->pieces.data (), b->pieces.size ());
 	gdsp_interval_piece f;
 	memset (&f, 0, sizeof(f));
-	f.min = HUGE_VAL;  f.max = -HUGE_VAL;  f.maxpos = UINT32_MAX;
-	bool anyFlag = false;
-	for (const gdsp_interval_piece& p : b->pieces)
-		{
-		anyFlag |= (p.flag != 0);
-		if (p.count == 0) continue;
-		f.count += p.count;
-		if (p.min < f.min) f.min = p.min;
-		if ((p.max > f.max) || ((p.max == f.max) && (p.maxpos < f.maxpos))) { f.max = p.max;  f.maxpos = p.maxpos; }
-		}
-	double a[2] = { 0.0, 0.0 }, left = 0.0;
-	if (!anyFlag)
-		{
-		for (size_t k=0 ; (k<b->pieces.size ()) && (left == 0.0) ; k++)
-			{
-			const double term[2] = { b->pieces[k].a0, b->pieces[k].a1 };
-			for (int j=0 ; (j<2) && (left == 0.0) ; j++)
-				{
-				double r = term[j];
-				for (int i=0 ; i<2 ; i++)
-					{
-					const double s  = a[i] + r;
-					const double bp = s - a[i];
-					r    = (a[i] - (s - bp)) + (r - bp);
-					a[i] = s;
-					}
-				left = r;                                          // (an overflow leaves a NaN here)
-				}
-			}
-		}
-	if (!anyFlag && (left == 0.0)) { f.a0 = a[0];  f.a1 = a[1];  b->images.clear (); }
+	f.count = (uint32_t) m.count;  f.min = m.min;  f.max = m.max;  f.maxpos = m.maxpos;
+	double a[2];
+	if (!m.anyFlag && gdsp_pieces_two_terms (b->pieces.data (), b->pieces.size (), a)) { f.a0 = a[0];  f.a1 = a[1];  b->images.clear (); }
 	else
 		{
 		uint64_t img[GDSP_XSUM_WORDS];
-		memset (img, 0, sizeof(img));
-		const uint64_t* im = b->images.data ();
-		for (const gdsp_interval_piece& p : b->pieces)
-			{
-			if (p.flag == 0) { gdsp_xsum_add_host (img, p.a0);  gdsp_xsum_add_host (img, p.a1);  continue; }
-			for (int w=0 ; w<GDSP_XSUM_DIGITS ; w++) img[w] += im[w];
-			im += GDSP_XSUM_WORDS;
-			}
+		gdsp_pieces_image (b->pieces.data (), b->pieces.size (), b->images.data (), img);
 		for (int w=GDSP_XSUM_DIGITS ; w<GDSP_XSUM_WORDS ; w++) img[w] = 0;
 		f.flag = 1;
 		b->images.assign (img, img + GDSP_XSUM_WORDS);
@@ -543,79 +469,65 @@ int gdsp_run_pieces_batch (const gdsp_batch_item* items, int nitems, double T, i
 	GDSP_REQUIRE (items != NULL, "no vectors");
 	for (int k=0 ; k<nitems ; k++)
 		GDSP_REQUIRE ((items[k].n == 0) || ((items[k].d_in != NULL) && ((((uintptr_t) items[k].d_in) & 7) == 0)), "a vector must be 8-byte aligned");
-	int dev = 0;
-	GDSP_HIP_TRY (hipGetDevice (&dev));
-	GDSP_REQUIRE ((dev >= 0) && (dev < 64), "device index beyond 63");
+	int dev = 0, rc = gdsp_device_slot (&dev);
+	if (rc != GDSP_OK) return rc;
 	SgBuffers& W = sgBuffers[dev];
 	hipStream_t s = gdsp_stream (stream);
 	const uint32_t bound = sg_record_bound ();
-	hipEvent_t ev0, ev1;
-	GDSP_HIP_TRY (hipEventCreate (&ev0));
-	if (hipEventCreate (&ev1) != hipSuccess) { (void) hipEventDestroy (ev0);  gdsp_set_error ("gdsp_run_pieces_batch: no event");  return GDSP_EHIP; }
+	GdspEventPair ev;
+	rc = ev.create ("gdsp_run_pieces_batch");
+	if (rc != GDSP_OK) return rc;
 
-	auto body = [&] () -> int
+	for (int v0=0 ; v0<nitems ; v0+=GDSP_BATCH_MAX)                  // a table of vectors at a time
 		{
-		for (int v0=0 ; v0<nitems ; v0+=GDSP_BATCH_MAX)                  // a table of vectors at a time
+		const int nvec = std::min (GDSP_BATCH_MAX, nitems - v0);
+		GdspBatch C;
+		SgTable   B;
+		C.tile0[0] = 0;
+		for (int k=0 ; k<GDSP_BATCH_MAX ; k++)
 			{
-			const int nvec = std::min (GDSP_BATCH_MAX, nitems - v0);
-			GdspBatch C;
-			SgTable   B;
-			C.tile0[0] = 0;
-			for (int k=0 ; k<GDSP_BATCH_MAX ; k++)
-				{
-				const bool     have = (k < nvec) && (items[v0+k].n != 0);
-				const uint32_t lead = (have && !gdsp_aligned16 (items[v0+k].d_in))? 1 : 0;
-				C.in[k]  = have? items[v0+k].d_in : NULL;  C.out[k] = NULL;  C.n[k] = have? items[v0+k].n : 0;
-				B.in[k]  = C.in[k];  B.n[k] = C.n[k];
-				C.tile0[k+1] = C.tile0[k] + (uint32_t) (((uint64_t) C.n[k] + lead + SG_TILE - 1) / SG_TILE);
-				}
-			C.nvec = (uint32_t) nvec;
-			const uint32_t tiles = C.tile0[GDSP_BATCH_MAX];
-			if (tiles == 0) continue;
-
-			auto tCount = std::chrono::steady_clock::now ();
-			int rc = sg_grow ((void**) &W.h_counts, (void**) &W.d_counts, &W.capCounts, tiles, sizeof(uint32_t));
-			if (rc != GDSP_OK) return rc;
-			hipLaunchKernelGGL (sg_count_kernel, dim3(tiles), dim3(SG_THREADS), 0, s, C, T, tiesAbove, W.d_counts);
-			GDSP_LAUNCH_CHECK ();
-			GDSP_HIP_TRY (hipMemcpyAsync (W.h_counts, W.d_counts, (size_t) tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-			GDSP_HIP_TRY (hipStreamSynchronize (s));
-			sgTimes[0] += sg_ms_since (tCount);
-
-			// the tiles that have pieces, in order, cut where a launch is full
-			uint32_t nwork = 0, P = 0;
-			int v = 0;
-			for (uint32_t g=0 ; g<=tiles ; g++)
-				{
-				const uint32_t c = (g < tiles)? W.h_counts[g] : 0;
-				if ((g < tiles) && (c == 0)) continue;
-				GDSP_REQUIRE (c <= SG_TILE_PIECES, "a tile with more pieces than it can hold");
-				if ((nwork != 0) && ((g == tiles) || (P + c > bound)))
-					{
-					rc = sg_launch (W, B, items, v0, nwork, P, T, tiesAbove, emit, ctx, dev, s, ev0, ev1);
-					if (rc != GDSP_OK) return rc;
-					nwork = 0;  P = 0;
-					}
-				if (g == tiles) break;
-				while (C.tile0[v+1] <= g) v++;
-				rc = GDSP_OK;
-				if (nwork + 1 > W.capWork)
-					{
-					// (grown between launches only: what is pending moves to the new buffer)
-					std::vector<uint4> keep (W.h_work, W.h_work + nwork);
-					rc = sg_grow ((void**) &W.h_work, (void**) &W.d_work, &W.capWork, (size_t) nwork + 1, sizeof(uint4));
-					if (rc != GDSP_OK) return rc;
-					if (nwork != 0) memcpy (W.h_work, keep.data (), (size_t) nwork * sizeof(uint4));
-					}
-				W.h_work[nwork++] = make_uint4 (((uint32_t) v << 20) | (g - C.tile0[v]), P, c, 0);
-				P += c;
-				}
+			const bool     have = (k < nvec) && (items[v0+k].n != 0);
+			const uint32_t lead = have? gdsp_frame_lead (items[v0+k].d_in) : 0;
+			C.in[k]  = have? items[v0+k].d_in : NULL;  C.out[k] = NULL;  C.n[k] = have? items[v0+k].n : 0;
+			B.in[k]  = C.in[k];  B.n[k] = C.n[k];
+			C.tile0[k+1] = C.tile0[k] + (uint32_t) gdsp_frame_tiles (C.n[k], lead, SG_TILE);
 			}
-		return GDSP_OK;
-		};
-	const int rc = body ();
-	(void) hipEventDestroy (ev0);  (void) hipEventDestroy (ev1);
-	return rc;
+		C.nvec = (uint32_t) nvec;
+		const uint32_t tiles = C.tile0[GDSP_BATCH_MAX];
+		if (tiles == 0) continue;
+
+		const GdspTimer tCount;
+		rc = W.counts.grow (tiles, "gdsp_run_pieces");
+		if (rc != GDSP_OK) return rc;
+		hipLaunchKernelGGL (sg_count_kernel, dim3(tiles), dim3(SG_THREADS), 0, s, C, T, tiesAbove, W.counts.d);
+		GDSP_LAUNCH_CHECK ();
+		GDSP_HIP_TRY (hipMemcpyAsync (W.counts.h, W.counts.d, (size_t) tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+		GDSP_HIP_TRY (hipStreamSynchronize (s));
+		sgTimes[0] += tCount.ms ();
+
+		// the tiles that have pieces, in order, cut where a launch is full
+		uint32_t nwork = 0, P = 0;
+		int v = 0;
+		for (uint32_t g=0 ; g<=tiles ; g++)
+			{
+			const uint32_t c = (g < tiles)? W.counts.h[g] : 0;
+			if ((g < tiles) && (c == 0)) continue;
+			GDSP_REQUIRE (c <= SG_TILE_PIECES, "a tile with more pieces than it can hold");
+			if ((nwork != 0) && ((g == tiles) || (P + c > bound)))
+				{
+				rc = sg_launch (W, B, items, v0, nwork, P, T, tiesAbove, emit, ctx, dev, s, ev.ev0, ev.ev1);
+				if (rc != GDSP_OK) return rc;
+				nwork = 0;  P = 0;
+				}
+			if (g == tiles) break;
+			while (C.tile0[v+1] <= g) v++;
+			rc = W.work.grow ((size_t) nwork + 1, "gdsp_run_pieces", nwork, 1024);      // (between launches only: what is pending moves to the new buffer)
+			if (rc != GDSP_OK) return rc;
+			W.work.h[nwork++] = make_uint4 (((uint32_t) v << 20) | (g - C.tile0[v]), P, c, 0);
+			P += c;
+			}
+		}
+	return GDSP_OK;
 	}
 
 static int sg_feed_hook (void* ctx, const gdsp_run_piece* pieces, uint32_t count, const uint64_t* images)

@@ -765,7 +765,6 @@ static pthread_cond_t  allocCond = PTHREAD_COND_INITIALIZER;
 static int    allocThreaded  = false;                 /* a helper thread was started (and not yet joined) */
 static int    vectorsReady   = false, partnersReady = false, partnersPlanned = false;
 static double allocStartupMs = 0, allocVectorsMs = 0, allocPartnersMs = 0, allocWaitedMs = 0;
-static double now_ms (void);
 
 /* one arena on every device for `which` (0: the vectors, 1: the partners) of the whole chromosomes and of the stretches */
 static void make_arenas (int which)
@@ -1719,7 +1718,7 @@ static int    numPhases = 0;
 static span*  spans = NULL;
 static u32    numSpans = 0, capSpans = 0;
 
-static double now_ms (void)
+double now_ms (void)
 	{ struct timespec t;  clock_gettime (CLOCK_MONOTONIC, &t);  return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; }
 
 static int phase_for (dspop* op, int nops, const char* fixedLabel)

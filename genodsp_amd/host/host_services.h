@@ -38,9 +38,12 @@ void* long_window_workspace (size_t* bytes);   /* lazily allocated, for windows 
 int  device_count_in_use (void);
 int  device_index_of     (spec* s);
 int  physical_device_of  (spec* s);
+double now_ms (void);                          /* the monotonic clock, in milliseconds */
 
 /* ops_common.c: helpers shared by the operator files */
 void* new_op           (char* name, size_t bytes, int atRandom);   /* zeroed control record */
+void* must_alloc       (void* p, const char* name);                /* p, or the run ends with "out of memory" when it is NULL */
+int   origin_opt_take  (char* arg, int* originOne);                /* --origin=one|1|zero|0 */
 u32   window_arg       (char* name, char* arg, char* argVal, const char* what);
 /* "--x=<value|variable>": number now, or a named variable resolved at first apply */
 void  value_or_variable (char* argVal, valtype* val, char** varName);
@@ -63,6 +66,8 @@ void  close_table       (FILE* out);
  * at most 400 characters of it, by hand where that gives printf's characters (integers below 10^15, fixed point) */
 char* put_unsigned      (char* p, unsigned long long u);
 char* put_value         (char* p, valtype v, int precision);
+/* count, sum and then mean, min, max, summit or four NA, each behind a tab, and the newline: at most 1647 characters */
+char* put_interval_figures (char* p, const gdsp_interval_stat* stat, u32 chromStart, int originOne, int precision);
 
 /* ops_fused.c: run op (and the operators after it, up to stopOp) as one fused kernel when
  * the chain is one the device library fuses; returns how many operators were consumed (0 = none) */

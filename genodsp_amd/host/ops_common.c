@@ -16,6 +16,20 @@ void* new_op (char* name, size_t bytes, int atRandom)
 	return op;
 	}
 
+void* must_alloc (void* p, const char* name)
+	{
+	if (p == NULL) { fprintf (stderr, "[%s] out of memory\n", name);  exit (EXIT_FAILURE); }
+	return p;
+	}
+
+/* --origin=one|1|zero|0 of an operator with a coordinate convention of its own; true: `arg` was it */
+int origin_opt_take (char* arg, int* originOne)
+	{
+	if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { *originOne = true;   return true; }
+	if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { *originOne = false;  return true; }
+	return false;
+	}
+
 /* --window=<n> and friends: zero and negatives are errors, 1-2 are raised to 3 with a
  * warning (sum.c:121-132, minmax.c:1116-1126) */
 u32 window_arg (char* name, char* arg, char* argVal, const char* what)
@@ -178,4 +192,21 @@ char* put_value (char* p, valtype v, int precision)
 		return put_unsigned (p, (unsigned long long) fabs (v));
 		}
 	return p + clipped (format_value (p, 400, v, precision));
+	}
+
+/* the figures of an interval or segment behind the three leading columns of its line: tab, count, tab, sum, then mean,
+ * min, max and the summit (chromStart + maxpos, + 1 when originOne), or four NA when nothing was sampled; the line ends
+ * here.  At most 6 tabs and a newline, two integers of at most 20 digits and four values of at most 400 characters:
+ * 1647 characters, inside the 2200 / 2400 the callers reserve per line beyond the chromosome's name */
+char* put_interval_figures (char* p, const gdsp_interval_stat* stat, u32 chromStart, int originOne, int precision)
+	{
+	*(p++) = '\t';  p = put_unsigned (p, stat->count);
+	*(p++) = '\t';  p = put_value (p, stat->sum, precision);
+	if (stat->count == 0) { memcpy (p, "\tNA\tNA\tNA\tNA\n", 13);  return p + 13; }
+	*(p++) = '\t';  p = put_value (p, stat->mean, precision);
+	*(p++) = '\t';  p = put_value (p, stat->min,  precision);
+	*(p++) = '\t';  p = put_value (p, stat->max,  precision);
+	*(p++) = '\t';  p = put_unsigned (p, (unsigned long long) chromStart + stat->maxpos + (originOne? 1 : 0));
+	*(p++) = '\n';
+	return p;
 	}

@@ -82,8 +82,7 @@ dspop* op_correlate_parse (char* name, int argc, char** argv)
 			op->valColumn = col;
 			continue;
 			}
-		if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { op->originOne = true;   continue; }
-		if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { op->originOne = false;  continue; }
+		if (origin_opt_take (arg, &op->originOne)) continue;
 		if ((strcmp (arg, "--report:bash") == 0) || (strcmp (arg, "--bash") == 0)) { op->reportForBash = true;  continue; }
 		if (strcmp_prefix (arg, "--debug") == 0) continue;
 		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);

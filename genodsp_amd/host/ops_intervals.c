@@ -68,8 +68,7 @@ static dspop* fileop_parse (char* name, int argc, char** argv, int kind)
 			op->haveMaskVal = true;
 			continue;
 			}
-		if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { op->originOne = true;   continue; }
-		if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { op->originOne = false;  continue; }
+		if (origin_opt_take (arg, &op->originOne)) continue;
 		if (((kind == K_ADD) || (kind == K_SUBTRACT) || isWith) && (strcmp (arg, "--destroy") == 0)) { op->destroyFile = true;  continue; }
 		if ((kind == K_DIVIDE) && (strcmp_prefix (arg, "--infinity=") == 0)) { op->infinityVal = string_to_valtype (argVal);  continue; }
 		if (strcmp (arg, "--debug") == 0) continue;
@@ -275,8 +274,7 @@ dspop* op_input_parse (char* name, int argc, char** argv)       /* opio.c:88-205
 		if (strcmp (arg, "--overlap=sum") == 0) { op->overlapOp = ri_overlapSum;  continue; }
 		if ((strcmp (arg, "--overlap=minimum") == 0) || (strcmp (arg, "--overlap=min") == 0)) { op->overlapOp = ri_overlapMin;  continue; }
 		if ((strcmp (arg, "--overlap=maximum") == 0) || (strcmp (arg, "--overlap=max") == 0)) { op->overlapOp = ri_overlapMax;  continue; }
-		if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { op->originOne = true;   continue; }
-		if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { op->originOne = false;  continue; }
+		if (origin_opt_take (arg, &op->originOne)) continue;
 		if (strcmp (arg, "--destroy") == 0) { op->destroyFile = true;  continue; }
 		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
 		if (op->filename == NULL) { op->filename = copy_string (arg);  continue; }
@@ -342,8 +340,7 @@ dspop* op_output_parse (char* name, int argc, char** argv)      /* opio.c:320-43
 		if ((strcmp (arg, "--uncovered:show") == 0) || (strcmp (arg, "--show:uncovered") == 0)) { op->showUncovered = uncovered_show;  continue; }
 		if ((strcmp (arg, "--uncovered:NA") == 0) || (strcmp (arg, "--uncovered:mark") == 0)
 		 || (strcmp (arg, "--mark:uncovered") == 0) || (strcmp (arg, "--markgaps") == 0)) { op->showUncovered = uncovered_NA;  continue; }
-		if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { op->originOne = true;   continue; }
-		if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { op->originOne = false;  continue; }
+		if (origin_opt_take (arg, &op->originOne)) continue;
 		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
 		if (op->filename == NULL) { op->filename = copy_string (arg);  continue; }
 		chastise ("[%s] Can't understand \"%s\"\n", name, arg);

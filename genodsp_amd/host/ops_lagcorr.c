@@ -140,8 +140,7 @@ static dspop* lagcorr_parse (char* name, int argc, char** argv, int withFile)
 			op->valColumn = col;
 			continue;
 			}
-		if (withFile && ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0))) { op->originOne = true;   continue; }
-		if (withFile && ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0))) { op->originOne = false;  continue; }
+		if (withFile && origin_opt_take (arg, &op->originOne)) continue;
 		if (strcmp_prefix (arg, "--debug") == 0) continue;
 		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
 		if (withFile && (op->filename == NULL)) { op->filename = copy_string (arg);  continue; }

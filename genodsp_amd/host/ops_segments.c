@@ -104,9 +104,7 @@ int segments_opts_take (segments_opts* o, char* name, char* arg)
 		if (o->precision < 0) chastise ("[%s] precision can't be negative (\"%s\")\n", name, arg);
 		return true;
 		}
-	if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { o->originOne = true;   return true; }
-	if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { o->originOne = false;  return true; }
-	return false;
+	return origin_opt_take (arg, &o->originOne);
 	}
 
 /* what is left when the operator's own options have had their turn: --debug, an option nobody knows, the threshold */
@@ -163,12 +161,6 @@ typedef struct tablestate
 	u64        kept, covered, longest;
 	} tablestate;
 
-static void* must (void* p, const char* name)
-	{
-	if (p == NULL) { fprintf (stderr, "[%s] out of memory\n", name);  exit (EXIT_FAILURE); }
-	return p;
-	}
-
 /* every chromosome whose turn has come and that is complete leaves; so does what the next one has waiting */
 static void advance (tablestate* t)
 	{
@@ -210,7 +202,7 @@ static int take_segments (void* ctx, const gdsp_segment* segs, uint32_t count)
 				if (c->len + len > c->cap)
 					{
 					c->cap  = 2 * (c->len + len) + 4096;
-					c->text = (char*) must (realloc (c->text, c->cap), name);
+					c->text = (char*) must_alloc (realloc (c->text, c->cap), name);
 					}
 				memcpy (c->text + c->len, t->text, len);  c->len += len;
 				}
@@ -219,8 +211,7 @@ static int take_segments (void* ctx, const gdsp_segment* segs, uint32_t count)
 		if (k == count) break;
 		complete_before (t, (int) segs[k].vec);
 		held = ci;
-		const gdsp_segment*       g = &segs[k];
-		const gdsp_interval_stat* r = &g->stat;
+		const gdsp_segment* g = &segs[k];
 		spec* s = t->chroms[ci].s;
 		t->kept++;  t->covered += g->end - g->start;
 		if (g->end - g->start > t->longest) t->longest = g->end - g->start;
@@ -229,23 +220,13 @@ static int take_segments (void* ctx, const gdsp_segment* segs, uint32_t count)
 		if (chromLen + 2400 > t->textCap)
 			{
 			t->textCap = (1u << 20) + chromLen + 2400;
-			t->text = (char*) must (realloc (t->text, t->textCap), name);
+			t->text = (char*) must_alloc (realloc (t->text, t->textCap), name);
 			}
 		char* p = t->text + len;
 		memcpy (p, s->chrom, chromLen);  p += chromLen;  *(p++) = '\t';
 		p = put_unsigned (p, (unsigned long long) s->start + g->start + o);  *(p++) = '\t';
-		p = put_unsigned (p, (unsigned long long) s->start + g->end);        *(p++) = '\t';
-		p = put_unsigned (p, r->count);      *(p++) = '\t';
-		p = put_value (p, r->sum, op->precision);
-		if (r->count == 0) { memcpy (p, "\tNA\tNA\tNA\tNA\n", 13);  p += 13; }
-		else
-			{
-			*(p++) = '\t';  p = put_value (p, r->mean, op->precision);
-			*(p++) = '\t';  p = put_value (p, r->min,  op->precision);
-			*(p++) = '\t';  p = put_value (p, r->max,  op->precision);
-			*(p++) = '\t';  p = put_unsigned (p, (unsigned long long) s->start + r->maxpos + o);
-			*(p++) = '\n';
-			}
+		p = put_unsigned (p, (unsigned long long) s->start + g->end);
+		p = put_interval_figures (p, &g->stat, s->start, op->originOne, op->precision);
 		len = (size_t) (p - t->text);
 		}
 	return 0;
@@ -265,9 +246,9 @@ void segments_run (dspop* _op, segments_opts* op, int wantTable, const segments_
 	memset (&t, 0, sizeof(t));
 	t.op = op;  t.name = name;
 	for (spec* s=chromsOfInterest ; s!=NULL ; s=s->next) t.numChroms++;
-	t.chroms = (chromtext*) must (calloc (t.numChroms + 1, sizeof(chromtext)), name);
-	t.mine   = (int*) must (calloc (t.numChroms + 1, sizeof(int)), name);
-	gdsp_batch_item* items = (gdsp_batch_item*) must (calloc (t.numChroms + 1, sizeof(gdsp_batch_item)), name);
+	t.chroms = (chromtext*) must_alloc (calloc (t.numChroms + 1, sizeof(chromtext)), name);
+	t.mine   = (int*) must_alloc (calloc (t.numChroms + 1, sizeof(int)), name);
+	gdsp_batch_item* items = (gdsp_batch_item*) must_alloc (calloc (t.numChroms + 1, sizeof(gdsp_batch_item)), name);
 		{
 		int ci = 0;
 		for (spec* s=chromsOfInterest ; s!=NULL ; s=s->next) t.chroms[ci++].s = s;

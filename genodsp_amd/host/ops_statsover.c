@@ -16,7 +16,6 @@
 #include <string.h>
 #include <math.h>
 #include <float.h>
-#include <time.h>
 #include "genodsp_interface.h"
 #include "genodsp_hip.h"
 #include "utilities.h"
@@ -64,8 +63,7 @@ dspop* op_statsover_parse (char* name, int argc, char** argv)
 		if (strcmp_prefix (arg, "--output=") == 0)
 			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
 		if (sample_opts_take (&op->sample, name, arg, SAMPLE_OPT_PRECISION)) continue;
-		if ((strcmp (arg, "--origin=one") == 0)  || (strcmp (arg, "--origin=1") == 0)) { op->originOne = true;   continue; }
-		if ((strcmp (arg, "--origin=zero") == 0) || (strcmp (arg, "--origin=0") == 0)) { op->originOne = false;  continue; }
+		if (origin_opt_take (arg, &op->originOne)) continue;
 		if (strcmp (arg, "--debug") == 0) continue;
 		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
 		if (op->filename == NULL) { op->filename = copy_string (arg);  continue; }
@@ -95,26 +93,12 @@ typedef struct batch
 	char*  text;   size_t textCap;
 	} batch;
 
-static void* must (void* p, const char* name)
-	{
-	if (p == NULL) { fprintf (stderr, "[%s] out of memory\n", name);  exit (EXIT_FAILURE); }
-	return p;
-	}
-
-static double now_ms (void)
-	{
-	struct timespec t;
-	clock_gettime (CLOCK_MONOTONIC, &t);
-	return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
-	}
-
 /* the pending intervals' figures, device by device (one launch each), then their lines in file order */
 static void flush_batch (dspop_statsover* op, batch* b, u64 pending, FILE* f)
 	{
 	const char* name = op->common.name;
 	const int   numChroms = ib_chromosomes ();
-	const u32   o = op->originOne? 1 : 0;
-	gdsp_batch_item* items = (gdsp_batch_item*) must (calloc (numChroms + 1, sizeof(gdsp_batch_item)), name);
+	gdsp_batch_item* items = (gdsp_batch_item*) must_alloc (calloc (numChroms + 1, sizeof(gdsp_batch_item)), name);
 	if (pending == 0) { free (items);  return; }
 	sync_all_devices ();
 	const double t0 = now_ms ();
@@ -133,11 +117,11 @@ static void flush_batch (dspop_statsover* op, batch* b, u64 pending, FILE* f)
 		if (want > b->ivCap)
 			{
 			free (b->vec);  free (b->start);  free (b->end);  free (b->serial);  free (b->out);
-			b->vec    = (u32*) must (malloc (want * sizeof(u32)), name);
-			b->start  = (u32*) must (malloc (want * sizeof(u32)), name);
-			b->end    = (u32*) must (malloc (want * sizeof(u32)), name);
-			b->serial = (u32*) must (malloc (want * sizeof(u32)), name);
-			b->out    = (gdsp_interval_stat*) must (malloc (want * sizeof(gdsp_interval_stat)), name);
+			b->vec    = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
+			b->start  = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
+			b->end    = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
+			b->serial = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
+			b->out    = (gdsp_interval_stat*) must_alloc (malloc (want * sizeof(gdsp_interval_stat)), name);
 			b->ivCap  = want;
 			}
 		for (int ci=0 ; ci<numChroms ; ci++)
@@ -164,7 +148,6 @@ static void flush_batch (dspop_statsover* op, batch* b, u64 pending, FILE* f)
 	for (u64 r=0 ; r<pending ; r++)
 		{
 		const row* w = &b->rows[r];
-		const gdsp_interval_stat* g = &b->rec[r];
 		const size_t chromLen = strlen (w->s->chrom);
 		if (len + chromLen + 2200 > b->textCap)
 			{
@@ -172,24 +155,14 @@ static void flush_batch (dspop_statsover* op, batch* b, u64 pending, FILE* f)
 			if (chromLen + 2200 > b->textCap)
 				{
 				b->textCap = (1u << 20) + chromLen + 2200;
-				b->text = (char*) must (realloc (b->text, b->textCap), name);
+				b->text = (char*) must_alloc (realloc (b->text, b->textCap), name);
 				}
 			}
 		char* p = b->text + len;
 		memcpy (p, w->s->chrom, chromLen);  p += chromLen;  *(p++) = '\t';
 		p = put_unsigned (p, w->fileStart);  *(p++) = '\t';
-		p = put_unsigned (p, w->fileEnd);    *(p++) = '\t';
-		p = put_unsigned (p, g->count);      *(p++) = '\t';
-		p = put_value (p, g->sum, op->sample.precision);
-		if (g->count == 0) { memcpy (p, "\tNA\tNA\tNA\tNA\n", 13);  p += 13; }
-		else
-			{
-			*(p++) = '\t';  p = put_value (p, g->mean, op->sample.precision);
-			*(p++) = '\t';  p = put_value (p, g->min,  op->sample.precision);
-			*(p++) = '\t';  p = put_value (p, g->max,  op->sample.precision);
-			*(p++) = '\t';  p = put_unsigned (p, (unsigned long long) w->s->start + g->maxpos + o);
-			*(p++) = '\n';
-			}
+		p = put_unsigned (p, w->fileEnd);
+		p = put_interval_figures (p, &b->rec[r], w->s->start, op->originOne, op->sample.precision);
 		len = (size_t) (p - b->text);
 		}
 	if (len != 0) fwrite (b->text, 1, len, f);
@@ -225,31 +198,15 @@ void op_statsover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_co
 
 		const u32 fileStart = start;
 		start -= o;
-		u32 adjStart = start, adjEnd = end;
-		if (s->start == 0)
-			{
-			if (end > s->length)
-				{
-				fprintf (stderr, "[%s] in \"%s\", %s %d %d is beyond the end of the chromosome (L=%d)\n",
-				                 _op->name, op->filename, chrom, start, end, s->length);
-				exit (EXIT_FAILURE);
-				}
-			}
-		else
-			{
-			if (end <= s->start) continue;
-			adjEnd   = end - s->start;
-			adjStart = (start <= s->start)? 0 : start - s->start;
-			if (adjStart >= s->length) continue;
-			if (adjEnd   >= s->length) adjEnd = s->length;
-			}
+		u32 adjStart, adjEnd;
+		if (!place_interval (_op->name, op->filename, chrom, s, start, end, &adjStart, &adjEnd)) continue;
 		if (adjStart >= adjEnd) continue;                      /* (an empty interval has no sample and no line) */
 		const u64 serial = ib_pending ();
 		if (serial >= b.cap)
 			{
 			b.cap  = (b.cap == 0)? 4096 : 2*b.cap;
-			b.rows = (row*) must (realloc (b.rows, b.cap * sizeof(row)), _op->name);
-			b.rec  = (gdsp_interval_stat*) must (realloc (b.rec, b.cap * sizeof(gdsp_interval_stat)), _op->name);
+			b.rows = (row*) must_alloc (realloc (b.rows, b.cap * sizeof(row)), _op->name);
+			b.rec  = (gdsp_interval_stat*) must_alloc (realloc (b.rec, b.cap * sizeof(gdsp_interval_stat)), _op->name);
 			}
 		b.rows[serial].s = s;  b.rows[serial].fileStart = fileStart;  b.rows[serial].fileEnd = end;
 		ib_add (s, adjStart, adjEnd, (valtype) serial);

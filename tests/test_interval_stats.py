@@ -2,14 +2,25 @@
 include/genodsp_hip.h; not in the reference).  Every figure is a function of the interval's sample alone, exact and
 rounded once, so every comparison is bit for bit.  The checker is numpy on the CPU: tests/xsum_ref.py's exact sum of the
 finite, in-range values of v[s:e] for count, sum and mean; numpy's min / max with + 0.0; the first index of the sample
-equal to the maximum.  On integer read depth np.add.reduceat in float64 is exact and checks a whole chromosome."""
+equal to the maximum.  On integer read depth np.add.reduceat in float64 is exact and checks a whole chromosome.
+
+Run as a program it prints a digest of the flagged-pieces call below (its poison test starts it with GDSP_POISON set)."""
 import ctypes
+import hashlib
 import math
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-import xsum_ref as ref
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import xsum_ref as ref                                                                         # noqa: E402
 
 DBL_MAX = ref.DBL_MAX
 TINY = 5e-324
@@ -341,3 +352,55 @@ def test_a_whole_chromosome_of_read_depth():
         assert (int(got["count"][i]), got["sum"][i], got["mean"][i]) == (e - s, total, total / (e - s)), i
         assert got["max"][i] == seg.max() and got["min"][i] == seg.min() and int(got["maxpos"][i]) == s + int(seg.argmax()), i
     assert np.array_equal(d.numpy().view(np.uint64), x.view(np.uint64))           # unchanged afterwards
+
+
+def flagged_beyond_the_first_tile():
+    """Two vectors in one call.  Both are integer read depth, which flags nothing; the second starts on an odd element of
+    its buffer (8-byte but not 16-byte aligned: its frame has a lead), is 2 T + 5 long, and has huge cancelling triples in
+    its second tile and across the boundary into its third.  The piece [2 T - 1, 2 T + 5), all of it in the third tile, sums
+    to -1e308 + 2 + 2^-200, which no two doubles hold: asked for alone, it is one piece and that piece is flagged.  Checked
+    against the exact checker -> (one hash of every byte returned, the flagged pieces of the first call)"""
+    g = dev()
+    T = g.interval_stats_tile()
+    rng = np.random.default_rng(21)
+    n = 2 * T + 5
+    x0, x1 = rng.integers(0, 60, 1000).astype(np.float64), rng.integers(0, 60, n).astype(np.float64)
+    for a, b in ((T + 100, T + 400), (2 * T - 32, 2 * T + 4)):               # (frame tile k is [k T - 1, (k + 1) T - 1) of x1)
+        x1[a:b:3], x1[a + 1:b:3], x1[a + 2:b:3] = 1e308, 1.0, -1e308
+    x1[2 * T + 4] = 2.0 ** -200
+    d0, d1 = g.DeviceVector.from_numpy(x0), g.DeviceVector.from_numpy(np.concatenate([[1e300], x1]))
+    iv = [(0, 0, 1000), (0, 10, 20),
+          (1, T + 50, T + 500), (1, T + 100, T + 103), (1, T - 1, 2 * T - 1),     # wholly inside the second tile
+          (1, 2 * T - 100, 2 * T + 3), (1, 2 * T - 2, 2 * T + 5),                 # across into the third
+          (1, 0, n), (1, 0, T - 1), (1, 1, n - 1)]
+    which, start, end = (np.array(a, np.uint32) for a in zip(*iv))
+    got = g.interval_stats([d0, (d1, 1, n)], start, end, vec=which)
+    flagged = g.interval_stats_last()["flagged"]
+    third = g.interval_stats([d0, (d1, 1, n)], [2 * T - 1], [2 * T + 5], vec=[1])
+    last = g.interval_stats_last()
+    assert (last["pieces"], last["flagged"]) == (1, 1), last
+    h = hashlib.sha256()
+    for k, x in enumerate((x0, x1)):
+        sel = which == k
+        check({name: got[name][sel] for name in got}, x, start[sel], end[sel], what=k)
+    check(third, x1, [2 * T - 1], [2 * T + 5], what="third tile")
+    for table in (got, third):
+        for name in sorted(table):
+            h.update(np.ascontiguousarray(table[name]).tobytes())
+    return h.hexdigest(), flagged
+
+
+@pytest.mark.gpu
+def test_flagged_pieces_beyond_the_first_tile_and_vector():
+    """the second, exact sum of a flagged piece reads the right stretch wherever the piece lies; and again with every
+    device allocation poisoned (the library's own staging and image buffers among them), in a fresh process"""
+    want, flagged = flagged_beyond_the_first_tile()
+    assert flagged > 0
+    p = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, GDSP_POISON="nan"),
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert p.stdout.strip().splitlines()[-1] == "%s %d" % (want, flagged)
+
+
+if __name__ == "__main__":
+    print("%s %d" % flagged_beyond_the_first_tile())

@@ -204,6 +204,56 @@ def test_record_bound_second_call_and_untouched_input(monkeypatch):
             assert buf.numpy().tobytes() == before
 
 
+SPARSE_TILES = 1100
+
+
+def sparse_tiles(_made=[]):
+    """-> (v, where its members lie, the checker's table): SPARSE_TILES tiles of zeros with one member each, at a position
+    that varies with the tile -- more than 1024 work entries in one table, so the work list is regrown while it is being
+    filled.  Made once."""
+    if not _made:
+        t = tile()
+        k = np.arange(SPARSE_TILES)
+        pos = k * t + (k * 37) % t
+        v = np.zeros(SPARSE_TILES * t)
+        v[pos] = 1.0 + k % 7
+        _made.append((v, pos, sref.genome([v], 0.5)))
+    return _made[0]
+
+
+def test_the_checker_finds_one_segment_in_every_sparse_tile():
+    v, pos, want = sparse_tiles()
+    assert len(want) == SPARSE_TILES
+    assert [w[1] for w in want] == pos.tolist() and all(w[2] == w[1] + 1 and w[3] == 1 for w in want)
+
+
+def regrown_work_list():
+    """one record per tile, each where its member is, from run_pieces; the same through the builder.  For a process that
+    has made no call yet: its work list starts at 1024 entries and is regrown at the 1025th tile"""
+    v, pos, want = sparse_tiles()
+    item, buf = put(v, 0)
+    chunks = gd().run_pieces([item], 0.5)
+    recs = np.concatenate([c[0] for c in chunks])
+    assert recs.size == SPARSE_TILES and all(c[1] is None for c in chunks)
+    assert np.array_equal(recs["vec"], np.zeros(SPARSE_TILES, np.uint32))
+    assert np.array_equal(recs["start"], pos) and np.array_equal(recs["end"], pos + 1)
+    pc = recs["piece"]
+    assert np.array_equal(pc["count"], np.ones(SPARSE_TILES, np.uint32)) and np.array_equal(pc["maxpos"], pos)
+    for name in ("a0", "min", "max"):
+        assert pc[name].tobytes() == v[pos].tobytes(), name
+    assert not pc["a1"].any() and not np.signbit(pc["a1"]).any() and not pc["flag"].any()
+    sref.same_table(gd().segments([item], 0.5), want)
+    return "regrown %d" % recs.size
+
+
+@pytest.mark.gpu
+def test_a_work_list_that_is_regrown_while_it_is_filled():
+    """in a fresh process, whose buffers no earlier test has grown: the first call there is the one that regrows"""
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "regrow"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert p.stdout.strip().splitlines()[-1] == "regrown %d" % SPARSE_TILES
+
+
 def digest():
     """a fixed set of calls -> one hash of every byte they return"""
     t = tile()
@@ -232,4 +282,4 @@ def test_poisoned_allocations_do_not_move_the_results():
 
 
 if __name__ == "__main__":
-    print(digest())
+    print(regrown_work_list() if sys.argv[1:] == ["regrow"] else digest())
