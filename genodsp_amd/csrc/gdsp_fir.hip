@@ -5,6 +5,11 @@
 // with taps outside [0,n) skipped.  Skipping a tap and adding taps[k]*(+0.0) give
 // the same bits (the running sum starts at +0.0 and can never become -0.0), so
 // the kernels stage a zero-padded tile and run the full tap range everywhere.
+// That needs finite taps (inf * 0 is NaN: gdsp_fir_plan_create refuses others).  One corner of FMA mode is outside it: a
+// fused step whose exact value is negative and too small for a subnormal rounds to -0.0, and a padded tap w[k] * (+0.0)
+// with w[k] > 0 turns that into +0.0 where skipping keeps -0.0 -- the sign of a zero at the bottom of the range.
+// Taps are applied as given, k ascending against ascending inputs (correlation order, not flipped), for ANY taps: only
+// gdsp_fir_slide.hip assumes w[k] == w[W-1-k], and a plan goes there only when its taps are mirrored bit for bit.
 //
 // Shape of the work on MI355X.  W=101 taps on f64 is 101 multiply-adds against
 // 16 bytes per base: the FP64 vector pipe (16 lanes/clk/SIMD), not HBM, is the
@@ -357,6 +362,7 @@ struct gdsp_fir_plan
 	uint32_t W;
 	double*  h_taps;     // W values
 	double*  d_taps;     // W values + padding, device
+	bool     mirrored;   // w[k] and w[W-1-k] are the same 8 bytes for every k (what gdsp_fir_slide.hip assumes)
 	};
 
 extern "C" {
@@ -385,12 +391,16 @@ int gdsp_fir_plan_create (gdsp_fir_plan** plan, const double* h_taps, uint32_t W
 	GDSP_REQUIRE (plan != NULL, "plan is NULL");
 	GDSP_REQUIRE (h_taps != NULL, "h_taps is NULL");
 	GDSP_REQUIRE ((W >= 1) && (W & 1), "W must be odd");
+	// zero padding stands for the reference's skipped taps only while tap * (+0.0) is a zero: inf * 0 and NaN * 0 are NaN
+	for (uint32_t k=0 ; k<W ; k++) GDSP_REQUIRE (isfinite (h_taps[k]), "taps must be finite");
 	gdsp_fir_plan* p = (gdsp_fir_plan*) calloc (1, sizeof(gdsp_fir_plan));
 	if (p == NULL) { gdsp_set_error ("out of host memory");  return GDSP_ENOMEM; }
 	p->W = W;
 	p->h_taps = (double*) malloc ((size_t) W * sizeof(double));
 	if (p->h_taps == NULL) { free (p);  gdsp_set_error ("out of host memory");  return GDSP_ENOMEM; }
 	memcpy (p->h_taps, h_taps, (size_t) W * sizeof(double));
+	p->mirrored = true;                                    // (bit patterns, not values: the slide route must see the same doubles)
+	for (uint32_t k=0 ; k<W/2 ; k++) p->mirrored = p->mirrored && (memcmp (&h_taps[k], &h_taps[W-1-k], sizeof(double)) == 0);
 	size_t padded = (size_t) W + 2*FIR_R;
 	hipError_t e = hipMalloc ((void**) &p->d_taps, padded * sizeof(double));
 	if (e != hipSuccess) { free (p->h_taps);  free (p);  GDSP_HIP_TRY (e); }
@@ -425,7 +435,8 @@ int gdsp_fir_apply (const gdsp_fir_plan* plan, const double* d_in, double* d_out
 	const uint32_t ntiles = (uint32_t) (((uint64_t) n + T - 1) / T);
 	hipStream_t    s = gdsp_stream (stream);
 
-	if ((plan->W == 101) && (mode == GDSP_FIR_EXACT) && gdsp_fir_slide_wanted (n))
+	// the sliding-accumulator kernel computes w[m] x[j] once for taps m and 100-m: mirrored taps only (every Hann plan is)
+	if ((plan->W == 101) && plan->mirrored && (mode == GDSP_FIR_EXACT) && gdsp_fir_slide_wanted (n))
 		{
 		const gdsp_batch_item one = { d_in, d_out, n };
 		return gdsp_fir_slide_batch (&one, 1, plan->h_taps, stream);

@@ -307,6 +307,7 @@ static uint32_t fs_strip_length (uint64_t totalBases)
 	return (uint32_t) ((S + 15) / 16 * 16);
 	}
 
+// h_taps: 101 MIRRORED taps (w[100-m] and w[m] the same double; the callers in gdsp_fir.hip see to it): only w[0..50] are read
 int gdsp_fir_slide_batch (const gdsp_batch_item* items, int nitems, const double* h_taps, void* stream)
 	{
 	FsTaps taps;

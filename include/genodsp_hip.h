@@ -85,7 +85,12 @@ int gdsp_fill           (double* d_v, uint32_t n, double val, void* stream);
 /* Host: the reference's Hann taps (sum.c:632-645), W odd >= 3. */
 int gdsp_hann_taps (uint32_t W, double* h_taps);
 
-/* op_smooth_apply (sum.c:616-676): zero-padded W-tap FIR, out-of-place. */
+/* op_smooth_apply (sum.c:616-676): zero-padded W-tap FIR, out-of-place.  A plan takes any odd number W >= 1 of
+ * arbitrary finite taps and applies them as out[i] = sum_k w[k] v[i-h+k], h = (W-1)/2, k ascending from a sum of +0.0,
+ * inputs outside [0,n) skipped: correlation order, the taps are NOT flipped (a convolution kernel is passed reversed).
+ * GDSP_FIR_EXACT rounds every product and every sum, GDSP_FIR_FMA fuses each tap's two into one rounding.
+ * gdsp_fir_plan_create refuses a NaN or infinite tap (GDSP_EINVAL): the kernels pad with zeros instead of skipping,
+ * which is the same only while tap * (+0.0) is a zero, and inf * 0 is NaN. */
 typedef struct gdsp_fir_plan gdsp_fir_plan;
 int gdsp_fir_plan_create  (gdsp_fir_plan** plan, const double* h_taps, uint32_t W);
 int gdsp_fir_plan_destroy (gdsp_fir_plan* plan);
