@@ -9,7 +9,8 @@
 //     segment, walking it in 2048-base chunks with a carry), then out = pick(Hs[a], G[b]) for the
 //     window [a,b]; 48-56 B/base of traffic instead of 16, but any window.
 //   * slidingsum: whole-vector cumulative sum, then the difference of two prefix values per base
-//     (bit-identical on exactly summable signals, like the tiled form).
+//     (bit-identical on exactly summable signals, like the tiled form; on other reals within the
+//     allowances of the two prefixes, as tests/runsum_ref.py's sliding_exact grants them).
 // The *_any entry points pick the tiled kernel whenever the window fits it.
 
 #include <math.h>

@@ -12,7 +12,12 @@
 //   * `slidingsum`, `cumulativesum`, and `sum` over longer windows: bit-identical
 //     whenever every partial sum is exactly representable (integer or dyadic
 //     signals such as read depth, the operator's normal input); otherwise within
-//     the reference's own accumulated rounding error (tests state the bound).
+//     what any order of summation may differ from the exact sum by, per position:
+//     tests/runsum_ref.py derives it (cumsum_exact: gamma_k sum|v[0..k]|;
+//     sliding_exact: gamma_(2 (W + 4096) + 4) sum|v| over the window and one tile on
+//     either side; window_exact: gamma_len sum|v| over the window) and
+//     tests/test_hip_cumsum_real.py, tests/test_hip_windowsum_real.py hold every
+//     route to it, bit for bit where no sum of the span can round.
 // All three are HBM-bound (16 B/base).
 
 #include <mutex>

@@ -1,5 +1,5 @@
-"""The inputs of the real-valued running-sum tests (test_runsum_ref.py on the CPU, test_hip_clump_real.py and
-test_hip_cumsum_real.py on the GPU): fixed seeds, nothing here touches a GPU.
+"""The inputs of the real-valued running-sum tests (test_runsum_ref.py on the CPU, test_hip_clump_real.py,
+test_hip_cumsum_real.py and test_hip_windowsum_real.py on the GPU): fixed seeds, nothing here touches a GPU.
 
 clump classes
   natural  three signals with islands of about 700, 3000 and 12 000 bases (shorter in short vectors) so that every L
@@ -174,3 +174,69 @@ def super_group(real):
         return depth(SUPER_N)
     rng = np.random.default_rng(SEED + 33)
     return 16.0 + rng.integers(0, 32 << 30, SUPER_N).astype(np.float64) * 2.0 ** -30
+
+
+# ---- slidingsum and sum on real values (test_hip_windowsum_real.py; the checker's own tests use prefixes of these)
+
+WINDOW_SIGNALS = ("positive", "mixed", "smooth", "grid")
+WINDOW_N = 300007                               # crosses cumulativesum's chunks (8192) and groups (524 288 / 64 chunks)
+WINDOW_LONG_N = 130003                          # "about 130 000": more than 30 tiles of either tiled form
+
+# gdsp_sliding_sum's routes (W <= 14332) and gdsp_sliding_sum_any's whole-vector route; every form's first and last
+# window, both parities, and the block form's switch from blocks added one by one to a running sum over block totals
+# (more than 8 whole blocks between: W >= 161)
+SLIDING_WINDOWS = {"prefix-short": (3, 4, 16),
+                   "blocks": (17, 18, 33, 100, 101, 160, 161, 1000, 2047, 2048),
+                   "prefix-long": (2049, 4001, 8192, 8193, 14332),
+                   "whole-vector": (14333, 20000, 65536, 400000)}          # 400 000: longer than every vector here
+SLIDING_ODD_DENOMS = (4, 16, 100, 161, 2049, 14332, 14333, 65536)           # two per form: 3.0 and float(W) as well
+
+SUM_WINDOWS = (8193, 9000, 50000)               # window_sum_wide_kernel
+
+
+@functools.lru_cache(maxsize=None)
+def window_signal(kind):
+    """300 007 bases; the shorter cases are its prefixes.  grid: multiples of 2^-30 in [16, 48), as super_group(True)
+    draws them -- no sum of 2^17 of them rounds (below 2^23 at quantum 2^-30)"""
+    if kind == "grid":
+        rng = np.random.default_rng(SEED + 34)
+        v = 16.0 + rng.integers(0, 32 << 30, WINDOW_N).astype(np.float64) * 2.0 ** -30
+    else:
+        v = np.array(cumsum_signal(kind)[:WINDOW_N])
+    v.setflags(write=False)
+    return v
+
+
+def sliding_route(W):
+    return next(route for route, ws in SLIDING_WINDOWS.items() if W in ws)
+
+
+def sliding_outs(W):
+    """outputs per workgroup, as gdsp_sliding_sum lays the tiles out: the block form gives up (W-1)//16 + 1 of its 256
+    blocks of 16 to the halo and 2 more outputs where the alignment shift is needed; the prefix form writes 4096"""
+    if 17 <= W <= 2048:
+        sh = ((W - 1) // 2) & 1
+        return (256 - ((W - 1) // 16 + 1)) * 16 - 2 * sh
+    return 4096
+
+
+def sliding_lengths(W):
+    if W > 14332:
+        every = {1, W - 1, W, W + 1, WINDOW_LONG_N, WINDOW_N}
+    else:
+        outs = sliding_outs(W)
+        every = {1, W - 1, W, W + 1, outs - 1, outs, outs + 1, 2 * outs + 3, 3 * outs + 5, WINDOW_LONG_N}
+    return tuple(sorted(n for n in every if 1 <= n <= WINDOW_N))
+
+
+def sliding_denoms(W):
+    return (1.0, 0.25, 3.0, float(W)) if W in SLIDING_ODD_DENOMS else (1.0, 0.25)
+
+
+def sum_lengths(W):
+    return tuple(sorted({W - 1, W, W + 1, 3 * W + W // 3, 100003}))
+
+
+def sum_params(W):
+    """(denom, use_actual, zero)"""
+    return ((1.0, False, 0.0), (float(W), False, 0.0), (1.0, True, -1.0))

@@ -1,5 +1,6 @@
 """Exact checker for the operators that keep one running sum along the whole chromosome: clump / anticlump
-(gdsp_clump.hip) and cumulativesum (gdsp_sums.hip).  CPU only: numpy and Python ints.
+(gdsp_clump.hip) and cumulativesum (gdsp_sums.hip), and for the window sums formed from such sums: slidingsum and `sum`
+over windows beyond 8192 bases (gdsp_sums.hip, gdsp_longwin.hip).  CPU only: numpy and Python ints.
 
 Like xsum_ref.py it rests on every finite double being an integer times a power of two, so the prefix sums
 
@@ -25,6 +26,35 @@ marked bases is then trimmed to its first and last base on the threshold's side.
 and both marking and trimming are monotone in the set of admitted pairs, so the output under the second test
 ("strict") is contained in every correct output, which is contained in the output under the first ("lenient").
 
+Window sums.  slidingsum's window at base c is [lo, hi] = [max(0, c-lft), min(n-1, c+rgt)], rgt = (W-1)//2,
+lft = W-1-rgt (sum.c:436-455; an even W reaches one base further to the left); `sum`'s windows are [s, min(s+W, n)-1]
+for s = 0, W, 2W, ... (the last one ragged), the result goes to base s and the zero value to the window's other bases
+(sum.c:230-249).  In both S = P[hi] - P[lo-1] is formed in integers, and what a correct evaluation may return is
+|x~ - S| <= E with E stated per route, again without reference to one order of summation:
+
+  tiled slidingsum (W <= TILED_MAX_W = 14332: the prefix form and the block form of gdsp_sliding_sum).  A workgroup
+    stages the windows of its outputs and sums inside what it staged: at most TILE = 4096 bases beyond the window on
+    either side.  It may associate those terms in any way (a running sum from the tile's first base, block totals, a
+    running sum over block totals) and may form the window as the difference of two such partial sums.  Each partial
+    sum has at most W + TILE terms out of the span Z = [c-lft-TILE, c+rgt+TILE] (clipped to the vector), so it is off
+    by at most gamma_(W+TILE-1) A(Z); the difference adds the two errors and one rounding of its own, u (|S| + both
+    errors) <= u (1 + 2 gamma) A(Z); and the exact value this checker returns is itself rounded once, u |S| <= u A(Z).
+    In all fewer than 2 (W + TILE) + 4 factors (1 + delta), |delta| <= u, per term:
+        E[c] = gamma_m A(Z),    m = 2 (W + TILE) + 4
+    and E[c] = 0 where A(Z) <= 2^53 q: then no sum of any of the span's terms rounds and the result is S, bit for bit.
+  whole-vector slidingsum (W > TILED_MAX_W: gdsp_sliding_sum_any copies the vector, runs cumulativesum over the copy
+    and subtracts two of its values).  E[c] = eps[hi] + eps[lo-1], eps exactly what cumsum_exact grants each prefix
+    (eps[-1] = 0: nothing is subtracted there).  This is a little stronger than "any order": it leaves the
+    subtraction's own rounding, u |S|, no room of its own.  Where something is subtracted (lo >= 1) hi >= W-1 >= 14332,
+    so that rounding is at most 1/14332 of eps[hi], which a prefix of that length only uses up if it is one chain of
+    hi additions whose every rounding goes the same way; cumulativesum's chunked look-back is far from that.
+  `sum`.  One window of len = hi-lo+1 terms in any order or tree: len-1 additions, and one more factor for the
+    rounding of the checker's own exact value:  E = gamma_len A(window), 0 where A(window) <= 2^53 q.
+
+The quotient.  got = fl(x~ / denom), so |got - S/denom| <= (E + u (|S| + E)) / |denom|: that, rounded up, is `allow`.
+Dividing by a power of two does not round and the u term is dropped.  `exact` is S / denom rounded once (to nearest,
+from the integers: never the quotient of an already rounded S).
+
 Two back ends, same results where both apply:
   "int"    Python ints, any finite doubles; a few microseconds per base
   "int64"  numpy int64 for values (and threshold) that are multiples of 2^-30 with sum |d| 2^30 < 2^62; a second or
@@ -37,6 +67,10 @@ import numpy as np
 
 U_BITS = 53
 GRID_BITS = 30                                  # the int64 back end's quantum is 2^-30
+TILE = 4096                                     # gdsp_sliding_sum's `tile` (prefix form) and SLB_ELEMS (block form): no
+                                                # workgroup stages, or sums, more than this beyond a window on either side
+TILED_MAX_W = 14332                             # gdsp_sliding_sum: 18432 doubles of LDS - tile - 4; longer windows go
+                                                # through gdsp_sliding_sum_any's whole-vector route
 MAX_INT64_N = 1 << 26                           # k A[k] is formed in two limbs that assume k < 2^26
 
 
@@ -88,12 +122,17 @@ def _quantum(D):
     return (bits & -bits) or 1
 
 
-def _ceil_kA_over_den(A):
-    """ceil(k A[k] / (2^53 - k)) for k = 0 .. n-1 in int64, exactly: k A[k] < 2^88 is held as hi 2^31 + lo and divided
-    eight (seven) bits at a time, so that no intermediate reaches 2^63"""
+def _ceil_kA_over_den(A, k=None):
+    """ceil(k A[k] / (2^53 - k)) for k = 0 .. n-1 (or the k given: one number or one per entry, below 2^26) in int64,
+    exactly: k A[k] < 2^88 is held as hi 2^31 + lo and divided eight (seven) bits at a time, so that no intermediate
+    reaches 2^63"""
     n = A.size
-    assert n <= MAX_INT64_N and (n == 0 or (0 <= int(A[0]) and int(A[-1]) < (1 << 62)))
-    k = np.arange(n, dtype=np.int64)
+    if k is None:
+        assert n <= MAX_INT64_N and (n == 0 or (0 <= int(A[0]) and int(A[-1]) < (1 << 62)))
+        k = np.arange(n, dtype=np.int64)
+    else:
+        k = np.broadcast_to(np.asarray(k, np.int64), A.shape)
+        assert n == 0 or (0 <= int(k.min()) and int(k.max()) <= MAX_INT64_N and 0 <= int(A.min()) and int(A.max()) < (1 << 62))
     den = (np.int64(1) << U_BITS) - k
     low = k * (A & ((1 << 31) - 1))                         # < 2^57
     hi = k * (A >> 31) + (low >> 31)                        # < 2^58
@@ -126,7 +165,8 @@ class Prefix:
             self.A = np.cumsum(np.abs(D))
             assert n == 0 or int(self.A[-1]) < (1 << 62)
             self.eps = np.zeros(n, np.int64)
-            rounds = int(np.searchsorted(self.A, min(_quantum(D) << U_BITS, 1 << 62), "right"))          # the first k with A[k] above it
+            self.exact_below = min(_quantum(D) << U_BITS, 1 << 62)            # 2^53 q: no sum with A up to here rounds
+            rounds = int(np.searchsorted(self.A, self.exact_below, "right"))                            # the first k with A[k] above it
             if slack and rounds < n:
                 self.eps[rounds:] = _ceil_kA_over_den(self.A)[rounds:]
         else:
@@ -134,12 +174,14 @@ class Prefix:
             D, self.E = _as_ints(d, unit)
             self.P = list(itertools.accumulate(D))
             self.A = list(itertools.accumulate(map(abs, D)))
+            self.exact_below = _quantum(D) << U_BITS
             if slack:
-                one, exact = 1 << U_BITS, _quantum(D) << U_BITS
+                one, exact = 1 << U_BITS, self.exact_below
                 self.eps = [0 if a <= exact else -((-k * a) // (one - k)) for k, a in enumerate(self.A)]
             else:
                 self.eps = [0] * n
         self._from = None
+        self._padded = None
 
     # -- as doubles
     def _to_float(self, ints, up):
@@ -155,6 +197,46 @@ class Prefix:
     def eps_float(self):
         """eps, rounded up"""
         return self._to_float(self.eps, True)
+
+    # -- window sums
+    def padded(self):
+        """(P, A, eps) as arrays with a 0 in front: entry k+1 belongs to base k, entry 0 to "before the vector" (int64,
+        or Python ints in object arrays)"""
+        if self._padded is None:
+            dt = np.int64 if self.backend == "int64" else object
+            self._padded = tuple(np.concatenate((np.zeros(1, dt), np.array(x, dtype=dt))) if self.n else np.zeros(1, dt)
+                                 for x in (self.P, self.A, self.eps))
+        return self._padded
+
+    def gamma_times(self, m, A):
+        """ceil(gamma_m A) = ceil(m A / (2^53 - m)) where A is above 2^53 q, 0 where no sum of such terms can round"""
+        if self.backend == "int64":
+            g = _ceil_kA_over_den(A, m)
+        else:
+            m = np.broadcast_to(np.asarray(m), A.shape).astype(object)          # (Python ints: an int64 times a long int is a float)
+            g = -((-m * A) // ((1 << U_BITS) - m))
+        return np.where(A <= self.exact_below, 0, g) if A.size else A
+
+    def quotient(self, S, E, den):
+        """(S / den rounded once, (E + u (|S| + E)) / |den| rounded up; the u term only where den is no power of two);
+        den: one double or one per entry"""
+        n = S.size
+        den = np.broadcast_to(np.asarray(den, np.float64), S.shape)
+        assert np.all(np.isfinite(den)) and np.all(den != 0.0)
+        m, e = np.frexp(den)
+        pow2 = np.abs(m) == 0.5
+        exact = self._to_float(S, False) / den if n else np.zeros(0)            # a power of two: scaled, not rounded again
+        allow = self._to_float(E, True)
+        if not pow2.all():
+            D = np.ldexp(m, U_BITS).astype(np.int64).tolist()                    # den = D 2^(e-53), exactly
+            ints, rest = S.tolist(), np.flatnonzero(~pow2)
+            q = np.array([ints[i] / D[i] for i in rest.tolist()], np.float64)    # int / int: rounded once, to nearest
+            exact[rest] = np.ldexp(q, self.E - (e[rest].astype(np.int64) - U_BITS))
+            absS = np.abs(S) if self.backend == "int64" else np.array([abs(x) for x in ints], dtype=object)
+            up = lambda x: np.where(x > 0, np.nextafter(x, np.inf), x)
+            allow = np.where(pow2, allow, up(allow + np.ldexp(self._to_float(absS + E, True), -U_BITS)))
+        allow = allow / np.abs(den)
+        return exact, np.where(allow > 0, np.nextafter(allow, np.inf), allow)
 
     # -- clump
     def froms(self):
@@ -219,6 +301,53 @@ def cumsum_exact(v, backend=None, unit=None):
     """(the exact prefix sums rounded once, eps rounded up), per position"""
     p = Prefix(_terms(v, None, True), backend, True, unit)
     return p.exact(), p.eps_float()
+
+
+class Sliding:
+    """slidingsum of one vector at one W: S and E per base in the prefix's unit, whatever the denominator"""
+
+    def __init__(self, prefix, W):
+        assert W >= 1
+        self.prefix, self.W, n = prefix, W, prefix.n
+        self.tiled = W <= TILED_MAX_W
+        rgt = (W - 1) // 2
+        lft = W - 1 - rgt
+        c = np.arange(n, dtype=np.int64)
+        self.lo, self.hi = np.maximum(c - lft, 0), np.minimum(c + rgt, n - 1)
+        P, A, eps = prefix.padded()
+        self.S = P[self.hi + 1] - P[self.lo]
+        if self.tiled:
+            a, b = np.maximum(c - lft - TILE, 0), np.minimum(c + rgt + TILE, n - 1)
+            self.E = prefix.gamma_times(2 * (W + TILE) + 4, A[b + 1] - A[a])
+        else:
+            self.E = eps[self.hi + 1] + eps[self.lo]
+
+    def over(self, denom):
+        """(exact, allow) per base"""
+        return self.prefix.quotient(self.S, self.E, float(denom))
+
+
+def sliding_exact(v, W, denom=1.0, backend=None):
+    """slidingsum: (the exact window sums over denom rounded once, what a correct result may differ by), per base.
+    v: the values, or their Prefix"""
+    p = v if isinstance(v, Prefix) else Prefix(_terms(v, None, True), backend)
+    return Sliding(p, W).over(denom)
+
+
+def window_exact(v, W, denom=1.0, use_actual=False, zero=0.0, backend=None):
+    """`sum`: (exact, allow, is_sum) per base: at a window's first base the exact sum over denom (over the window's own
+    length with use_actual) rounded once and its allowance; `zero` and 0 at every other base"""
+    assert W >= 1
+    p = v if isinstance(v, Prefix) else Prefix(_terms(v, None, True), backend)
+    n = p.n
+    s = np.arange(0, n, W, dtype=np.int64)
+    e = np.minimum(s + W, n)
+    P, A, _ = p.padded()
+    E = p.gamma_times(e - s, A[e] - A[s])
+    q, a = p.quotient(P[e] - P[s], E, (e - s).astype(np.float64) if use_actual else float(denom))
+    exact, allow, is_sum = np.full(n, float(zero)), np.zeros(n), np.zeros(n, bool)
+    exact[s], allow[s], is_sum[s] = q, a, True
+    return exact, allow, is_sum
 
 
 def runs(b):
