@@ -303,6 +303,30 @@ def prominence(v, W, as_="prominence", out=None, stream=None):
     return out
 
 
+# ------------------------------------------------- localstats (not in the reference) ----
+
+LOCALSTATS_MAX_WINDOW = 12287                 # GDSP_LOCALSTATS_MAX_WINDOW
+LOCALSTATS_WHAT = {"zscore": 0, "mean": 1, "variance": 2, "stddev": 3, "difference": 4, "ratio": 5}    # GDSP_LOCALSTATS_*
+
+
+def _localstats_params(W, as_, floor, minsd):
+    if as_ not in LOCALSTATS_WHAT:
+        raise ValueError("as_ must be one of %s, not %r" % (", ".join(LOCALSTATS_WHAT), as_))
+    return (int(W), LOCALSTATS_WHAT[as_], int(floor is not None), float(floor or 0.0),
+            int(minsd is not None), float(minsd or 0.0))
+
+
+def local_stats(v, W, as_="zscore", floor=None, minsd=None, out=None, stream=None):
+    """out[c] = v[c] against the mean and the population variance of slidingsum's window around c, cut off at the ends
+    of the vector (gdsp_localstats in include/genodsp_hip.h): the z-score, or with as_ the mean, variance, stddev,
+    difference or ratio.  floor: max(mean, floor) stands for the mean in mean, difference and ratio; minsd: max(stddev,
+    minsd) for the stddev in stddev and zscore."""
+    params = _localstats_params(W, as_, floor, minsd)
+    out = out if out is not None else v.like()
+    call("gdsp_localstats", v.ptr, out.ptr, v.n, *params, _sp(stream))
+    return out
+
+
 # ---------------------------------------------------------- morphology.c ----
 
 def split_length(length):
@@ -1420,6 +1444,10 @@ def sliding_percentile_batch(vecs, W, p_thousandths, outs=None, stream=None):
 
 def prominence_batch(vecs, W, as_="prominence", outs=None, stream=None):
     return _batch("gdsp_prominence_batch", vecs, outs, int(W), _prominence_what(as_), stream=stream)
+
+
+def local_stats_batch(vecs, W, as_="zscore", floor=None, minsd=None, outs=None, stream=None):
+    return _batch("gdsp_localstats_batch", vecs, outs, *_localstats_params(W, as_, floor, minsd), stream=stream)
 
 
 def dilate_batch(vecs, left, right, T=0.0, one=1.0, zero=0.0, outs=None, stream=None):

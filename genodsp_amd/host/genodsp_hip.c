@@ -83,6 +83,9 @@ dspprototypes(op_keepsegments)
 #ifdef GDSP_PROMINENCE                                 /* not in the reference: ops_prominence.c */
 dspprototypes(op_prominence)
 #endif
+#ifdef GDSP_LOCALSTATS                                 /* not in the reference: ops_localstats.c */
+dspprototypes(op_localstats)
+#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
@@ -161,6 +164,10 @@ static dspinfo dspTable[] =
 #endif
 #ifdef GDSP_PROMINENCE                                 /* how far each base stands above its surroundings, after those */
 	 , dspinforecord("prominence"  , op_prominence)     , dspinfoalias ("peakprominence")
+#endif
+#ifdef GDSP_LOCALSTATS                                 /* each base against the window around it, between those and `stats` */
+	 , dspinforecord("localstats"  , op_localstats)     , dspinfoalias ("local_stats")    , dspinfoalias ("localzscore")
+	 , dspinfoalias ("localbackground")
 #endif
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS
 	 , GDSP_EXTRA_DSPTABLE_ROWS

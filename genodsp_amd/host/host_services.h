@@ -105,6 +105,10 @@ int   op_rankfilt_batch   (dspop* op, const gdsp_batch_item* items, int nitems, 
 int   op_prominence_is     (dspop* op);
 u32   op_prominence_window (dspop* op);
 int   op_prominence_batch  (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
+/* ops_localstats.c (localstats; compiled in with -DGDSP_LOCALSTATS): likewise */
+int   op_localstats_is     (dspop* op);
+u32   op_localstats_window (dspop* op);
+int   op_localstats_batch  (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
 /* ops_stats.c (stats, normalize, multiplyconst, divideconst; compiled in with -DGDSP_GENOME_STATS) */
 int   op_const_is         (dspop* op);       /* multiplyconst / divideconst: per-base, in place */
 int   op_const_batch      (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);

@@ -45,6 +45,10 @@ int op_reach (dspop* op, u32* left, u32* right)
 	if (op_prominence_is (op))                             /* the same window: neither walk leaves [i-wL, i+wR] */
 		{ u32 W = op_prominence_window (op);  *left = (W - 1) / 2;  *right = W - 1 - *left;  return true; }
 #endif
+#ifdef GDSP_LOCALSTATS
+	if (op_localstats_is (op))                             /* slidingsum's window: [c-lft, c+rgt], the longer side on the left */
+		{ u32 W = op_localstats_window (op);  *right = (W - 1) / 2;  *left = W - 1 - *right;  return true; }
+#endif
 	return false;                                          /* sum, slidingsum, cumulativesum, clump, anticlump, plugins */
 	}
 
@@ -97,6 +101,9 @@ int op_batchable (dspop* op)
 #endif
 #ifdef GDSP_PROMINENCE
 	if (op_prominence_is (op)) return true;
+#endif
+#ifdef GDSP_LOCALSTATS
+	if (op_localstats_is (op)) return true;
 #endif
 #ifdef GDSP_GENOME_STATS
 	if (op_const_is (op)) return true;
@@ -184,6 +191,10 @@ int batch_apply_on_device (dspop* op, dspop* stopOp, spec** units, int nunits, i
 #ifdef GDSP_PROMINENCE
 	else if (op_prominence_is (op))
 		rc = op_prominence_batch (op, items, nunits, st);     /* (likewise) */
+#endif
+#ifdef GDSP_LOCALSTATS
+	else if (op_localstats_is (op))
+		rc = op_localstats_batch (op, items, nunits, st);     /* (likewise) */
 #endif
 	else
 		{

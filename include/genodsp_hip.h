@@ -252,6 +252,50 @@ uint32_t gdsp_prominence_tile  (uint32_t W);
 int gdsp_prominence       (const double* d_in, double* d_out, uint32_t n, uint32_t W, int what, void* stream);
 int gdsp_prominence_batch (const gdsp_batch_item* items, int nitems, uint32_t W, int what, void* stream);
 
+/* ---- localstats (not in the reference): each base against the mean and variance of the window centred on it -----
+ * Take a vector v of n values and a window W with 1 <= W <= GDSP_LOCALSTATS_MAX_WINDOW.  The window is slidingsum's
+ * (sum.c:436-455), cut off at the ends of the vector: with rgt = (W-1)/2 and lft = W-1-rgt (an even W reaches one
+ * base further to the left), base c has lo = max(0, c-lft), hi = min(n-1, c+rgt) and m = hi-lo+1 bases in its window.
+ *   S1 = the sum of v[k], S2 = the sum of fl(v[k] v[k]) over k = lo .. hi (one rounded product per term).
+ * From these, every step one rounded IEEE operation on doubles, in this order and never fused:
+ *   mean     = fl(S1 / m)
+ *   N        = fl(fl(m S2) - fl(S1 S1))
+ *   variance = +0.0 if N <= 0, else fl(N / fl(m m))          (the population variance, as in gdsp_genome_stats)
+ *   stddev   = sqrt(variance), correctly rounded
+ *   bg       = floor if haveFloor and floor > mean, else mean       (MACS's max(local, genome-wide))
+ *   sd       = minSd if haveMinSd and minSd > stddev, else stddev
+ * what:  GDSP_LOCALSTATS_MEAN       writes bg
+ *        GDSP_LOCALSTATS_VARIANCE   writes variance
+ *        GDSP_LOCALSTATS_STDDEV     writes sd
+ *        GDSP_LOCALSTATS_DIFFERENCE writes fl(v[c] - bg)
+ *        GDSP_LOCALSTATS_RATIO      writes fl(v[c] / bg), +0.0 where bg == 0
+ *        GDSP_LOCALSTATS_ZSCORE     writes fl(fl(v[c] - mean) / sd), +0.0 where sd == 0
+ * so the floor touches mean, difference and ratio only, and minSd stddev and zscore only.
+ * The two sums may be formed in any order or tree, inside the tile a workgroup stages: no further than
+ * gdsp_localstats_tile(W) bases beyond the window on either side.  A result therefore lies within what
+ * S1 +- gamma_M A1 and S2 +- gamma_M A2 allow, M = 2 (W + tile) + 4, A the sum of the magnitudes over the window
+ * widened by the tile (tests/localstats_ref.py pushes those intervals through the steps above).  Where no sum of those
+ * terms can round, every figure is the definition's, bit for bit, however the implementation sums: for read depth N is
+ * exact while m S2 < 2^53 (depth up to about 9000 at W = 10001) and variance is then the exact population variance of
+ * the window, rounded once.  Non-finite values inside a window give that base whatever the arithmetic above gives.
+ * Out-of-place; GDSP_EINVAL for d_in == d_out, W == 0, W above the maximum or an unknown `what`; n == 0 is a no-op.
+ * One kernel launch covers every vector of a batch, and the single-vector call runs the same kernel over a table of
+ * one (gdsp_localstats.hip: per tile the staged values in LDS, running sums over blocks of 16 of them for v and for
+ * fl(v v), each window's two sums as differences, and the staged v for the last step). */
+#define GDSP_LOCALSTATS_MAX_WINDOW 12287       /* what leaves a workgroup's 16384 staged values a tile of 4096 */
+#define GDSP_LOCALSTATS_ZSCORE     0
+#define GDSP_LOCALSTATS_MEAN       1
+#define GDSP_LOCALSTATS_VARIANCE   2
+#define GDSP_LOCALSTATS_STDDEV     3
+#define GDSP_LOCALSTATS_DIFFERENCE 4
+#define GDSP_LOCALSTATS_RATIO      5
+/* Host: outputs per workgroup tile of the kernel for window W (0 outside 1..the maximum) */
+uint32_t gdsp_localstats_tile  (uint32_t W);
+int gdsp_localstats       (const double* d_in, double* d_out, uint32_t n, uint32_t W, int what,
+                           int haveFloor, double floor, int haveMinSd, double minSd, void* stream);
+int gdsp_localstats_batch (const gdsp_batch_item* items, int nitems, uint32_t W, int what,
+                           int haveFloor, double floor, int haveMinSd, double minSd, void* stream);
+
 /* ---- logical.c, mask.c, add.c (in place) ---------------------------------------- */
 int gdsp_binarize     (double* d_v, uint32_t n, double T, int tiesAbove, double one, double zero,
                        void* stream);                                 /* logical.c:216-268 */
