@@ -37,8 +37,8 @@
 
 /* ------------------------------------------------------------ operator table */
 /* same names, aliases and order as the reference's dspTable (genodsp.c:117-174): all 37
- * operators, then (with GDSP_RANK_FILTER, as the Makefile builds it) slidingpercentile and median, which the
- * reference does not have.  As in the reference a "plugin" is a link-time function group: a further group
+ * operators, then the rows of the operator groups the reference does not have (opGroups, below).  As in the
+ * reference a "plugin" is a link-time function group: a further group
  * is added by compiling the driver with -DGDSP_EXTRA_OPERATORS='"my_ops.h"', a header that
  * declares the groups (dspprototypes) and defines GDSP_EXTRA_DSPTABLE_ROWS as the rows to append
  * (dspinforecord("name", op_x), ...), and by linking the group's object file (INTEGRATION.md;
@@ -56,41 +56,11 @@ dspprototypes(op_mask)           dspprototypes(op_mask_not)      dspprototypes(o
 dspprototypes(op_and)            dspprototypes(op_min_with)      dspprototypes(op_max_with)
 dspprototypes(op_map)            dspprototypes(op_min_in_interval) dspprototypes(op_max_in_interval)
 dspprototypes(op_clump)          dspprototypes(op_skimp)
-#ifdef GDSP_RANK_FILTER                                /* not in the reference: ops_rankfilt.c */
-dspprototypes(op_sliding_percentile) dspprototypes(op_sliding_median)
-#endif
-#ifdef GDSP_GENOME_STATS                               /* not in the reference: ops_stats.c */
-dspprototypes(op_stats)          dspprototypes(op_normalize)     dspprototypes(op_multiply_constant)
-dspprototypes(op_divide_constant)
-#endif
-#ifdef GDSP_INTERVAL_STATS                             /* not in the reference: ops_statsover.c */
-dspprototypes(op_statsover)
-#endif
-#ifdef GDSP_HISTOGRAM                                  /* not in the reference: ops_histogram.c */
-dspprototypes(op_histogram)
-#endif
-#ifdef GDSP_CORRELATE                                  /* not in the reference: ops_correlate.c */
-dspprototypes(op_correlate)
-#endif
-#ifdef GDSP_LAGCORR                                    /* not in the reference: ops_lagcorr.c */
-dspprototypes(op_crosscorrelate)
-dspprototypes(op_autocorrelate)
-#endif
-#ifdef GDSP_SEGMENTS                                   /* not in the reference: ops_segments.c, ops_keepsegments.c */
-dspprototypes(op_segments)
-dspprototypes(op_keepsegments)
-#endif
-#ifdef GDSP_PROMINENCE                                 /* not in the reference: ops_prominence.c */
-dspprototypes(op_prominence)
-#endif
-#ifdef GDSP_LOCALSTATS                                 /* not in the reference: ops_localstats.c */
-dspprototypes(op_localstats)
-#endif
 #ifdef GDSP_EXTRA_OPERATORS
 #include GDSP_EXTRA_OPERATORS
 #endif
 
-static dspinfo dspTable[] =
+static const dspinfo dspTable[] =
 	{dspinforecord("sum"           , op_window_sum)     , dspinfoalias ("window_sum")     ,
 	 dspinforecord("slidingsum"    , op_sliding_sum)    , dspinfoalias ("sliding_sum")    ,
 	 dspinforecord("smooth"        , op_smooth)         ,
@@ -130,50 +100,57 @@ static dspinfo dspTable[] =
 	 dspinforecord("input"         , op_input)          ,
 	 dspinforecord("output"        , op_output)         ,
 	 dspinforecord("variables"     , op_show_variables)
-#ifdef GDSP_RANK_FILTER                                /* windowed order statistics, after the reference's 37 */
-	 , dspinforecord("slidingpercentile", op_sliding_percentile), dspinfoalias ("sliding_percentile"),
-	 dspinforecord("median"        , op_sliding_median) , dspinfoalias ("slidingmedian")  , dspinfoalias ("sliding_median")
-#endif
-#ifdef GDSP_GENOME_STATS                               /* genome-wide figures and scaling by them, after the reference's 37 */
-	 , dspinforecord("stats"       , op_stats)          ,
-	 dspinforecord("normalize"     , op_normalize)      ,
-	 dspinforecord("multiplyconst" , op_multiply_constant), dspinfoalias ("multiply_const"), dspinfoalias ("scale"),
-	 dspinforecord("divideconst"   , op_divide_constant), dspinfoalias ("divide_const")
-#endif
-#ifdef GDSP_INTERVAL_STATS                             /* the signal quantified over the intervals of a file, after those */
-	 , dspinforecord("statsover"   , op_statsover)      , dspinfoalias ("stats_over")     , dspinfoalias ("intervalstats"),
-	 dspinfoalias ("interval_stats")
-#endif
-#ifdef GDSP_HISTOGRAM                                  /* the genome-wide distribution of the values, after those */
-	 , dspinforecord("histogram"   , op_histogram)      , dspinfoalias ("hist")           , dspinfoalias ("distribution")
-#endif
-#ifdef GDSP_CORRELATE                                  /* the signal against a second track, after that */
-	 , dspinforecord("correlate"   , op_correlate)      , dspinfoalias ("correlation")    , dspinfoalias ("pearson")
-	 , dspinfoalias ("covariance")
-#endif
-#ifdef GDSP_LAGCORR                                    /* the same at every lag of a range, and the signal against itself */
-	 , dspinforecord("crosscorrelate", op_crosscorrelate) , dspinfoalias ("cross_correlate") , dspinfoalias ("xcorr")
-	 , dspinfoalias ("ccf")
-	 , dspinforecord("autocorrelate" , op_autocorrelate)  , dspinfoalias ("autocorrelation") , dspinfoalias ("acf")
-#endif
-#ifdef GDSP_SEGMENTS                                   /* the signal's own regions above a threshold, quantified, after those */
-	 , dspinforecord("segments"    , op_segments)       , dspinfoalias ("callpeaks")      , dspinfoalias ("call_peaks")
-	 , dspinfoalias ("islands")
-	 , dspinforecord("keepsegments", op_keepsegments)   , dspinfoalias ("keep_segments")  , dspinfoalias ("hysteresis")
-	 , dspinfoalias ("paintsegments")
-#endif
-#ifdef GDSP_PROMINENCE                                 /* how far each base stands above its surroundings, after those */
-	 , dspinforecord("prominence"  , op_prominence)     , dspinfoalias ("peakprominence")
-#endif
-#ifdef GDSP_LOCALSTATS                                 /* each base against the window around it, between those and `stats` */
-	 , dspinforecord("localstats"  , op_localstats)     , dspinfoalias ("local_stats")    , dspinfoalias ("localzscore")
-	 , dspinfoalias ("localbackground")
-#endif
-#ifdef GDSP_EXTRA_DSPTABLE_ROWS
-	 , GDSP_EXTRA_DSPTABLE_ROWS
-#endif
 	};
 #define dspTableLen (sizeof(dspTable)/sizeof(dspinfo))
+
+/* the groups the reference does not have, in the order of their rows: each is defined in the ops_*.c that owns it and is
+ * absent (NULL) from a build whose source list leaves that file out */
+extern const opgroup opgroup_rankfilt   __attribute__((weak));      /* windowed order statistics */
+extern const opgroup opgroup_stats      __attribute__((weak));      /* genome-wide figures and scaling by them */
+extern const opgroup opgroup_statsover  __attribute__((weak));      /* the signal quantified over the intervals of a file */
+extern const opgroup opgroup_histogram  __attribute__((weak));      /* the genome-wide distribution of the values */
+extern const opgroup opgroup_correlate  __attribute__((weak));      /* the signal against a second track */
+extern const opgroup opgroup_lagcorr    __attribute__((weak));      /* the same at every lag of a range, and against itself */
+extern const opgroup opgroup_segments   __attribute__((weak));      /* the signal's own regions above a threshold */
+extern const opgroup opgroup_prominence __attribute__((weak));      /* how far each base stands above its surroundings */
+extern const opgroup opgroup_localstats __attribute__((weak));      /* each base against the window around it */
+static const opgroup* const opGroups[] =
+	{ &opgroup_rankfilt, &opgroup_stats, &opgroup_statsover, &opgroup_histogram, &opgroup_correlate, &opgroup_lagcorr,
+	  &opgroup_segments, &opgroup_prominence, &opgroup_localstats };
+#define numOpGroups ((int) (sizeof(opGroups)/sizeof(opGroups[0])))
+
+#ifdef GDSP_EXTRA_DSPTABLE_ROWS
+static const dspinfo extraRows[] = { GDSP_EXTRA_DSPTABLE_ROWS };
+#define numExtraRows (sizeof(extraRows)/sizeof(dspinfo))
+#endif
+
+/* row i of the whole table -- the reference's rows, the groups', the linked-in ones last -- or NULL behind its end */
+static const dspinfo* table_row (u32 i)
+	{
+	if (i < dspTableLen) return &dspTable[i];
+	i -= dspTableLen;
+	for (int g=0 ; g<numOpGroups ; g++)
+		{
+		if (opGroups[g] == NULL) continue;
+		if (i < (u32) opGroups[g]->nrows) return &opGroups[g]->rows[i];
+		i -= opGroups[g]->nrows;
+		}
+#ifdef GDSP_EXTRA_DSPTABLE_ROWS
+	if (i < numExtraRows) return &extraRows[i];
+#endif
+	return NULL;
+	}
+
+const optraits* traits_of (dspop* op)
+	{
+	for (int i=0 ; i<coreTraitsLen ; i++) { if (coreTraits[i].apply == op->funcApply) return &coreTraits[i]; }
+	for (int g=0 ; g<numOpGroups ; g++)
+		{
+		if (opGroups[g] == NULL) continue;
+		for (int i=0 ; i<opGroups[g]->ntraits ; i++) { if (opGroups[g]->traits[i].apply == op->funcApply) return &opGroups[g]->traits[i]; }
+		}
+	return NULL;
+	}
 
 static const char* notInThisBuild[] = { NULL };    /* every operator of the reference's table is built */
 
@@ -326,18 +303,19 @@ void chastise (const char* format, ...)          /* genodsp.c:193-209 */
 static void usage_operations (void)
 	{
 	fprintf (stderr, "Operations (general form is %c <operator> [arguments]):\n", specialPipeChar);
-	for (u32 i=0 ; i<dspTableLen ; i++)
-		{ if (dspTable[i].funcShort != NULL) (*dspTable[i].funcShort) (dspTable[i].name, 12, stderr, "  "); }
+	const dspinfo* row;
+	for (u32 i=0 ; (row=table_row(i))!=NULL ; i++)
+		{ if (row->funcShort != NULL) (*row->funcShort) (row->name, 12, stderr, "  "); }
 	exit (EXIT_FAILURE);
 	}
 
-static dspinfo* find_operator (const char* name)  /* alias rows resolve to the row above, genodsp.c:666-673 */
+static const dspinfo* find_operator (const char* name)  /* alias rows resolve to the row above, genodsp.c:666-673 */
 	{
-	dspinfo* real = NULL;
-	for (u32 i=0 ; i<dspTableLen ; i++)
+	const dspinfo* real = NULL, *row;
+	for (u32 i=0 ; (row=table_row(i))!=NULL ; i++)
 		{
-		if (dspTable[i].funcShort != NULL) real = &dspTable[i];
-		if (strcmp (name, dspTable[i].name) == 0) return real;
+		if (row->funcShort != NULL) real = row;
+		if (strcmp (name, row->name) == 0) return real;
 		}
 	return NULL;
 	}
@@ -670,18 +648,13 @@ static void ensure_device_comm (void)
 		}
 	check_gdsp (rc, "create the RCCL communicator");
 	check_gdsp (gdsp_percentiles_use_comm (deviceComm), "hand the communicator to percentile");
-#ifdef GDSP_GENOME_STATS
-	check_gdsp (gdsp_genome_stats_use_comm (deviceComm), "hand the communicator to stats");
-#endif
-#ifdef GDSP_HISTOGRAM
-	check_gdsp (gdsp_genome_histogram_use_comm (deviceComm), "hand the communicator to histogram");
-#endif
-#ifdef GDSP_CORRELATE
-	check_gdsp (gdsp_genome_correlation_use_comm (deviceComm), "hand the communicator to correlate");
-#endif
-#ifdef GDSP_LAGCORR
-	check_gdsp (gdsp_genome_lag_correlation_use_comm (deviceComm), "hand the communicator to crosscorrelate");
-#endif
+	for (int g=0 ; g<numOpGroups ; g++)
+		{
+		if ((opGroups[g] == NULL) || (opGroups[g]->useComm == NULL)) continue;
+		char what[160];
+		snprintf (what, sizeof(what), "hand the communicator to %s", opGroups[g]->rows[0].name);
+		check_gdsp ((*opGroups[g]->useComm) (deviceComm), what);
+		}
 	if (trackOperations)
 		{
 		int version = 0;
@@ -894,40 +867,17 @@ static void ensure_partners (void)
 	partnersPlanned = partnersReady = partnersSeen = true;
 	}
 
-/* does the parsed pipeline hold an operator that writes into a partner?  The built-in in-place operators are named;
- * anything else (the out-of-place ones, operators linked in through GDSP_EXTRA_OPERATORS) counts as wanting one */
+/* does the parsed pipeline hold an operator that writes into a partner?  Those that say they work in place do not; anything
+ * else (the out-of-place ones, operators nobody described: those linked in through GDSP_EXTRA_OPERATORS) counts as wanting one */
 static int pipeline_wants_partners (void)
 	{
-	static const opfunc_apply inPlace[] =
-		{ op_window_sum_apply, op_cumulative_sum_apply, op_add_apply, op_subtract_apply, op_add_constant_apply, op_invert_apply,
-		  op_multiply_apply, op_divide_apply, op_absolute_value_apply, op_clip_apply, op_erase_apply, op_binarize_apply,
-		  op_input_apply, op_output_apply, op_show_variables_apply, op_mask_apply, op_mask_not_apply, op_or_apply, op_and_apply,
-		  op_min_with_apply, op_max_with_apply, op_map_apply, op_min_in_interval_apply, op_max_in_interval_apply,
-		  op_clump_apply, op_skimp_apply,
-#ifdef GDSP_GENOME_STATS
-		  op_stats_apply, op_normalize_apply, op_multiply_constant_apply, op_divide_constant_apply,
-#endif
-#ifdef GDSP_INTERVAL_STATS
-		  op_statsover_apply,
-#endif
-#ifdef GDSP_HISTOGRAM
-		  op_histogram_apply,
-#endif
-#ifdef GDSP_LAGCORR
-		  op_autocorrelate_apply,                                  /* (the signal against itself: no partner is touched) */
-#endif
-#ifdef GDSP_SEGMENTS
-		  op_segments_apply,
-#endif
-		};
 	if (shardBases) return true;                               /* (stretches and their runs: not worth a second rule) */
 	for (dspop* op=pipeline ; op!=NULL ; op=op->next)
 		{
-		int known = false;
-		for (size_t i=0 ; i<sizeof(inPlace)/sizeof(inPlace[0]) ; i++) { if (op->funcApply == inPlace[i]) known = true; }
-		if (op->funcApply == op_percentile_apply)                  /* (fused with the binarize behind it, it writes partners) */
-			known = !(fuseChains && (op->next != NULL) && (op->next->funcApply == op_binarize_apply));
-		if (!known) return true;
+		const optraits* t = traits_of (op);
+		if ((t == NULL) || !t->inPlace) return true;
+		if ((op->funcApply == op_percentile_apply)                 /* (fused with the binarize behind it, it writes partners) */
+		 && fuseChains && (op->next != NULL) && (op->next->funcApply == op_binarize_apply)) return true;
 		}
 	return false;
 	}
@@ -1823,7 +1773,7 @@ static int process_operator_options (int argc, char** argv)    /* genodsp.c:634-
 	else dspName = skip_whitespace (arg+1);
 	if (dbgPipe) fprintf (stderr, "  dspName=\"%s\"\n", dspName);
 
-	dspinfo* info = find_operator (dspName);
+	const dspinfo* info = find_operator (dspName);
 	if (info == NULL)
 		{
 		for (int i=0 ; notInThisBuild[i]!=NULL ; i++)
@@ -1863,7 +1813,7 @@ static int process_operator_options (int argc, char** argv)    /* genodsp.c:634-
 
 static void help_for (char* name)
 	{
-	dspinfo* info = find_operator (name);
+	const dspinfo* info = find_operator (name);
 	if (info == NULL) { fprintf (stderr, "\"%s\" is not a known operation\n", name);  exit (EXIT_FAILURE); }
 	fprintf (stderr, "=== %s ===\n", info->name);
 	(*info->funcUsage) (info->name, stderr, "  ");
@@ -1969,12 +1919,15 @@ static void parse_options (int _argc, char** _argv)            /* genodsp.c:284-
 		if (strcmp (arg, "--help") == 0)
 			{
 		help_for_all:
-			for (u32 i=0 ; i<dspTableLen ; i++)
+			{
+			const dspinfo* row;
+			for (u32 i=0 ; (row=table_row(i))!=NULL ; i++)
 				{
-				if (dspTable[i].funcShort == NULL) continue;
-				fprintf (stderr, "=== %s ===\n", dspTable[i].name);
-				(*dspTable[i].funcUsage) (dspTable[i].name, stderr, "  ");
+				if (row->funcShort == NULL) continue;
+				fprintf (stderr, "=== %s ===\n", row->name);
+				(*row->funcUsage) (row->name, stderr, "  ");
 				}
+			}
 			exit (EXIT_SUCCESS);
 			}
 		if ((strcmp (arg, "--report=comments") == 0) || (strcmp (arg, "--report:comments") == 0))
@@ -2168,14 +2121,8 @@ int main (int argc, char** argv)
 		else
 			{
 			if (trackOperations) tracking_report ("%s(*)\n", stopOp->name);
-			int onParts = (stopOp->funcApply == op_percentile_apply) || (stopOp->funcApply == op_invert_apply)
-			           || (stopOp->funcApply == op_show_variables_apply);
-#ifdef GDSP_GENOME_STATS
-			if (op_stats_is_stop (stopOp)) onParts = true;           /* (normalize rewrites halo and owner alike) */
-#endif
-#ifdef GDSP_HISTOGRAM
-			if (op_histogram_is_stop (stopOp)) onParts = true;       /* (reads the parts as they are, each with its `first`) */
-#endif
+			const optraits* traits = traits_of (stopOp);
+			int onParts = (traits != NULL) && traits->onParts;
 			if (!onParts) to_whole ();                         /* file-driven operators address whole chromosomes */
 			double t0 = now_ms ();
 			u64 ivBefore = intervalsRead;
@@ -2195,10 +2142,12 @@ int main (int argc, char** argv)
 				for (int i=0 ; chromsSorted[i]!=NULL ; i++) total += chromsSorted[i]->length;
 				sync_all_devices ();
 				if (stopOp->funcApply == op_show_variables_apply) ;
-#ifdef GDSP_INTERVAL_STATS
-				else if (op_statsover_is (stopOp))                 /* 8 B per base of interval length */
-					wall_phase (stopOp, stopOp->name, now_ms () - t0, op_statsover_bases (stopOp), "bases", 8);
-#endif
+				else if ((traits != NULL) && (traits->work != NULL))
+					{
+					u64 bases = total;  double bpb = 16;
+					(*traits->work) (stopOp, &bases, &bpb);
+					wall_phase (stopOp, stopOp->name, now_ms () - t0, bases, "bases", bpb);
+					}
 				else if ((intervalsRead != ivBefore) && (stopOp->funcApply != op_percentile_apply))
 					{
 					char label[160];
@@ -2206,21 +2155,7 @@ int main (int argc, char** argv)
 					wall_phase (stopOp, label, now_ms () - t0, intervalsRead - ivBefore, "intervals", 0);
 					}
 				else if (ran == 2) wall_phase (stopOp, "percentile=binarize", now_ms () - t0, total, "bases", 24);
-				else
-					{
-					double bpb = (stopOp->funcApply == op_percentile_apply)? 8 : 16;
-#ifdef GDSP_GENOME_STATS
-					if (op_stats_is_stop (stopOp)) bpb = op_stats_is_normalize (stopOp)? 32 : 16;   /* 8 B/base per stats pass */
-#endif
-#ifdef GDSP_HISTOGRAM
-					if (op_histogram_is_stop (stopOp)) bpb = 8;              /* one read of the signal */
-#endif
-#ifdef GDSP_SEGMENTS
-					if (op_segments_is (stopOp)) bpb = 8;                    /* one read of the signal (and of the tiles that hold regions) */
-					if (op_keepsegments_is (stopOp)) bpb = op_keepsegments_copies (stopOp)? 24 : 16;   /* that read, a store per base, and the signal again inside the regions */
-#endif
-					wall_phase (stopOp, stopOp->name, now_ms () - t0, total, "bases", bpb);
-					}
+				else wall_phase (stopOp, stopOp->name, now_ms () - t0, total, "bases", (stopOp->funcApply == op_percentile_apply)? 8 : 16);
 				}
 			firstOp = (ran == 2)? stopOp->next->next : stopOp->next;
 			}
@@ -2248,19 +2183,12 @@ int main (int argc, char** argv)
 
 	for (dspop* op=pipeline, *next ; op!=NULL ; op=next)
 		{ next = op->next;  free (op->name);  (*op->funcFree) (op); }
-#ifdef GDSP_GENOME_STATS
-	if (deviceComm != NULL) gdsp_genome_stats_use_comm (NULL);
-#endif
-#ifdef GDSP_HISTOGRAM
-	if (deviceComm != NULL) gdsp_genome_histogram_use_comm (NULL);
-#endif
-#ifdef GDSP_CORRELATE
-	if (deviceComm != NULL) gdsp_genome_correlation_use_comm (NULL);
-#endif
-#ifdef GDSP_LAGCORR
-	if (deviceComm != NULL) gdsp_genome_lag_correlation_use_comm (NULL);
-#endif
-	if (deviceComm != NULL) { gdsp_percentiles_use_comm (NULL);  gdsp_comm_destroy (deviceComm); }
+	if (deviceComm != NULL)
+		{
+		for (int g=0 ; g<numOpGroups ; g++) { if ((opGroups[g] != NULL) && (opGroups[g]->useComm != NULL)) (*opGroups[g]->useComm) (NULL); }
+		gdsp_percentiles_use_comm (NULL);
+		gdsp_comm_destroy (deviceComm);
+		}
 	return EXIT_SUCCESS;
 	}
 

@@ -44,6 +44,7 @@ double now_ms (void);                          /* the monotonic clock, in millis
 void* new_op           (char* name, size_t bytes, int atRandom);   /* zeroed control record */
 void* must_alloc       (void* p, const char* name);                /* p, or the run ends with "out of memory" when it is NULL */
 int   origin_opt_take  (char* arg, int* originOne);                /* --origin=one|1|zero|0 */
+int   value_column_take (char* name, char* arg, int* valColumn);   /* --value=<col>, --novalue, --novalues, --value=none */
 u32   window_arg       (char* name, char* arg, char* argVal, const char* what);
 /* "--x=<value|variable>": number now, or a named variable resolved at first apply */
 void  value_or_variable (char* argVal, valtype* val, char** varName);
@@ -74,6 +75,7 @@ char* put_interval_figures (char* p, const gdsp_interval_stat* stat, u32 chromSt
 int   try_fused_apply   (dspop* op, dspop* stopOp, spec* s);
 /* one launch per operator per device (see ops_fused.c) */
 int   op_batchable          (dspop* op);
+int   op_reach              (dspop* op, u32* left, u32* right);    /* the operator's reach (optraits), false: none */
 int   batch_apply_on_device (dspop* op, dspop* stopOp, spec** units, int nunits, int allowFusion);
 valtype* partner_of    (spec* s);              /* the second HBM buffer of a chromosome or stretch */
 void     flip_spec     (spec* s);              /* swap vector and partner */
@@ -83,10 +85,6 @@ valtype op_add_constant_value (dspop* op);
 u32   op_smooth_window    (dspop* op);
 u32   op_best_window      (dspop* op);
 void  op_morph_reach      (dspop* op, u32* left, u32* right);
-/* --sharding=bases: true when output i of this per-chromosome operator depends on inputs [i-left, i+right] only
- * and not on where i lies in the vector (so a stretch of a chromosome with that much halo computes what the whole
- * chromosome would); false for running sums, window grids and clump, which need the chromosome in one piece */
-int   op_reach            (dspop* op, u32* left, u32* right);
 void  op_local_describe   (dspop* op, u32* neighborhood, int* wantMax, valtype* fill);
 void  op_morph_describe   (dspop* op, u32* left, u32* right, valtype* T, valtype* one, valtype* zero);
 void  op_binarize_describe (dspop* op, valtype* T, int* tiesAbove, valtype* one, valtype* zero);
@@ -97,32 +95,38 @@ int   percentile_with_binarize (dspop* percentile, dspop* next);
 
 /* ops_percentile.c: a percentile as given on the command line -> thousandths of a percent (0 .. 100000) */
 u32   to_thousandths      (valtype pct);
-/* ops_rankfilt.c (slidingpercentile, median; compiled in with -DGDSP_RANK_FILTER): what ops_fused.c needs to know */
-int   op_rankfilt_is      (dspop* op);
-u32   op_rankfilt_window  (dspop* op);
-int   op_rankfilt_batch   (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
-/* ops_prominence.c (prominence; compiled in with -DGDSP_PROMINENCE): likewise */
-int   op_prominence_is     (dspop* op);
-u32   op_prominence_window (dspop* op);
-int   op_prominence_batch  (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
-/* ops_localstats.c (localstats; compiled in with -DGDSP_LOCALSTATS): likewise */
-int   op_localstats_is     (dspop* op);
-u32   op_localstats_window (dspop* op);
-int   op_localstats_batch  (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
-/* ops_stats.c (stats, normalize, multiplyconst, divideconst; compiled in with -DGDSP_GENOME_STATS) */
-int   op_const_is         (dspop* op);       /* multiplyconst / divideconst: per-base, in place */
-int   op_const_batch      (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);
-int   op_stats_is_stop    (dspop* op);       /* stats / normalize: whole-genome, on the signal's parts as they are */
-int   op_stats_is_normalize (dspop* op);
-/* ops_statsover.c (statsover; compiled in with -DGDSP_INTERVAL_STATS) and what the driver lends it: the pending
- * intervals of chromsSorted[ci] as ib_add left them (ib_begin forgets them), and the report's "%.*f" (NULL: not a case
- * for the hand-rolled form, print through printf) */
-int   op_statsover_is     (dspop* op);
-u64   op_statsover_bases  (dspop* op);       /* summed length of the intervals since the last call (--report=gpu) */
-/* ops_histogram.c (histogram; compiled in with -DGDSP_HISTOGRAM) */
-int   op_histogram_is_stop (dspop* op);      /* whole-genome, on the signal's parts as they are; the signal is only read */
-/* ops_segments.c (segments; compiled in with -DGDSP_SEGMENTS) */
-int   op_segments_is      (dspop* op);       /* whole-genome, on whole chromosomes; the signal is only read */
+/* what the driver knows about an operator, said once, beside the operator, and found by its apply function (traits_of).
+ * An operator nobody described (a plugin's) gets the defaults: it may ask for a partner, needs its chromosome in one piece,
+ * has no one-launch form, and as a stop operator takes whole chromosomes and is credited the genome's bases at 16 B each */
+typedef struct optraits
+	{
+	opfunc_apply apply;            /* whose traits these are */
+	int   inPlace;                 /* never asks for a partner (a one-launch form then gets d_in NULL, d_out the vector) */
+	int   onParts;                 /* stop operator that takes the signal's parts as they are (no to_whole()) */
+	/* --sharding=bases: true when output i depends on inputs [i-left, i+right] only and not on where i lies in the vector
+	 * (so a stretch of a chromosome with that much halo computes what the whole chromosome would); NULL for running
+	 * sums, window grids and clump, which need the chromosome in one piece */
+	int   (*reach) (dspop* op, u32* left, u32* right);
+	int   (*batch) (dspop* op, const gdsp_batch_item* items, int nitems, void* stream);   /* one launch per device; NULL: none */
+	/* --report=gpu, stop operators: bytes per base, and the bases when they are not the genome's; NULL: 16 */
+	void  (*work)  (dspop* op, u64* bases, double* bytesPerBase);
+	} optraits;
+/* an operator group beyond the reference's: its rows of the operator table (aliases included), its operators' traits, and
+ * where its library half takes the RCCL communicator (NULL: it reduces nothing).  Each group is defined in its own
+ * ops_*.c; the driver holds weak references to them, so a build from a shorter source list simply lacks the group */
+typedef struct opgroup
+	{
+	const dspinfo*  rows;    int nrows;
+	const optraits* traits;  int ntraits;
+	int (*useComm) (gdsp_comm* comm);
+	} opgroup;
+#define OPGROUP(rows, traits, useComm) \
+	{ rows, (int) (sizeof(rows)/sizeof(rows[0])), traits, (int) (sizeof(traits)/sizeof(traits[0])), useComm }
+const optraits* traits_of (dspop* op);        /* NULL: nobody described it */
+extern const optraits coreTraits[];           /* ops_fused.c: the reference's operators */
+extern const int      coreTraitsLen;
+int   reach_none    (dspop* op, u32* left, u32* right);   /* per-base operators: 0, 0 */
+int   reach_centred (u32 W, u32* left, u32* right);       /* bestmax's window: (W-1)/2 left, the rest right */
 /* what segments and keepsegments (ops_keepsegments.c) share: the options that select the segments and shape their
  * table, parsed in one place, and the pass itself.  take: true when `arg` was one of them; take_other: --debug, the
  * complaint about an unknown option, the threshold as a bare number.  segments_run with `paint`: every chromosome's
@@ -142,13 +146,12 @@ int   segments_opts_take       (segments_opts* o, char* name, char* arg);
 void  segments_opts_take_other (segments_opts* o, char* name, char* arg);
 void  segments_opts_free       (segments_opts* o);
 void  segments_run             (dspop* op, segments_opts* o, int wantTable, const segments_paint* paint);
-/* ops_keepsegments.c (keepsegments; with -DGDSP_SEGMENTS too) */
-int   op_keepsegments_is  (dspop* op);       /* whole-genome, on whole chromosomes; rewrites them through their partners */
-int   op_keepsegments_copies (dspop* op);    /* --as=value: the signal is read a second time, inside the kept segments */
+/* what the driver lends statsover (ops_statsover.c): the pending intervals of chromsSorted[ci] as ib_add left them
+ * (ib_begin forgets them), and the report's "%.*f" (NULL: not a case for the hand-rolled form, print through printf) */
 int   ib_chromosomes      (void);
 u32   ib_pending_of       (int ci, spec** s, u32** start, u32** end, valtype** val);
 char* put_value_fixed     (char* p, valtype v, int precision);
-/* ops_correlate.c (correlate; compiled in with -DGDSP_CORRELATE), shared with ops_lagcorr.c: the intervals of a file, read
+/* ops_correlate.c (correlate), shared with ops_lagcorr.c: the intervals of a file, read
  * by the rules of `add <file>`, into every chromosome's partner -- what `add <file>` would leave on an all-zero genome */
 void  load_track_into_partners (char* name, char* filename, int valColumn, int originOne);
 

@@ -30,6 +30,27 @@ int origin_opt_take (char* arg, int* originOne)
 	return false;
 	}
 
+/* --value=<col>, or --novalue / --novalues / --value=none, of an operator that reads a file of intervals; true: `arg`
+ * was it, and *valColumn is the column counted from 0 (-1: the intervals carry no value) */
+int value_column_take (char* name, char* arg, int* valColumn)
+	{
+	if ((strcmp (arg, "--novalue") == 0) || (strcmp (arg, "--novalues") == 0) || (strcmp (arg, "--value=none") == 0))
+		{ *valColumn = -1;  return true; }
+	if (strcmp_prefix (arg, "--value=") != 0) return false;
+	int col = string_to_int (strchr (arg, '=') + 1) - 1;
+	if (col == -1) chastise ("[%s] value column can't be 0 (\"%s\")\n", name, arg);
+	if (col < 0)   chastise ("[%s] value column can't be negative (\"%s\")\n", name, arg);
+	if (col < 3)   chastise ("[%s] value column can't be 1, 2 or 3 (\"%s\")\n", name, arg);
+	*valColumn = col;
+	return true;
+	}
+
+/* --sharding=bases, the reach of an operator (optraits): none for a per-base operator; for a window centred as bestmax
+ * centres its own (minmax.c:1636-1640: [i-wLft, i+wRgt]), (W-1)/2 bases to the left and the rest to the right */
+int reach_none (dspop* op, u32* left, u32* right) { *left = *right = 0;  return true; }
+
+int reach_centred (u32 W, u32* left, u32* right) { *left = (W - 1) / 2;  *right = W - 1 - *left;  return true; }
+
 /* --window=<n> and friends: zero and negatives are errors, 1-2 are raised to 3 with a
  * warning (sum.c:121-132, minmax.c:1116-1126) */
 u32 window_arg (char* name, char* arg, char* argVal, const char* what)

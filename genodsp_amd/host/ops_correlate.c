@@ -10,8 +10,8 @@
  * correlation, slope and intercept derived from them -- so what is printed does not depend on the number of devices,
  * the cut of the genome, chromosome order, the interval batches or the way the devices' images meet.
  *
- * The driver's table row and the lines that hand the communicator to the library are compiled only with
- * -DGDSP_CORRELATE (genodsp_amd/host/Makefile); every call into the device library for it stays in this file. */
+ * The driver finds this operator through opgroup_correlate, at the end of this file (host_services.h); every call into the
+ * device library for it stays here. */
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -71,17 +71,7 @@ dspop* op_correlate_parse (char* name, int argc, char** argv)
 		if (sample_opts_take (&op->sample, name, arg, SAMPLE_OPT_WINDOW | SAMPLE_OPT_QUIET | SAMPLE_OPT_PRECISION)) continue;
 		if (strcmp_prefix (arg, "--filemin=") == 0) { op->fileMin = string_to_valtype (argVal);  continue; }
 		if (strcmp_prefix (arg, "--filemax=") == 0) { op->fileMax = string_to_valtype (argVal);  continue; }
-		if ((strcmp (arg, "--novalue") == 0) || (strcmp (arg, "--novalues") == 0) || (strcmp (arg, "--value=none") == 0))
-			{ op->valColumn = -1;  continue; }
-		if (strcmp_prefix (arg, "--value=") == 0)
-			{
-			int col = string_to_int (argVal) - 1;
-			if (col == -1) chastise ("[%s] value column can't be 0 (\"%s\")\n", name, arg);
-			if (col < 0)   chastise ("[%s] value column can't be negative (\"%s\")\n", name, arg);
-			if (col < 3)   chastise ("[%s] value column can't be 1, 2 or 3 (\"%s\")\n", name, arg);
-			op->valColumn = col;
-			continue;
-			}
+		if (value_column_take (name, arg, &op->valColumn)) continue;
 		if (origin_opt_take (arg, &op->originOne)) continue;
 		if ((strcmp (arg, "--report:bash") == 0) || (strcmp (arg, "--bash") == 0)) { op->reportForBash = true;  continue; }
 		if (strcmp_prefix (arg, "--debug") == 0) continue;
@@ -185,3 +175,8 @@ void op_correlate_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_co
 	if (fig[GDSP_CORR_COUNT] == 0)
 		fprintf (stderr, "[%s] nothing can be computed;  no input values meet the criteria\n", name);
 	}
+
+/* the driver: no traits of its own (the track is built in the partners; it is a file-driven operator on whole chromosomes) */
+static const dspinfo correlateRows[] =
+	{ dspinforecord("correlate", op_correlate), dspinfoalias ("correlation"), dspinfoalias ("pearson"), dspinfoalias ("covariance") };
+const opgroup opgroup_correlate = { correlateRows, (int) (sizeof(correlateRows)/sizeof(correlateRows[0])), NULL, 0, gdsp_genome_correlation_use_comm };

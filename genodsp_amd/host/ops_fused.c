@@ -13,43 +13,99 @@
 #include "utilities.h"
 #include "host_services.h"
 
-dspprototypes(op_smooth)  dspprototypes(op_local_minima)  dspprototypes(op_local_maxima)
-dspprototypes(op_dilate)  dspprototypes(op_erode)         dspprototypes(op_binarize)
+dspprototypes(op_window_sum)     dspprototypes(op_smooth)        dspprototypes(op_cumulative_sum)
+dspprototypes(op_percentile)     dspprototypes(op_add)           dspprototypes(op_subtract)
+dspprototypes(op_add_constant)   dspprototypes(op_invert)        dspprototypes(op_multiply)
+dspprototypes(op_divide)         dspprototypes(op_absolute_value) dspprototypes(op_clip)
+dspprototypes(op_erase)          dspprototypes(op_binarize)      dspprototypes(op_local_minima)
+dspprototypes(op_local_maxima)   dspprototypes(op_best_local_min) dspprototypes(op_best_local_max)
+dspprototypes(op_close)          dspprototypes(op_open)          dspprototypes(op_dilate)
+dspprototypes(op_erode)          dspprototypes(op_input)         dspprototypes(op_output)
+dspprototypes(op_show_variables) dspprototypes(op_mask)          dspprototypes(op_mask_not)
+dspprototypes(op_or)             dspprototypes(op_and)           dspprototypes(op_min_with)
+dspprototypes(op_max_with)       dspprototypes(op_map)           dspprototypes(op_min_in_interval)
+dspprototypes(op_max_in_interval) dspprototypes(op_clump)        dspprototypes(op_skimp)
 
-dspprototypes(op_best_local_min)  dspprototypes(op_best_local_max)  dspprototypes(op_close)  dspprototypes(op_open)
-dspprototypes(op_clip)  dspprototypes(op_erase)  dspprototypes(op_add_constant)  dspprototypes(op_absolute_value)  dspprototypes(op_map)
+/* ---- what the driver knows about the reference's operators (optraits, host_services.h); slidingsum has nothing to say */
+static int smooth_reach (dspop* op, u32* left, u32* right)             /* sum.c:647-663: taps -h..+h */
+	{ *left = *right = (op_smooth_window (op) - 1) / 2;  return true; }
+static int local_reach (dspop* op, u32* left, u32* right)              /* minmax.c:1195-1216 */
+	{ u32 N;  int wantMax;  valtype fill;  op_local_describe (op, &N, &wantMax, &fill);  *left = *right = (N - 1) / 2;  return true; }
+static int best_reach (dspop* op, u32* left, u32* right) { return reach_centred (op_best_window (op), left, right); }
+static int morph_reach (dspop* op, u32* left, u32* right) { op_morph_reach (op, left, right);  return (*left != u32Max); }
+
+/* one launch per device; GDSP_EINVAL from the extrema and the morphology: no tiled kernel takes this window */
+static int smooth_batch (dspop* op, const gdsp_batch_item* items, int n, void* st)
+	{ return gdsp_smooth_batch (items, n, op_smooth_window (op), firMode, st); }
+static int local_batch (dspop* op, const gdsp_batch_item* items, int n, void* st)
+	{ u32 N;  int wantMax;  valtype fill;  op_local_describe (op, &N, &wantMax, &fill);  return gdsp_local_extrema_batch (items, n, N, wantMax, fill, st); }
+static int best_batch (dspop* op, const gdsp_batch_item* items, int n, void* st)
+	{ return gdsp_best_extrema_batch (items, n, op_best_window (op), op->funcApply == op_best_local_max_apply, st); }
+static int morph_batch (dspop* op, const gdsp_batch_item* items, int n, void* st)
+	{
+	u32 l, r;  valtype T, one, zero;
+	op_morph_describe (op, &l, &r, &T, &one, &zero);
+	return (op->funcApply == op_dilate_apply)? gdsp_dilate_batch (items, n, l, r, T, one, zero, st)
+	                                         : gdsp_erode_batch  (items, n, l, r, T, one, zero, st);
+	}
+static int binarize_batch (dspop* op, const gdsp_batch_item* items, int n, void* st)
+	{ valtype T, one, zero;  int ties;  op_binarize_describe (op, &T, &ties, &one, &zero);  return gdsp_binarize_batch (items, n, T, ties, one, zero, st); }
+static int limits_batch (dspop* op, const gdsp_batch_item* items, int n, void* st)
+	{
+	int haveMin, haveMax, keepInside;  valtype lo, hi, zero;
+	op_limits_describe (op, &haveMin, &lo, &haveMax, &hi, &keepInside, &zero);
+	return (op->funcApply == op_clip_apply)? gdsp_clip_batch  (items, n, haveMin, lo, haveMax, hi, st)
+	                                       : gdsp_erase_batch (items, n, haveMin, lo, haveMax, hi, keepInside, zero, st);
+	}
+static int add_constant_batch (dspop* op, const gdsp_batch_item* items, int n, void* st)
+	{ return gdsp_add_constant_batch (items, n, op_add_constant_value (op), st); }
+static int abs_batch (dspop* op, const gdsp_batch_item* items, int n, void* st) { return gdsp_abs_batch (items, n, st); }
+
+const optraits coreTraits[] =
+	{ /* apply                    inPlace onParts reach         batch               work */
+	{ op_window_sum_apply,        true,  false, NULL,         NULL,               NULL },
+	{ op_smooth_apply,            false, false, smooth_reach, smooth_batch,       NULL },
+	{ op_cumulative_sum_apply,    true,  false, NULL,         NULL,               NULL },
+	{ op_clump_apply,             true,  false, NULL,         NULL,               NULL },
+	{ op_skimp_apply,             true,  false, NULL,         NULL,               NULL },
+	{ op_percentile_apply,        true,  true,  NULL,         NULL,               NULL },   /* (but see percentile = binarize) */
+	{ op_add_apply,               true,  false, NULL,         NULL,               NULL },
+	{ op_subtract_apply,          true,  false, NULL,         NULL,               NULL },
+	{ op_add_constant_apply,      true,  false, reach_none,   add_constant_batch, NULL },
+	{ op_invert_apply,            true,  true,  NULL,         NULL,               NULL },
+	{ op_multiply_apply,          true,  false, NULL,         NULL,               NULL },
+	{ op_divide_apply,            true,  false, NULL,         NULL,               NULL },
+	{ op_absolute_value_apply,    true,  false, reach_none,   abs_batch,          NULL },
+	{ op_mask_apply,              true,  false, NULL,         NULL,               NULL },
+	{ op_mask_not_apply,          true,  false, NULL,         NULL,               NULL },
+	{ op_clip_apply,              true,  false, reach_none,   limits_batch,       NULL },
+	{ op_erase_apply,             true,  false, reach_none,   limits_batch,       NULL },
+	{ op_binarize_apply,          true,  false, reach_none,   binarize_batch,     NULL },
+	{ op_or_apply,                true,  false, NULL,         NULL,               NULL },
+	{ op_and_apply,               true,  false, NULL,         NULL,               NULL },
+	{ op_max_in_interval_apply,   true,  false, NULL,         NULL,               NULL },
+	{ op_min_in_interval_apply,   true,  false, NULL,         NULL,               NULL },
+	{ op_local_minima_apply,      false, false, local_reach,  local_batch,        NULL },
+	{ op_local_maxima_apply,      false, false, local_reach,  local_batch,        NULL },
+	{ op_best_local_min_apply,    false, false, best_reach,   best_batch,         NULL },
+	{ op_best_local_max_apply,    false, false, best_reach,   best_batch,         NULL },
+	{ op_min_with_apply,          true,  false, NULL,         NULL,               NULL },
+	{ op_max_with_apply,          true,  false, NULL,         NULL,               NULL },
+	{ op_close_apply,             false, false, morph_reach,  NULL,               NULL },
+	{ op_open_apply,              false, false, morph_reach,  NULL,               NULL },
+	{ op_dilate_apply,            false, false, morph_reach,  morph_batch,        NULL },
+	{ op_erode_apply,             false, false, morph_reach,  morph_batch,        NULL },
+	{ op_map_apply,               true,  false, reach_none,   NULL,               NULL },
+	{ op_input_apply,             true,  false, NULL,         NULL,               NULL },
+	{ op_output_apply,            true,  false, NULL,         NULL,               NULL },
+	{ op_show_variables_apply,    true,  true,  NULL,         NULL,               NULL } };
+const int coreTraitsLen = (int) (sizeof(coreTraits)/sizeof(coreTraits[0]));
 
 int op_reach (dspop* op, u32* left, u32* right)
 	{
-	opfunc_apply f = op->funcApply;
+	const optraits* t = traits_of (op);
 	*left = *right = 0;
-	if (f == op_smooth_apply)                              /* sum.c:647-663: taps -h..+h */
-		{ *left = *right = (op_smooth_window (op) - 1) / 2;  return true; }
-	if ((f == op_local_maxima_apply) || (f == op_local_minima_apply))      /* minmax.c:1195-1216 */
-		{ u32 N;  int wantMax;  valtype fill;  op_local_describe (op, &N, &wantMax, &fill);  *left = *right = (N - 1) / 2;  return true; }
-	if ((f == op_best_local_max_apply) || (f == op_best_local_min_apply))  /* minmax.c:1636-1640: [i-wLft, i+wRgt] */
-		{ u32 W = op_best_window (op);  *left = (W - 1) / 2;  *right = W - 1 - *left;  return true; }
-	if ((f == op_dilate_apply) || (f == op_erode_apply) || (f == op_close_apply) || (f == op_open_apply))
-		{ op_morph_reach (op, left, right);  return (*left != u32Max); }
-	if ((f == op_binarize_apply) || (f == op_clip_apply) || (f == op_erase_apply) || (f == op_add_constant_apply)
-	 || (f == op_absolute_value_apply) || (f == op_map_apply))
-		return true;
-#ifdef GDSP_GENOME_STATS
-	if (op_const_is (op)) return true;                     /* multiplyconst, divideconst */
-#endif
-#ifdef GDSP_RANK_FILTER
-	if (op_rankfilt_is (op))                               /* bestmax's window: [i-wL, i+wR] */
-		{ u32 W = op_rankfilt_window (op);  *left = (W - 1) / 2;  *right = W - 1 - *left;  return true; }
-#endif
-#ifdef GDSP_PROMINENCE
-	if (op_prominence_is (op))                             /* the same window: neither walk leaves [i-wL, i+wR] */
-		{ u32 W = op_prominence_window (op);  *left = (W - 1) / 2;  *right = W - 1 - *left;  return true; }
-#endif
-#ifdef GDSP_LOCALSTATS
-	if (op_localstats_is (op))                             /* slidingsum's window: [c-lft, c+rgt], the longer side on the left */
-		{ u32 W = op_localstats_window (op);  *right = (W - 1) / 2;  *left = W - 1 - *right;  return true; }
-#endif
-	return false;                                          /* sum, slidingsum, cumulativesum, clump, anticlump, plugins */
+	return (t != NULL) && (t->reach != NULL) && (*t->reach) (op, left, right);
 	}
 
 int try_fused_apply (dspop* op, dspop* stopOp, spec* s)
@@ -95,133 +151,71 @@ int try_fused_apply (dspop* op, dspop* stopOp, spec* s)
  * order lets one grid cover all the vectors a device owns (no ramp and drain between 24 short kernels). */
 int op_batchable (dspop* op)
 	{
+	const optraits* t = traits_of (op);
+	return (t != NULL) && (t->batch != NULL);
+	}
+
+/* the chains the device library fuses, and a smooth that feeds an extremum (which is not evaluated as hann, fused or not:
+ * as op_smooth_apply / try_fused_apply); returns how many operators *rc speaks for, 0 when op heads no such chain */
+static int chain_batch (dspop* op, dspop* next, dspop* stopOp, const gdsp_batch_item* items, int nunits, int allowFusion, void* st, int* rc)
+	{
 	opfunc_apply f = op->funcApply;
-#ifdef GDSP_RANK_FILTER
-	if (op_rankfilt_is (op)) return true;
-#endif
-#ifdef GDSP_PROMINENCE
-	if (op_prominence_is (op)) return true;
-#endif
-#ifdef GDSP_LOCALSTATS
-	if (op_localstats_is (op)) return true;
-#endif
-#ifdef GDSP_GENOME_STATS
-	if (op_const_is (op)) return true;
-#endif
-	return (f == op_smooth_apply) || (f == op_local_maxima_apply) || (f == op_local_minima_apply)
-	    || (f == op_best_local_max_apply) || (f == op_best_local_min_apply)
-	    || (f == op_dilate_apply) || (f == op_erode_apply)
-	    || (f == op_binarize_apply) || (f == op_clip_apply) || (f == op_erase_apply)
-	    || (f == op_add_constant_apply) || (f == op_absolute_value_apply);
+	if (next == NULL) return 0;
+	if ((f == op_smooth_apply) && ((next->funcApply == op_local_maxima_apply) || (next->funcApply == op_local_minima_apply)))
+		{
+		int mode = (firMode == GDSP_FIR_HANN)? GDSP_FIR_FMA : firMode;
+		u32 N;  int wantMax;  valtype fill;
+		op_local_describe (next, &N, &wantMax, &fill);
+		if (allowFusion && gdsp_smooth_local_extrema_fusable (op_smooth_window (op), N))
+			{ *rc = gdsp_smooth_local_extrema_batch (items, nunits, op_smooth_window (op), mode, N, wantMax, fill, st);  return 2; }
+		*rc = gdsp_smooth_batch (items, nunits, op_smooth_window (op), mode, st);
+		return 1;
+		}
+	if (allowFusion && (f == op_dilate_apply) && (next->funcApply == op_erode_apply))
+		{
+		u32 l, r, el, er;  valtype T, one, zero, eT, eOne, eZero, bT = 0, bOne = 1, bZero = 0;  int bTies = false, withBinarize = false;
+		op_morph_describe (op,   &l,  &r,  &T,  &one,  &zero);
+		op_morph_describe (next, &el, &er, &eT, &eOne, &eZero);
+		if (!gdsp_dilate_erode_fusable (l, r, el, er)) return 0;     /* (a property of the reaches alone: every device decides alike) */
+		dspop* third = next->next;
+		if ((third != NULL) && (third != stopOp) && (third->funcApply == op_binarize_apply))
+			{ op_binarize_describe (third, &bT, &bTies, &bOne, &bZero);  withBinarize = true; }
+		*rc = gdsp_dilate_erode_batch (items, nunits, l, r, T, one, zero, el, er, eT, eOne, eZero,
+		                               withBinarize, bT, bTies, bOne, bZero, st);
+		return withBinarize? 3 : 2;
+		}
+	return 0;
 	}
 
 /* apply op -- and the operators fused behind it -- to units[0..nunits), all of them on the current device;
  * returns how many operators were consumed (>= 1; op must be batchable) */
 int batch_apply_on_device (dspop* op, dspop* stopOp, spec** units, int nunits, int allowFusion)
 	{
+	const optraits* t = traits_of (op);
 	opfunc_apply f = op->funcApply;
-	dspop* next = op->next;
-	if (next == stopOp) next = NULL;
 	gdsp_batch_item* items = (gdsp_batch_item*) calloc (nunits? nunits : 1, sizeof(gdsp_batch_item));
 	if (items == NULL) { fprintf (stderr, "out of memory\n");  exit (EXIT_FAILURE); }
 	/* (the in-place operators never ask for a partner: a pipeline of them alone runs without the partners' arena) */
-	int inPlace = (f == op_binarize_apply) || (f == op_clip_apply) || (f == op_erase_apply)
-	           || (f == op_add_constant_apply) || (f == op_absolute_value_apply);
-#ifdef GDSP_GENOME_STATS
-	if (op_const_is (op)) inPlace = true;
-#endif
 	for (int i=0 ; i<nunits ; i++)
-		{ items[i].d_in = units[i]->valVector;  items[i].d_out = inPlace? NULL : partner_of (units[i]);  items[i].n = units[i]->length; }
+		{
+		items[i].n = units[i]->length;
+		if (t->inPlace) { items[i].d_in = NULL;                 items[i].d_out = units[i]->valVector; }
+		else            { items[i].d_in = units[i]->valVector;  items[i].d_out = partner_of (units[i]); }
+		}
 	void* st = op_stream ();
-	int   consumed = 1, outOfPlace = true, rc = GDSP_OK;
-
-	if (f == op_smooth_apply)
+	int   rc = GDSP_OK;
+	int   consumed = chain_batch (op, (op->next == stopOp)? NULL : op->next, stopOp, items, nunits, allowFusion, st, &rc);
+	if (consumed == 0)
 		{
-		int mode = firMode;
-		int feedsLocal = (next != NULL) && ((next->funcApply == op_local_maxima_apply) || (next->funcApply == op_local_minima_apply));
-		if ((mode == GDSP_FIR_HANN) && feedsLocal) mode = GDSP_FIR_FMA;             /* as op_smooth_apply / try_fused_apply */
-		u32 N = 0;  int wantMax = 0;  valtype fill = 0;
-		if (feedsLocal) op_local_describe (next, &N, &wantMax, &fill);
-		if (allowFusion && feedsLocal && gdsp_smooth_local_extrema_fusable (op_smooth_window (op), N))
-			{ rc = gdsp_smooth_local_extrema_batch (items, nunits, op_smooth_window (op), mode, N, wantMax, fill, st);  consumed = 2; }
-		else rc = gdsp_smooth_batch (items, nunits, op_smooth_window (op), mode, st);
-		}
-	else if ((f == op_local_maxima_apply) || (f == op_local_minima_apply))
-		{
-		u32 N;  int wantMax;  valtype fill;
-		op_local_describe (op, &N, &wantMax, &fill);
-		rc = gdsp_local_extrema_batch (items, nunits, N, wantMax, fill, st);
-		if (rc == GDSP_EINVAL) goto one_by_one;              /* neighbourhood beyond one LDS tile */
-		}
-	else if ((f == op_best_local_max_apply) || (f == op_best_local_min_apply))
-		{
-		rc = gdsp_best_extrema_batch (items, nunits, op_best_window (op), f == op_best_local_max_apply, st);
-		if (rc == GDSP_EINVAL) goto one_by_one;              /* window beyond one LDS tile */
-		}
-	else if ((f == op_dilate_apply) || (f == op_erode_apply))
-		{
-		u32 l, r;  valtype T, one, zero;
-		op_morph_describe (op, &l, &r, &T, &one, &zero);
-		rc = GDSP_EINVAL;
-		if (allowFusion && (f == op_dilate_apply) && (next != NULL) && (next->funcApply == op_erode_apply))
-			{
-			u32 el, er;  valtype eT, eOne, eZero, bT = 0, bOne = 1, bZero = 0;  int bTies = false, withBinarize = false;
-			op_morph_describe (next, &el, &er, &eT, &eOne, &eZero);
-			if (gdsp_dilate_erode_fusable (l, r, el, er))          /* (a property of the reaches alone: every device decides alike) */
-				{
-				dspop* third = next->next;
-				if ((third != NULL) && (third != stopOp) && (third->funcApply == op_binarize_apply))
-					{ op_binarize_describe (third, &bT, &bTies, &bOne, &bZero);  withBinarize = true; }
-				rc = gdsp_dilate_erode_batch (items, nunits, l, r, T, one, zero, el, er, eT, eOne, eZero,
-				                              withBinarize, bT, bTies, bOne, bZero, st);
-				consumed = withBinarize? 3 : 2;
-				}
-			}
-		if ((rc == GDSP_EINVAL) && (consumed == 1))           /* not fused (or the combined reach is beyond one tile) */
-			{
-			rc = (f == op_dilate_apply)? gdsp_dilate_batch (items, nunits, l, r, T, one, zero, st)
-			                           : gdsp_erode_batch  (items, nunits, l, r, T, one, zero, st);
-			if (rc == GDSP_EINVAL) goto one_by_one;            /* reach beyond one LDS tile */
-			}
-		}
-#ifdef GDSP_RANK_FILTER
-	else if (op_rankfilt_is (op))
-		rc = op_rankfilt_batch (op, items, nunits, st);       /* (windows above the maximum were refused at parse time) */
-#endif
-#ifdef GDSP_PROMINENCE
-	else if (op_prominence_is (op))
-		rc = op_prominence_batch (op, items, nunits, st);     /* (likewise) */
-#endif
-#ifdef GDSP_LOCALSTATS
-	else if (op_localstats_is (op))
-		rc = op_localstats_batch (op, items, nunits, st);     /* (likewise) */
-#endif
-	else
-		{
-		outOfPlace = false;
-		for (int i=0 ; i<nunits ; i++) { items[i].d_in = NULL;  items[i].d_out = units[i]->valVector; }    /* in place */
-		if (f == op_binarize_apply)
-			{
-			valtype T, one, zero;  int ties;
-			op_binarize_describe (op, &T, &ties, &one, &zero);
-			rc = gdsp_binarize_batch (items, nunits, T, ties, one, zero, st);
-			}
-		else if ((f == op_clip_apply) || (f == op_erase_apply))
-			{
-			int haveMin, haveMax, keepInside;  valtype lo, hi, zero;
-			op_limits_describe (op, &haveMin, &lo, &haveMax, &hi, &keepInside, &zero);
-			rc = (f == op_clip_apply)? gdsp_clip_batch  (items, nunits, haveMin, lo, haveMax, hi, st)
-			                         : gdsp_erase_batch (items, nunits, haveMin, lo, haveMax, hi, keepInside, zero, st);
-			}
-		else if (f == op_add_constant_apply) rc = gdsp_add_constant_batch (items, nunits, op_add_constant_value (op), st);
-#ifdef GDSP_GENOME_STATS
-		else if (op_const_is (op))           rc = op_const_batch (op, items, nunits, st);
-#endif
-		else                                 rc = gdsp_abs_batch (items, nunits, st);
+		consumed = 1;
+		rc = (*t->batch) (op, items, nunits, st);
+		int tiledOnly = (f == op_local_maxima_apply) || (f == op_local_minima_apply) || (f == op_best_local_max_apply)
+		             || (f == op_best_local_min_apply) || (f == op_dilate_apply) || (f == op_erode_apply);
+		if (tiledOnly && (rc == GDSP_EINVAL)) goto one_by_one;     /* neighbourhood, window or reach beyond one LDS tile */
 		}
 	free (items);
 	check_gdsp (rc, op->name);
-	if (outOfPlace) { for (int i=0 ; i<nunits ; i++) flip_spec (units[i]); }
+	if (!t->inPlace) { for (int i=0 ; i<nunits ; i++) flip_spec (units[i]); }
 	return consumed;
 
 	/* no tiled kernel takes this window: the operator's own apply, vector by vector, which goes on to its

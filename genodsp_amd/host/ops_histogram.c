@@ -9,8 +9,8 @@
  * the way the devices' words meet (RCCL all-reduce of u64 words, or a host sum with --reduce=host).  The signal is not
  * modified; the variables count and mode are set.
  *
- * The driver's table rows and the stop-operator branches that name this operator are compiled only with
- * -DGDSP_HISTOGRAM (genodsp_amd/host/Makefile); every call into the device library for it stays in this file. */
+ * The driver finds this operator through opgroup_histogram, at the end of this file (host_services.h); every call into the
+ * device library for it stays here. */
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -203,5 +203,9 @@ void op_histogram_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_co
 	free (words);
 	}
 
-/* the driver: what it needs to know */
-int op_histogram_is_stop (dspop* op) { return op->funcApply == op_histogram_apply; }
+/* the driver: one read of the signal's parts as they are, each with its `first` */
+static void histogram_work (dspop* op, u64* bases, double* bytesPerBase) { *bytesPerBase = 8; }
+
+static const dspinfo  histogramRows[]   = { dspinforecord("histogram", op_histogram), dspinfoalias ("hist"), dspinfoalias ("distribution") };
+static const optraits histogramTraits[] = { { op_histogram_apply, true, true, NULL, NULL, histogram_work } };
+const opgroup opgroup_histogram = OPGROUP (histogramRows, histogramTraits, gdsp_genome_histogram_use_comm);

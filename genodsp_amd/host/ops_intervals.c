@@ -45,18 +45,9 @@ static dspop* fileop_parse (char* name, int argc, char** argv, int kind)
 		const int isOver = (kind == K_MINOVER) || (kind == K_MAXOVER);
 		const int isMask = (kind == K_MASK) || (kind == K_MASKNOT) || isOver;     /* no value column either */
 		const int isWith = (kind == K_MINWITH) || (kind == K_MAXWITH);
-		if (!isMask && !isWith
-		 && ((strcmp (arg, "--novalue") == 0) || (strcmp (arg, "--novalues") == 0) || (strcmp (arg, "--value=none") == 0)))
-			{ op->valColumn = -1;  continue; }
-		if (!isMask && (strcmp_prefix (arg, "--value=") == 0))
-			{
-			int col = string_to_int (argVal) - 1;
-			if (col == -1) chastise ("[%s] value column can't be 0 (\"%s\")\n", name, arg);
-			if (col < 0)   chastise ("[%s] value column can't be negative (\"%s\")\n", name, arg);
-			if (col < 3)   chastise ("[%s] value column can't be 1, 2 or 3 (\"%s\")\n", name, arg);
-			op->valColumn = col;
-			continue;
-			}
+		/* (minwith and maxwith take a column but none of the spellings of "no value": to them "none" is not an integer) */
+		if (isWith && (strcmp (arg, "--value=none") == 0)) string_to_int (argVal);
+		if (!isMask && (!isWith || (strcmp_prefix (arg, "--value=") == 0)) && value_column_take (name, arg, &op->valColumn)) continue;
 		if ((kind == K_MINOVER) && (strcmp_prefix (arg, "--infinity=") == 0)) { op->maskVal = string_to_valtype (argVal);  continue; }
 		if ((kind == K_MAXOVER) && is_opt3 (arg, "zero", "Z"))                { op->maskVal = string_to_valtype (argVal);  continue; }
 		if (isMask && !isOver && is_opt3 (arg, "mask", "M"))
@@ -258,17 +249,7 @@ dspop* op_input_parse (char* name, int argc, char** argv)       /* opio.c:88-205
 		{
 		char* arg = argv[0];
 		char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
-		if ((strcmp (arg, "--novalue") == 0) || (strcmp (arg, "--novalues") == 0) || (strcmp (arg, "--value=none") == 0))
-			{ op->valColumn = -1;  continue; }
-		if (strcmp_prefix (arg, "--value=") == 0)
-			{
-			int col = string_to_int (argVal) - 1;
-			if (col == -1) chastise ("[%s] value column can't be 0 (\"%s\")\n", name, arg);
-			if (col < 0)   chastise ("[%s] value column can't be negative (\"%s\")\n", name, arg);
-			if (col < 3)   chastise ("[%s] value column can't be 1, 2 or 3 (\"%s\")\n", name, arg);
-			op->valColumn = col;
-			continue;
-			}
+		if (value_column_take (name, arg, &op->valColumn)) continue;
 		if (strcmp_prefix (arg, "--missing=") == 0)
 			{ op->missingVal = (int) string_to_valtype (argVal);  continue; }     /* an int in the reference too, opio.c:35 */
 		if (strcmp (arg, "--overlap=sum") == 0) { op->overlapOp = ri_overlapSum;  continue; }

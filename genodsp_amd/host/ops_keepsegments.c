@@ -10,7 +10,7 @@
  * signal; the table of the kept segments is written only when --output= names a file.  The variables segments, covered
  * and longest are set.
  *
- * Compiled in with -DGDSP_SEGMENTS, like ops_segments.c. */
+ * The driver finds this operator and `segments` through opgroup_segments, at the end of this file (host_services.h). */
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -19,7 +19,7 @@
 #include "utilities.h"
 #include "host_services.h"
 
-dspprototypes(op_keepsegments)
+dspprototypes(op_keepsegments)  dspprototypes(op_segments)
 
 typedef struct dspop_keepsegments
 	{
@@ -101,6 +101,16 @@ void op_keepsegments_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont
 	segments_run (_op, &op->o, op->o.outFilename != NULL, &op->paint);
 	}
 
-/* the driver: what it needs to know */
-int op_keepsegments_is     (dspop* op) { return op->funcApply == op_keepsegments_apply; }
-int op_keepsegments_copies (dspop* op) { return ((dspop_keepsegments*) op)->paint.mode == GDSP_KEEP_VALUE; }
+/* the driver: both work on whole chromosomes.  segments only reads the signal (and the tiles that hold regions);
+ * keepsegments adds a store per base through the partners and, with --as=value, the signal again inside the regions */
+static void segments_work (dspop* op, u64* bases, double* bytesPerBase) { *bytesPerBase = 8; }
+static void keepsegments_work (dspop* op, u64* bases, double* bytesPerBase)
+	{ *bytesPerBase = (((dspop_keepsegments*) op)->paint.mode == GDSP_KEEP_VALUE)? 24 : 16; }
+
+static const dspinfo segmentsRows[] =
+	{ dspinforecord("segments"    , op_segments)    , dspinfoalias ("callpeaks")    , dspinfoalias ("call_peaks"), dspinfoalias ("islands"),
+	  dspinforecord("keepsegments", op_keepsegments), dspinfoalias ("keep_segments"), dspinfoalias ("hysteresis"), dspinfoalias ("paintsegments") };
+static const optraits segmentsTraits[] =
+	{ { op_segments_apply,     true,  false, NULL, NULL, segments_work },
+	  { op_keepsegments_apply, false, false, NULL, NULL, keepsegments_work } };
+const opgroup opgroup_segments = OPGROUP (segmentsRows, segmentsTraits, NULL);

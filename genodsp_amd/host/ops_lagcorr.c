@@ -10,8 +10,8 @@
  * divided by the size of lag 0's sample as R's acf / ccf do -- so what is printed does not depend on the number of
  * devices, the cut of the genome, chromosome order or the way the devices' images meet.  The signal is only read.
  *
- * The driver's table rows and the lines that hand the communicator to the library are compiled only with -DGDSP_LAGCORR
- * (genodsp_amd/host/Makefile); every call into the device library for them stays in this file. */
+ * The driver finds these operators through opgroup_lagcorr, at the end of this file (host_services.h); every call into the
+ * device library for them stays here. */
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -129,17 +129,7 @@ static dspop* lagcorr_parse (char* name, int argc, char** argv, int withFile)
 		if (strcmp_prefix (arg, "--output=") == 0)
 			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
 		if ((strcmp (arg, "--report:bash") == 0) || (strcmp (arg, "--bash") == 0)) { op->reportForBash = true;  continue; }
-		if (withFile && ((strcmp (arg, "--novalue") == 0) || (strcmp (arg, "--novalues") == 0) || (strcmp (arg, "--value=none") == 0)))
-			{ op->valColumn = -1;  continue; }
-		if (withFile && (strcmp_prefix (arg, "--value=") == 0))
-			{
-			int col = string_to_int (argVal) - 1;
-			if (col == -1) chastise ("[%s] value column can't be 0 (\"%s\")\n", name, arg);
-			if (col < 0)   chastise ("[%s] value column can't be negative (\"%s\")\n", name, arg);
-			if (col < 3)   chastise ("[%s] value column can't be 1, 2 or 3 (\"%s\")\n", name, arg);
-			op->valColumn = col;
-			continue;
-			}
+		if (withFile && value_column_take (name, arg, &op->valColumn)) continue;
 		if (withFile && origin_opt_take (arg, &op->originOne)) continue;
 		if (strcmp_prefix (arg, "--debug") == 0) continue;
 		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
@@ -262,3 +252,10 @@ void op_crosscorrelate_apply (dspop* op, arg_dont_complain(char* vName), arg_don
 
 void op_autocorrelate_apply (dspop* op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
 	{ lagcorr_apply (op); }
+
+/* the driver: autocorrelate is the signal against itself, no partner is touched */
+static const dspinfo lagcorrRows[] =
+	{ dspinforecord("crosscorrelate", op_crosscorrelate), dspinfoalias ("cross_correlate"), dspinfoalias ("xcorr"), dspinfoalias ("ccf"),
+	  dspinforecord("autocorrelate" , op_autocorrelate) , dspinfoalias ("autocorrelation"), dspinfoalias ("acf") };
+static const optraits lagcorrTraits[] = { { op_autocorrelate_apply, true, false, NULL, NULL, NULL } };
+const opgroup opgroup_lagcorr = OPGROUP (lagcorrRows, lagcorrTraits, gdsp_genome_lag_correlation_use_comm);

@@ -3,8 +3,8 @@
  * Window, centring and edge rule are slidingsum's (ops_sum.c, sum.c:436-455 in the reference).
  * The definition is at gdsp_localstats (include/genodsp_hip.h).
  *
- * The driver's table row and the batch / reach branches in ops_fused.c that name this operator are compiled only with
- * -DGDSP_LOCALSTATS (genodsp_amd/host/Makefile); every call into the device library for it stays in this file. */
+ * The driver finds this operator through opgroup_localstats, at the end of this file (host_services.h); every call into the
+ * device library for it stays here. */
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -128,15 +128,20 @@ void op_localstats_apply (dspop* _op, char* vName, u32 vLen, valtype* v)
 	flip_vector (vName);
 	}
 
-/* ops_fused.c: the window (op_reach) and one launch per device (batch_apply_on_device) */
-int op_localstats_is (dspop* op) { return (op->funcApply == op_localstats_apply); }
+/* the driver: slidingsum's window, [c-lft, c+rgt] with the longer side on the left, and one launch per device (windows
+ * above the maximum were refused at parse time) */
+static int localstats_reach (dspop* op, u32* left, u32* right) { return reach_centred (((dspop_localstats*) op)->windowSize, right, left); }
 
-u32 op_localstats_window (dspop* op) { return ((dspop_localstats*) op)->windowSize; }
-
-int op_localstats_batch (dspop* _op, const gdsp_batch_item* items, int nitems, void* stream)
+static int localstats_batch (dspop* _op, const gdsp_batch_item* items, int nitems, void* stream)
 	{
 	dspop_localstats* op = (dspop_localstats*) _op;
 	resolve_levels (op);
 	return gdsp_localstats_batch (items, nitems, op->windowSize, op->what,
 	                              op->haveFloor, op->floor, op->haveMinSd, op->minSd, stream);
 	}
+
+static const dspinfo localstatsRows[] =
+	{ dspinforecord("localstats", op_localstats), dspinfoalias ("local_stats"), dspinfoalias ("localzscore"),
+	  dspinfoalias ("localbackground") };
+static const optraits localstatsTraits[] = { { op_localstats_apply, false, false, localstats_reach, localstats_batch, NULL } };
+const opgroup opgroup_localstats = OPGROUP (localstatsRows, localstatsTraits, NULL);

@@ -3,8 +3,8 @@
  * Window, centring and edge rule are bestmax's (ops_minmax.c, minmax.c:1527-1603 / :1616-1640 in the reference).
  * The definition is at gdsp_prominence (include/genodsp_hip.h).
  *
- * The driver's table row and the batch / reach branches in ops_fused.c that name this operator are compiled only with
- * -DGDSP_PROMINENCE (genodsp_amd/host/Makefile); every call into the device library for it stays in this file. */
+ * The driver finds this operator through opgroup_prominence, at the end of this file (host_services.h); every call into the
+ * device library for it stays here. */
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -72,13 +72,16 @@ void op_prominence_apply (dspop* _op, char* vName, u32 vLen, valtype* v)
 	flip_vector (vName);
 	}
 
-/* ops_fused.c: the window (op_reach) and one launch per device (batch_apply_on_device) */
-int op_prominence_is (dspop* op) { return (op->funcApply == op_prominence_apply); }
+/* the driver: bestmax's window (neither walk leaves [i-wL, i+wR]), and one launch per device (windows above the maximum
+ * were refused at parse time) */
+static int prominence_reach (dspop* op, u32* left, u32* right) { return reach_centred (((dspop_prominence*) op)->windowSize, left, right); }
 
-u32 op_prominence_window (dspop* op) { return ((dspop_prominence*) op)->windowSize; }
-
-int op_prominence_batch (dspop* _op, const gdsp_batch_item* items, int nitems, void* stream)
+static int prominence_batch (dspop* _op, const gdsp_batch_item* items, int nitems, void* stream)
 	{
 	dspop_prominence* op = (dspop_prominence*) _op;
 	return gdsp_prominence_batch (items, nitems, op->windowSize, op->what, stream);
 	}
+
+static const dspinfo  prominenceRows[]   = { dspinforecord("prominence", op_prominence), dspinfoalias ("peakprominence") };
+static const optraits prominenceTraits[] = { { op_prominence_apply, false, false, prominence_reach, prominence_batch, NULL } };
+const opgroup opgroup_prominence = OPGROUP (prominenceRows, prominenceTraits, NULL);

@@ -14,8 +14,8 @@
  * keepsegments (ops_keepsegments.c) selects its segments by the same options and writes them back into the signal: the
  * options' parser (segments_opts_*) and the pass (segments_run) are here for both.
  *
- * The driver's table rows and branches that name this operator are compiled only with -DGDSP_SEGMENTS
- * (genodsp_amd/host/Makefile); every call into the device library for it stays in this file. */
+ * The driver finds both operators through opgroup_segments, at the end of ops_keepsegments.c (host_services.h); every call
+ * into the device library for them stays in this file. */
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -296,6 +296,3 @@ void op_segments_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_com
 	dspop_segments* op = (dspop_segments*) _op;
 	segments_run (_op, &op->o, !op->quiet, NULL);
 	}
-
-/* the driver: what it needs to know */
-int op_segments_is (dspop* op) { return op->funcApply == op_segments_apply; }

@@ -10,8 +10,8 @@
  * way the devices' images meet (RCCL all-reduce of u64 words, or a host sum with --reduce=host).
  * multiplyconst and divideconst are per-base operators that take a number or a variable.
  *
- * The driver's table rows and the stop-operator, batch and reach branches that name these operators are compiled only
- * with -DGDSP_GENOME_STATS (genodsp_amd/host/Makefile); every call into the device library for them stays in this file. */
+ * The driver finds these operators through opgroup_stats, at the end of this file (host_services.h); every call into the
+ * device library for them stays here. */
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -224,18 +224,26 @@ void   op_divide_constant_free  (dspop* op) { const_free (op); }
 void op_divide_constant_apply (dspop* _op, arg_dont_complain(char* vName), u32 vLen, valtype* v)
 	{ valtype c = const_value (_op);  check_gdsp (gdsp_divide_constant (v, vLen, c, op_stream ()), _op->name); }
 
-/* ops_fused.c and the driver: what they need to know */
-int op_const_is (dspop* op)
-	{ return (op->funcApply == op_multiply_constant_apply) || (op->funcApply == op_divide_constant_apply); }
-
-int op_const_batch (dspop* op, const gdsp_batch_item* items, int nitems, void* stream)
+/* the driver: multiplyconst and divideconst are per-base and in place, with one launch per device; stats and normalize
+ * take the signal's parts as they are (normalize rewrites halo and owner alike), at 8 B per base and stats pass */
+static int const_batch (dspop* op, const gdsp_batch_item* items, int nitems, void* stream)
 	{
 	valtype c = const_value (op);
 	if (op->funcApply == op_multiply_constant_apply) return gdsp_multiply_constant_batch (items, nitems, c, stream);
 	return gdsp_divide_constant_batch (items, nitems, c, stream);
 	}
 
-int op_stats_is_stop (dspop* op)
-	{ return (op->funcApply == op_stats_apply) || (op->funcApply == op_normalize_apply); }
+static void stats_work     (dspop* op, u64* bases, double* bytesPerBase) { *bytesPerBase = 16; }
+static void normalize_work (dspop* op, u64* bases, double* bytesPerBase) { *bytesPerBase = 32; }
 
-int op_stats_is_normalize (dspop* op) { return op->funcApply == op_normalize_apply; }
+static const dspinfo statsRows[] =
+	{ dspinforecord("stats"         , op_stats)            ,
+	  dspinforecord("normalize"     , op_normalize)        ,
+	  dspinforecord("multiplyconst" , op_multiply_constant), dspinfoalias ("multiply_const"), dspinfoalias ("scale"),
+	  dspinforecord("divideconst"   , op_divide_constant)  , dspinfoalias ("divide_const") };
+static const optraits statsTraits[] =
+	{ { op_stats_apply,             true, true,  NULL,       NULL,        stats_work },
+	  { op_normalize_apply,         true, true,  NULL,       NULL,        normalize_work },
+	  { op_multiply_constant_apply, true, false, reach_none, const_batch, NULL },
+	  { op_divide_constant_apply,   true, false, reach_none, const_batch, NULL } };
+const opgroup opgroup_stats = OPGROUP (statsRows, statsTraits, gdsp_genome_stats_use_comm);

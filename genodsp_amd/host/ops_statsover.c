@@ -9,8 +9,8 @@
  * (gdsp_interval_stats_batch, include/genodsp_hip.h: every figure exact and rounded once, a function of the interval's
  * sample alone).  Batches are consecutive stretches of the file, so printing them one after the other keeps file order.
  *
- * The driver's table rows and branches that name this operator are compiled only with -DGDSP_INTERVAL_STATS
- * (genodsp_amd/host/Makefile); every call into the device library for it stays in this file. */
+ * The driver finds this operator through opgroup_statsover, at the end of this file (host_services.h); every call into the
+ * device library for it stays here. */
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -226,6 +226,12 @@ void op_statsover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_co
 	free (b.rows);  free (b.rec);  free (b.vec);  free (b.start);  free (b.end);  free (b.serial);  free (b.out);  free (b.text);
 	}
 
-/* the driver: what it needs to know */
-int op_statsover_is    (dspop* op) { return op->funcApply == op_statsover_apply; }
-u64 op_statsover_bases (dspop* op) { u64 n = ((dspop_statsover*) op)->bases;  ((dspop_statsover*) op)->bases = 0;  return n; }
+/* the driver: the signal is only read, 8 B per base of the intervals' summed length since the last call */
+static void statsover_work (dspop* op, u64* bases, double* bytesPerBase)
+	{ *bases = ((dspop_statsover*) op)->bases;  ((dspop_statsover*) op)->bases = 0;  *bytesPerBase = 8; }
+
+static const dspinfo statsoverRows[] =
+	{ dspinforecord("statsover", op_statsover), dspinfoalias ("stats_over"), dspinfoalias ("intervalstats"),
+	  dspinfoalias ("interval_stats") };
+static const optraits statsoverTraits[] = { { op_statsover_apply, true, false, NULL, NULL, statsover_work } };
+const opgroup opgroup_statsover = OPGROUP (statsoverRows, statsoverTraits, NULL);
