@@ -327,6 +327,27 @@ def local_stats(v, W, as_="zscore", floor=None, minsd=None, out=None, stream=Non
     return out
 
 
+# --------------------------------------------------- distance (not in the reference) ----
+
+DISTANCE_TO = {"nearest": 0, "left": 1, "right": 2}    # GDSP_DISTANCE_*
+
+
+def _distance_params(T, ties_above, to, signed, cap):
+    if to not in DISTANCE_TO:
+        raise ValueError("to must be one of %s, not %r" % (", ".join(DISTANCE_TO), to))
+    if cap is not None and int(cap) < 1:
+        raise ValueError("cap must be at least 1 (None: no cap), not %r" % (cap,))
+    return float(T), int(bool(ties_above)), DISTANCE_TO[to], int(bool(signed)), int(cap or 0)
+
+
+def distance(v, T=0.0, ties_above=False, to="nearest", signed=False, cap=None, stream=None):
+    """v[i] = the distance in bases from i to the nearest member (v > T, or >= with ties_above) on the side(s) `to`
+    names, len(v) where there is none; signed: members get minus their distance to the nearest non-member; cap: no
+    result beyond it (gdsp_distance in include/genodsp_hip.h).  In place."""
+    call("gdsp_distance", v.ptr, v.n, *_distance_params(T, ties_above, to, signed, cap), _sp(stream))
+    return v
+
+
 # ---------------------------------------------------------- morphology.c ----
 
 def split_length(length):
@@ -1448,6 +1469,11 @@ def prominence_batch(vecs, W, as_="prominence", outs=None, stream=None):
 
 def local_stats_batch(vecs, W, as_="zscore", floor=None, minsd=None, outs=None, stream=None):
     return _batch("gdsp_localstats_batch", vecs, outs, *_localstats_params(W, as_, floor, minsd), stream=stream)
+
+
+def distance_batch(vecs, T=0.0, ties_above=False, to="nearest", signed=False, cap=None, stream=None):
+    return _batch("gdsp_distance_batch", vecs, None, *_distance_params(T, ties_above, to, signed, cap), stream=stream,
+                  in_place=True)
 
 
 def dilate_batch(vecs, left, right, T=0.0, one=1.0, zero=0.0, outs=None, stream=None):

@@ -148,6 +148,11 @@ SIGNATURES = {
     "gdsp_localstats_tile": (_u32, [_u32]),
     "gdsp_localstats": (_int, [_vp, _vp, _u32, _u32, _int, _int, _f64, _int, _f64, _vp]),
     "gdsp_localstats_batch": (_int, [_vp, _int, _u32, _int, _int, _f64, _int, _f64, _vp]),
+    # distance (not in the reference)
+    "gdsp_distance_tile": (_u32, []),
+    "gdsp_distance": (_int, [_vp, _u32, _f64, _int, _int, _int, _u32, _vp]),
+    "gdsp_distance_batch": (_int, [_vp, _int, _f64, _int, _int, _int, _u32, _vp]),
+    "gdsp_distance_times": (None, [_vp]),
     # stats / normalize / multiplyconst / divideconst (not in the reference)
     "gdsp_xsum_init": (_int, [_vp, _vp]),
     "gdsp_xsum_accumulate_batch": (_int, [_vp, _int, _u32, _f64, _f64, _vp, _vp]),

@@ -114,9 +114,10 @@ extern const opgroup opgroup_lagcorr    __attribute__((weak));      /* the same 
 extern const opgroup opgroup_segments   __attribute__((weak));      /* the signal's own regions above a threshold */
 extern const opgroup opgroup_prominence __attribute__((weak));      /* how far each base stands above its surroundings */
 extern const opgroup opgroup_localstats __attribute__((weak));      /* each base against the window around it */
+extern const opgroup opgroup_distance   __attribute__((weak));      /* each base to the nearest base above a threshold */
 static const opgroup* const opGroups[] =
 	{ &opgroup_rankfilt, &opgroup_stats, &opgroup_statsover, &opgroup_histogram, &opgroup_correlate, &opgroup_lagcorr,
-	  &opgroup_segments, &opgroup_prominence, &opgroup_localstats };
+	  &opgroup_segments, &opgroup_prominence, &opgroup_localstats, &opgroup_distance };
 #define numOpGroups ((int) (sizeof(opGroups)/sizeof(opGroups[0])))
 
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS

@@ -142,6 +142,7 @@ typedef struct segments_opts
 	} segments_opts;
 typedef struct segments_paint { int mode;  valtype one, zero; } segments_paint;       /* mode: GDSP_KEEP_* */
 void  segments_opts_init       (segments_opts* o);
+int   segments_threshold_take  (segments_opts* o, char* name, char* arg);   /* --threshold= / T=, --ties: alone (distance) */
 int   segments_opts_take       (segments_opts* o, char* name, char* arg);
 void  segments_opts_take_other (segments_opts* o, char* name, char* arg);
 void  segments_opts_free       (segments_opts* o);

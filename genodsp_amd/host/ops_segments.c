@@ -74,8 +74,9 @@ void segments_opts_init (segments_opts* o)
 	o->originOne = (int) get_named_global ("originOne", false);
 	}
 
-/* the options that select the segments and shape their table; true: `arg` was one of them */
-int segments_opts_take (segments_opts* o, char* name, char* arg)
+/* the threshold as a variable's name and the side of the ties (distance, ops_distance.c, takes these and no more);
+ * true: `arg` was one of them */
+int segments_threshold_take (segments_opts* o, char* name, char* arg)
 	{
 	char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
 	if (is_opt3 (arg, "threshold", "T"))                 /* a variable NAME only, as binarize */
@@ -87,6 +88,14 @@ int segments_opts_take (segments_opts* o, char* name, char* arg)
 		}
 	if ((strcmp (arg, "--ties:below") == 0) || (strcmp (arg, "--ties=below") == 0)) { o->tiesAbove = false;  return true; }
 	if ((strcmp (arg, "--ties:above") == 0) || (strcmp (arg, "--ties=above") == 0)) { o->tiesAbove = true;   return true; }
+	return false;
+	}
+
+/* the options that select the segments and shape their table; true: `arg` was one of them */
+int segments_opts_take (segments_opts* o, char* name, char* arg)
+	{
+	char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
+	if (segments_threshold_take (o, name, arg)) return true;
 	if (strcmp_prefix (arg, "--mergegap=") == 0)  { o->mergeGap  = bases_arg (name, arg, argVal, "--mergegap");   return true; }
 	if (strcmp_prefix (arg, "--minlength=") == 0) { o->minLength = bases_arg (name, arg, argVal, "--minlength");  return true; }
 	if (strcmp_prefix (arg, "--minheight=") == 0)

@@ -296,6 +296,39 @@ int gdsp_localstats       (const double* d_in, double* d_out, uint32_t n, uint32
 int gdsp_localstats_batch (const gdsp_batch_item* items, int nitems, uint32_t W, int what,
                            int haveFloor, double floor, int haveMinSd, double minSd, void* stream);
 
+/* ---- distance (not in the reference): every base to the nearest base above a threshold ----------------------------
+ * Take a vector v of n values, a threshold T with tiesAbove, a side `to`, a flag isSigned and a cap R (0: none).
+ * Base i is a member iff v[i] > T, or v[i] >= T with tiesAbove: the test of gdsp_segments_batch; a NaN is never a member.
+ * For base i let L(i) be the largest member j <= i and Rt(i) the smallest member j >= i; either may not exist.
+ *   dl = i - L(i), dr = Rt(i) - i
+ *   to:  GDSP_DISTANCE_NEAREST  d = the smaller of those that exist
+ *        GDSP_DISTANCE_LEFT     d = dl  (towards lower coordinates)
+ *        GDSP_DISTANCE_RIGHT    d = dr
+ *   and d = n where nothing exists on the asked side(s): no distance reaches it (the largest is n-1).
+ * Unsigned: out[i] = d, so a member gets +0.0.
+ * Signed: a non-member gets d; a member gets -e, where e is the same figure for the complement set with positions -1
+ * and n counted as non-members (erode's convention: outside the vector is not in S).  So e >= 1 always exists, nothing
+ * is 0, the edge bases of a run are -1 and the base next to a run is +1; with LEFT / RIGHT e looks that way only.
+ * Cap R >= 1: out[i] = min(d, R), respectively max(-e, -R); a base with nothing on the asked side gets R, not n.  With
+ * a cap, out[i] depends on v[i-R .. i+R] only and not on where i lies in the vector.
+ * Every output is an integer held exactly by a double (n <= 2^32-1); the values enter through the membership test
+ * alone, so the result is the definition's bit for bit on any input.
+ * In place.  gdsp_distance_batch uses d_out only, as the other in-place batch calls.  GDSP_EINVAL for an unknown `to` or
+ * a NaN T; n == 0 is a no-op.  Three launches in stream order cover every vector of the batch, 32 vectors at a time
+ * (gdsp_distance.hip: membership bits and tile extents; a join of the extents per vector; the write), in workspace of
+ * the library's own (n/8 bytes and 32 per tile, per device, kept); calls on several streams of a device take it in turn.
+ * gdsp_distance_times: with GDSP_DISTANCE_TIMES=1 in the environment, the milliseconds of the last call's three
+ * launches, from events (the call then waits for them); zeros otherwise. */
+#define GDSP_DISTANCE_NEAREST 0
+#define GDSP_DISTANCE_LEFT    1
+#define GDSP_DISTANCE_RIGHT   2
+/* Host: bases per workgroup tile; results never depend on it */
+uint32_t gdsp_distance_tile  (void);
+int gdsp_distance       (double* d_v, uint32_t n, double T, int tiesAbove, int to, int isSigned, uint32_t cap, void* stream);
+int gdsp_distance_batch (const gdsp_batch_item* items, int nitems, double T, int tiesAbove, int to, int isSigned,
+                         uint32_t cap, void* stream);
+void gdsp_distance_times (double ms[3]);
+
 /* ---- logical.c, mask.c, add.c (in place) ---------------------------------------- */
 int gdsp_binarize     (double* d_v, uint32_t n, double T, int tiesAbove, double one, double zero,
                        void* stream);                                 /* logical.c:216-268 */
