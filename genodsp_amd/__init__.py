@@ -850,6 +850,105 @@ def genome_lag_correlation_last():
     return dict(zip(("count", "products", "flushes", "nonfinite_products"), [int(x) for x in out]))
 
 
+# ------------------------------------------------------ profileover (not in the reference) ----
+
+PROFILE_MAX_OFFSETS = 16384                        # GDSP_PROFILE_MAX_OFFSETS
+
+
+class ProfileSource(C.Structure):
+    """gdsp_profile_source of include/genodsp_hip.h"""
+    _fields_ = [("d_v", C.c_void_p), ("n", C.c_uint32), ("device", C.c_int), ("stream", C.c_void_p),
+                ("h_pos", C.c_void_p), ("h_minus", C.c_void_p), ("nanchors", C.c_uint32)]
+
+
+def profile_block():
+    """Offsets a workgroup of the profile kernel owns."""
+    return int(lib().gdsp_profile_block())
+
+
+def profile_set_launch_anchors(anchors):
+    """Anchors per launch of the profile kernel (0: the library's own number).  For tests that force several launches."""
+    call("gdsp_profile_set_launch_anchors", int(anchors))
+
+
+def _profile_anchors(anchors, nvecs):
+    """anchors: rows (vector index, position, strand +1 / -1) -> int64[count, 3]"""
+    a = np.asarray(anchors, dtype=np.int64).reshape(-1, 3)
+    assert np.all((a[:, 0] >= 0) & (a[:, 0] < max(nvecs, 1))) and np.all((a[:, 1] >= 0) & (a[:, 1] <= 0xFFFFFFFF))
+    assert np.all(np.abs(a[:, 2]) == 1)
+    return a
+
+
+def profile_images(vecs, anchors, off_lo, noffsets, lo=-DBL_MAX, hi=DBL_MAX, mean=None, stream=None):
+    """The canonical images of one pass of gdsp_profile_accumulate_batch, np.uint64[noffsets, XSUM_WORDS]: image k sums the
+    sampled values at offset off_lo + k from the anchors -- or, with mean (one per offset), their fl(fl(v - mean[k])^2).
+    vecs: as xsum_sources, whole chromosomes; anchors: rows (vector index, position, strand +1 / -1)."""
+    noffsets = int(noffsets)
+    src = xsum_sources(vecs, stream)
+    a = _profile_anchors(anchors, len(vecs))
+    items = (BatchItem * max(len(vecs), 1))()
+    for i in range(len(vecs)):
+        items[i].d_in, items[i].d_out, items[i].n = src[i].d_v, None, src[i].n
+    na = int(a.shape[0])
+    anc = DeviceBuffer(max(1, 2 * na) * 4)
+    if na:
+        anc.upload(np.concatenate([a[:, 1].astype(np.uint32), (a[:, 0] * 2 + (a[:, 2] < 0)).astype(np.uint32)]), stream=stream)
+    acc = DeviceBuffer(max(1, noffsets) * XSUM_WORDS * 8)
+    acc.upload(np.zeros(max(1, noffsets) * XSUM_WORDS, np.uint64), stream=stream)
+    d_mean = None
+    if mean is not None:
+        m = np.ascontiguousarray(mean, dtype=np.float64)
+        assert m.size == noffsets
+        d_mean = DeviceBuffer(max(1, noffsets) * 8)
+        d_mean.upload(m, stream=stream)
+    call("gdsp_profile_accumulate_batch", items, len(vecs), C.c_void_p(anc.ptr), C.c_void_p(anc.ptr + 4 * na), na,
+         int(off_lo), noffsets, float(lo), float(hi), C.c_void_p(d_mean.ptr) if d_mean is not None else None,
+         C.c_void_p(acc.ptr), _sp(stream))
+    return acc.download(np.uint64, noffsets * XSUM_WORDS, stream=stream).reshape(noffsets, XSUM_WORDS)
+
+
+def genome_profile(vecs, anchors, off_lo, noffsets, bin=1, lo=-DBL_MAX, hi=DBL_MAX, allreduce=None, stream=None):
+    """The aggregate profile of the signal around anchors (gdsp_genome_profile): per column of `bin` offsets out of
+    off_lo .. off_lo + noffsets - 1, the count, sum, mean, variance and stddev of the values found that far from the
+    anchors in their own direction, each exact and rounded once, and stderr = stddev / sqrt(count).  vecs: as
+    xsum_sources, whole chromosomes; anchors: rows (vector index, position, strand +1 / -1); allreduce: genome_stats'
+    hook.  Returns a dict of np arrays, one entry per column ("offsets": each column's lowest offset)."""
+    noffsets, bin = int(noffsets), int(bin)
+    src = xsum_sources(vecs, stream)
+    a = _profile_anchors(anchors, len(vecs))
+    tab = (ProfileSource * max(1, len(vecs)))()
+    keep = []
+    for i in range(len(vecs)):
+        mine = a[a[:, 0] == i]
+        pos = np.ascontiguousarray(mine[:, 1], dtype=np.uint32)
+        minus = np.ascontiguousarray(mine[:, 2] < 0, dtype=np.uint32)
+        keep.append((pos, minus))
+        tab[i].d_v, tab[i].n, tab[i].device, tab[i].stream = src[i].d_v, src[i].n, src[i].device, stream
+        tab[i].h_pos, tab[i].h_minus, tab[i].nanchors = pos.ctypes.data, minus.ctypes.data, pos.size
+    ncols = noffsets // bin if bin >= 1 and noffsets >= 1 else 0
+    count = np.zeros(max(1, ncols), np.uint64)
+    figs = [np.zeros(max(1, ncols), np.float64) for _ in range(4)]
+    failure = []
+    cb = _reduce_hook(allreduce, failure)
+    with _hook_failure_first(failure):
+        call("gdsp_genome_profile", tab, len(vecs), int(off_lo), noffsets, bin, float(lo), float(hi), cb, None,
+             count.ctypes.data_as(C.c_void_p), *[f.ctypes.data_as(C.c_void_p) for f in figs])
+    out = {"offsets": np.arange(ncols, dtype=np.int64) * bin + int(off_lo), "count": count[:ncols]}
+    for k, f in zip(("sum", "mean", "variance", "stddev"), figs):
+        out[k] = f[:ncols]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["stderr"] = out["stddev"] / np.sqrt(out["count"].astype(np.float64))
+    return out
+
+
+def genome_profile_last():
+    """What the last genome_profile did: its anchors, the samples taken over all offsets, lane flushes into the device
+    images (both passes), and the q that were not finite."""
+    out = (C.c_uint64 * 4)()
+    lib().gdsp_genome_profile_last(out)
+    return dict(zip(("anchors", "samples", "flushes", "nonfinite_squares"), [int(x) for x in out]))
+
+
 # ------------------------------------------------------ histogram (not in the reference) ----
 
 HISTOGRAM_MAX_BINS = 65536

@@ -178,6 +178,13 @@ SIGNATURES = {
     "gdsp_genome_lag_correlation": (_int, [_vp, _int, C.c_int32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gdsp_genome_lag_correlation_use_comm": (_int, [_vp]),
     "gdsp_genome_lag_correlation_last": (None, [_vp]),
+    # profileover (not in the reference)
+    "gdsp_profile_block": (_u32, []),
+    "gdsp_profile_set_launch_anchors": (_int, [_u32]),
+    "gdsp_profile_accumulate_batch": (_int, [_vp, _int, _vp, _vp, _u32, C.c_int32, _u32, _f64, _f64, _vp, _vp, _vp]),
+    "gdsp_genome_profile": (_int, [_vp, _int, C.c_int32, _u32, _u32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gdsp_genome_profile_use_comm": (_int, [_vp]),
+    "gdsp_genome_profile_last": (None, [_vp]),
     # statsover (not in the reference)
     "gdsp_interval_stats_tile": (_u32, []),
     "gdsp_interval_stats": (_int, [_vp, _u32, _vp, _vp, _u32, _f64, _f64, _vp, _vp]),

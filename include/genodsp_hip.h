@@ -588,6 +588,58 @@ int gdsp_genome_lag_correlation_use_comm (gdsp_comm* comm);   /* NULL switches b
  * images, [3] products that were not finite, [4] .. [7] zero */
 void gdsp_genome_lag_correlation_last (uint64_t out[8]);
 
+/* ---- profileover (not in the reference): the signal's figures at every offset from a list of anchors, exact ----------
+ * A genome is a list of WHOLE chromosome vectors.  An anchor is (vector, position p, strand s) with 0 <= p < n of its
+ * vector and s = +1 or -1.  For an integer offset k the anchor looks at base g = p + s k of its vector; the pair
+ * (anchor, k) is sampled iff 0 <= g < n and v[g] passes stats' test: finite, and !(v < lo) && !(v > hi).  An anchor whose
+ * window leaves its chromosome contributes the offsets that stay inside; a duplicated anchor contributes twice; nothing
+ * crosses a chromosome's end or joins two chromosomes.
+ * The offsets are the range offLo .. offLo + noffsets - 1: noffsets is 1 .. GDSP_PROFILE_MAX_OFFSETS, offLo any int32 for
+ * which the range stays in int32.  A bin width b >= 1 divides noffsets; column j is the sample of all the pairs
+ * (anchor, k) with offLo + j b <= k < offLo + (j+1) b.  Per column, exactly what gdsp_genome_stats defines for that sample:
+ *   count     the number of pairs sampled;
+ *   sum       the exact sum rounded once (an exact zero is +0.0);
+ *   mean      the exact sum divided by count, rounded once;
+ *   variance  the exact (sum of q) / count rounded once, q = fl(fl(v - mean)^2) without fma against the column's own mean;
+ *             +inf when some q is;   stddev = sqrt (variance).
+ *   count == 0: sum is +0.0 and the rest is NaN.
+ *   (stderr = fl(stddev / sqrt ((double) count)) is the caller's to derive.)
+ * Every figure is a function of the column's sample alone: nothing depends on the order of the anchors or of the
+ * chromosomes, on which device holds which chromosome, on grid, offset block, launch chunking or dispatch order.
+ *
+ * gdsp_profile_accumulate_batch adds the sampled values of every anchor into noffsets images of GDSP_XSUM_WORDS words side
+ * by side, offset offLo + k in image k -- always at base resolution: a column's image is the plain u64 sum of its b
+ * offsets' images -- and leaves the images in canonical digits.  The vectors are items[i] (d_in and n are read) on the
+ * current device, 8-byte aligned; anchor i is position d_pos[i] of vector d_code[i] >> 1, minus strand when d_code[i] & 1:
+ * DEVICE arrays of `count` entries, any order.  d_mean == NULL is pass 1 (the values themselves); otherwise pass 2, which
+ * adds fl(fl(v - d_mean[k])^2) for offset offLo + k (a DEVICE array of noffsets means: a column's mean at each of its
+ * offsets; the mean of an offset that samples nothing is not used) and counts a q that is not finite in the image's
+ * GDSP_XSUM_WORD_INF instead of adding it.  d_acc is zeroed by the caller.  One launch sequence per 32 vectors; within
+ * it the anchors go in launches short enough that no image word can overflow before it is carried
+ * (gdsp_profile_set_launch_anchors lowers that number so that tests can force several launches; 0 restores it).
+ * GDSP_EINVAL for a bad range or an anchor outside its vector (decided on the device: the call waits for the stream once).
+ * gdsp_profile_block () offsets belong to one workgroup (what tests size their shapes by). */
+#define GDSP_PROFILE_MAX_OFFSETS 16384
+uint32_t gdsp_profile_block (void);
+int gdsp_profile_set_launch_anchors (uint32_t anchors);
+int gdsp_profile_accumulate_batch (const gdsp_batch_item* items, int nitems, const uint32_t* d_pos, const uint32_t* d_code,
+                                   uint32_t count, int32_t offLo, uint32_t noffsets, double lo, double hi, const double* d_mean,
+                                   uint64_t* d_acc, void* stream);
+/* end to end, like gdsp_genome_lag_correlation: a source is a whole chromosome d_v[0 .. n) on `device` with its anchors as
+ * HOST arrays (h_pos[i] < n; h_minus[i] != 0 is the minus strand, h_minus == NULL all plus).  Sources may sit on several
+ * devices of this process (communicator and hook as for gdsp_genome_stats; the `reduce` hook is called once per pass
+ * over the noffsets * 72 words, and not for pass 2 when no column sampled anything).  count, sum, mean, variance, stddev:
+ * HOST arrays of noffsets / bin columns. */
+typedef struct gdsp_profile_source { const double* d_v; uint32_t n; int device; void* stream;
+                                     const uint32_t* h_pos; const uint32_t* h_minus; uint32_t nanchors; } gdsp_profile_source;
+int gdsp_genome_profile (const gdsp_profile_source* sources, int nsources, int32_t offLo, uint32_t noffsets, uint32_t bin,
+                         double lo, double hi, gdsp_reduce_fn reduce, void* reduceCtx, uint64_t* count, double* sum,
+                         double* mean, double* variance, double* stddev);
+int gdsp_genome_profile_use_comm (gdsp_comm* comm);   /* NULL switches back to host sums */
+/* what the last gdsp_genome_profile did: [0] anchors, [1] samples taken (all offsets), [2] lane flushes into the device
+ * images (both passes), [3] q that were not finite */
+void gdsp_genome_profile_last (uint64_t out[4]);
+
 /* ---- statsover (not in the reference): one signal quantified over many intervals, exact ---------------------------
  * For a vector v of n doubles, an interval [s, e) with 0 <= s < e <= n, and limits lo, hi:
  *   the sample of the interval is stats' sample restricted to it: the bases i in [s, e) with !(v[i] < lo) &&
