@@ -327,6 +327,34 @@ def local_stats(v, W, as_="zscore", floor=None, minsd=None, out=None, stream=Non
     return out
 
 
+# ----------------------------------------------- localcorrelate (not in the reference) ----
+
+LOCALCORR_MAX_WINDOW = 4097                   # GDSP_LOCALCORR_MAX_WINDOW
+LOCALCORR_WHAT = {"correlation": 0, "covariance": 1, "slope": 2, "intercept": 3}      # GDSP_LOCALCORR_*
+
+
+def _localcorr_what(as_):
+    if as_ not in LOCALCORR_WHAT:
+        raise ValueError("as_ must be one of %s, not %r" % (", ".join(LOCALCORR_WHAT), as_))
+    return LOCALCORR_WHAT[as_]
+
+
+def localcorr_tile(W):
+    """outputs per workgroup tile of the kernel for window W; 0 outside 1 .. LOCALCORR_MAX_WINDOW (host code)"""
+    return lib().gdsp_localcorr_tile(int(W))
+
+
+def local_correlation(x, y, W, as_="correlation", stream=None):
+    """y[c] = the correlation of x and y over slidingsum's window around c, cut off at the ends of the vectors
+    (gdsp_localcorr in include/genodsp_hip.h), or with as_ their covariance, or the slope or intercept of y regressed
+    on x.  y is overwritten and returned; x is only read."""
+    what = _localcorr_what(as_)
+    if x.n != y.n:
+        raise ValueError("x and y must have the same length (%d, %d)" % (x.n, y.n))
+    call("gdsp_localcorr", x.ptr, y.ptr, x.n, int(W), what, _sp(stream))
+    return y
+
+
 # --------------------------------------------------- distance (not in the reference) ----
 
 DISTANCE_TO = {"nearest": 0, "left": 1, "right": 2}    # GDSP_DISTANCE_*
@@ -1568,6 +1596,14 @@ def prominence_batch(vecs, W, as_="prominence", outs=None, stream=None):
 
 def local_stats_batch(vecs, W, as_="zscore", floor=None, minsd=None, outs=None, stream=None):
     return _batch("gdsp_localstats_batch", vecs, outs, *_localstats_params(W, as_, floor, minsd), stream=stream)
+
+
+def local_correlation_batch(xs, ys, W, as_="correlation", stream=None):
+    """local_correlation for every pair in one launch sequence; ys are overwritten and returned"""
+    what = _localcorr_what(as_)
+    if len(xs) != len(ys) or any(x.n != y.n for x, y in zip(xs, ys)):
+        raise ValueError("xs and ys must pair up, vector by vector and length by length")
+    return _batch("gdsp_localcorr_batch", xs, list(ys), int(W), what, stream=stream)
 
 
 def distance_batch(vecs, T=0.0, ties_above=False, to="nearest", signed=False, cap=None, stream=None):

@@ -148,6 +148,11 @@ SIGNATURES = {
     "gdsp_localstats_tile": (_u32, [_u32]),
     "gdsp_localstats": (_int, [_vp, _vp, _u32, _u32, _int, _int, _f64, _int, _f64, _vp]),
     "gdsp_localstats_batch": (_int, [_vp, _int, _u32, _int, _int, _f64, _int, _f64, _vp]),
+    # localcorrelate (not in the reference)
+    "gdsp_localcorr_tile": (_u32, [_u32]),
+    "gdsp_localcorr": (_int, [_vp, _vp, _u32, _u32, _int, _vp]),
+    "gdsp_localcorr_batch": (_int, [_vp, _int, _u32, _int, _vp]),
+    "gdsp_localcorr_times": (None, [_vp]),
     # distance (not in the reference)
     "gdsp_distance_tile": (_u32, []),
     "gdsp_distance": (_int, [_vp, _u32, _f64, _int, _int, _int, _u32, _vp]),

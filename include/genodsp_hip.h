@@ -296,6 +296,56 @@ int gdsp_localstats       (const double* d_in, double* d_out, uint32_t n, uint32
 int gdsp_localstats_batch (const gdsp_batch_item* items, int nitems, uint32_t W, int what,
                            int haveFloor, double floor, int haveMinSd, double minSd, void* stream);
 
+/* ---- localcorrelate (not in the reference): the signal against a second track over the window centred on each base -
+ * Take x (the signal) and y (the track) of n values each and a window W with 1 <= W <= GDSP_LOCALCORR_MAX_WINDOW.
+ * The window is localstats' and slidingsum's: with rgt = (W-1)/2 and lft = W-1-rgt, base c has lo = max(0, c-lft),
+ * hi = min(n-1, c+rgt) and m = hi-lo+1 bases in its window.  Over k = lo .. hi, each term one rounded product:
+ *   Sx = sum x[k]   Sy = sum y[k]   Sxx = sum fl(x[k] x[k])   Syy = sum fl(y[k] y[k])   Sxy = sum fl(x[k] y[k])
+ * From these, every step one rounded IEEE operation on doubles, in this order and never fused:
+ *   md  = (double) m                 mm  = fl(md md)
+ *   Nxx = fl(fl(md Sxx) - fl(Sx Sx))
+ *   Nyy = fl(fl(md Syy) - fl(Sy Sy))
+ *   Nxy = fl(fl(md Sxy) - fl(Sx Sy))
+ *   covariance  = +0.0 if Nxy == 0, else fl(Nxy / mm)               (the population covariance, as in gdsp_genome_correlation)
+ *   correlation = +0.0 if Nxx <= 0 or Nyy <= 0;
+ *                 else D = fl(sqrt(Nxx) * sqrt(Nyy)), each sqrt correctly rounded;
+ *                      +0.0 if D == 0, else fl(Nxy / D), clamped into [-1, 1]
+ *   slope       = +0.0 if Nxx <= 0, else fl(Nxy / Nxx)              (the track regressed on the signal: correlate's direction)
+ *   intercept   = fl(fl(Sy / md) - fl(slope * fl(Sx / md)))
+ * what:  GDSP_LOCALCORR_CORRELATION, _COVARIANCE, _SLOPE or _INTERCEPT writes that figure.
+ * The five sums may be formed in any order or tree, inside the tile a workgroup stages: no further than
+ * gdsp_localcorr_tile(W) bases beyond the window on either side -- the allowance localstats states.  A result therefore
+ * lies within what S +- gamma_M A allows for each of the five, M = 2 (W + tile) + 4, A the sum of the magnitudes of that
+ * sum's terms over the window widened by the tile (tests/localcorr_ref.py pushes those intervals through the steps
+ * above).  Where no sum of those terms can round, every figure is the definition's, bit for bit, however the
+ * implementation sums: for read depth while m Sxx, m Syy and m |Sxy| stay below 2^53.  Non-finite values inside a window
+ * give that base whatever the arithmetic above gives.
+ * d_x (items[].d_in) is the signal and is only read.  d_y (items[].d_out) holds the track on entry and the result on
+ * return: the caller then treats d_y as the new signal, exactly as after any out-of-place operator, and the old signal
+ * is nobody's data any more.  GDSP_EINVAL for d_x == d_y, a NULL or misaligned (16 bytes) pointer, W == 0, W above the
+ * maximum or an unknown `what`; n == 0 is a no-op.
+ * Two launches in stream order cover every vector of a batch, 32 vectors at a time, and the single-vector call runs
+ * the same over a table of one (gdsp_localcorr.hip).  A tile's halo bases of the track are its neighbours' own bases,
+ * which they overwrite, so a small kernel first copies, for every tile, the HL track values before it and the HR behind
+ * it (0.0 outside the vector) into a record of HL + HR doubles in workspace of the library's own (per device, grown on
+ * demand and kept; calls on several streams of a device take it in turn).  The main kernel then stages x from d_x, its
+ * own T track values from d_y and the halos from its record, forms the five sums as localstats forms its two, and
+ * writes its T results over d_y only after every thread of the workgroup has finished reading.  No workgroup reads a
+ * live base that another one writes; nothing is polled and nothing waits on another workgroup.
+ * The workspace is (HL + HR) / T of the track: about 1 % of it at W = 101, 14 % at W = 1001 and 100 % at W = 4097.
+ * gdsp_localcorr_times: with GDSP_LOCALCORR_TIMES=1 in the environment, the milliseconds of the last call's two
+ * launches, from events (the call then waits for them); zeros otherwise. */
+#define GDSP_LOCALCORR_MAX_WINDOW  4097        /* what leaves a workgroup's 8192 staged positions a tile of 4096 */
+#define GDSP_LOCALCORR_CORRELATION 0
+#define GDSP_LOCALCORR_COVARIANCE  1
+#define GDSP_LOCALCORR_SLOPE       2
+#define GDSP_LOCALCORR_INTERCEPT   3
+/* Host: outputs per workgroup tile of the kernel for window W (0 outside 1..the maximum) */
+uint32_t gdsp_localcorr_tile  (uint32_t W);
+int gdsp_localcorr       (const double* d_x, double* d_y, uint32_t n, uint32_t W, int what, void* stream);
+int gdsp_localcorr_batch (const gdsp_batch_item* items, int nitems, uint32_t W, int what, void* stream);
+void gdsp_localcorr_times (double ms[2]);
+
 /* ---- distance (not in the reference): every base to the nearest base above a threshold ----------------------------
  * Take a vector v of n values, a threshold T with tiesAbove, a side `to`, a flag isSigned and a cap R (0: none).
  * Base i is a member iff v[i] > T, or v[i] >= T with tiesAbove: the test of gdsp_segments_batch; a NaN is never a member.
