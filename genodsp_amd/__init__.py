@@ -977,6 +977,89 @@ def genome_profile_last():
     return dict(zip(("anchors", "samples", "flushes", "nonfinite_squares"), [int(x) for x in out]))
 
 
+# ------------------------------------------------------- matrixover (not in the reference) ----
+
+MATRIX_FIGURES = {"mean": 0, "sum": 1, "count": 2, "min": 3, "max": 4}       # GDSP_MATRIX_*
+
+
+def _matrix_figure(what):
+    return MATRIX_FIGURES[what] if isinstance(what, str) else int(what)
+
+
+def _matrix_columns(noffsets, bin):
+    return noffsets // bin if bin >= 1 and noffsets >= 1 and noffsets % bin == 0 else 0
+
+
+def matrix_set_launch_rows(rows):
+    """Rows per launch of genome_matrix (0: the library's own number).  For tests that force several launches."""
+    call("gdsp_matrix_set_launch_rows", int(rows))
+
+
+def matrix_rows(vecs, anchors, off_lo, noffsets, bin=1, what="mean", lo=-DBL_MAX, hi=DBL_MAX, stream=None):
+    """One gdsp_matrix_rows_batch: (rows, todo).  rows is np.float64[len(anchors), noffsets // bin] as the device left it,
+    todo the np.uint32 indices row * ncols + column of the cells it could not finish exactly (in no particular order),
+    whose entries of rows mean nothing.  vecs: as xsum_sources, whole chromosomes; anchors: rows (vector index, position,
+    strand +1 / -1)."""
+    noffsets, bin = int(noffsets), int(bin)
+    src = xsum_sources(vecs, stream)
+    a = _profile_anchors(anchors, len(vecs))
+    items = (BatchItem * max(len(vecs), 1))()
+    for i in range(len(vecs)):
+        items[i].d_in, items[i].d_out, items[i].n = src[i].d_v, None, src[i].n
+    na, ncols = int(a.shape[0]), _matrix_columns(noffsets, bin)
+    cells = na * ncols
+    anc = DeviceBuffer(max(1, 2 * na) * 4)
+    if na:
+        anc.upload(np.concatenate([a[:, 1].astype(np.uint32), (a[:, 0] * 2 + (a[:, 2] < 0)).astype(np.uint32)]), stream=stream)
+    out = DeviceBuffer(max(1, cells) * 8)
+    todo = DeviceBuffer((max(1, cells) + 1) * 4)                        # the counter, then the list
+    todo.upload(np.zeros(1, np.uint32), stream=stream)
+    call("gdsp_matrix_rows_batch", items, len(vecs), C.c_void_p(anc.ptr), C.c_void_p(anc.ptr + 4 * na), na, int(off_lo),
+         noffsets, bin, _matrix_figure(what), float(lo), float(hi), C.c_void_p(out.ptr), C.c_void_p(todo.ptr + 4),
+         C.c_void_p(todo.ptr), _sp(stream))
+    ntodo = int(todo.download(np.uint32, 1, stream=stream)[0])
+    assert ntodo <= cells
+    rows = out.download(np.float64, cells, stream=stream).reshape(na, ncols) if cells else np.zeros((na, ncols))
+    left = todo.download(np.uint32, 1 + ntodo, stream=stream)[1:].copy()
+    return rows, left
+
+
+def genome_matrix(vecs, anchors, off_lo, noffsets, bin=1, what="mean", lo=-DBL_MAX, hi=DBL_MAX, stream=None):
+    """The signal around each anchor (gdsp_genome_matrix): np.float64[len(anchors), noffsets // bin], row i the figure
+    `what` ("mean", "sum", "count", "min" or "max") of anchor i over each column of `bin` offsets out of
+    off_lo .. off_lo + noffsets - 1, in the anchor's own direction; every value exact and rounded once, NaN where a mean,
+    min or max has nothing to look at.  vecs: as xsum_sources, whole chromosomes; anchors: rows (vector index, position,
+    strand +1 / -1), and the rows come back in their order."""
+    noffsets, bin = int(noffsets), int(bin)
+    src = xsum_sources(vecs, stream)
+    a = _profile_anchors(anchors, len(vecs))
+    ncols = _matrix_columns(noffsets, bin)
+    tab = (ProfileSource * max(1, len(vecs)))()
+    rows = (C.c_void_p * max(1, len(vecs)))()
+    keep = []
+    for i in range(len(vecs)):
+        where = np.flatnonzero(a[:, 0] == i)
+        pos = np.ascontiguousarray(a[where, 1], dtype=np.uint32)
+        minus = np.ascontiguousarray(a[where, 2] < 0, dtype=np.uint32)
+        mine = np.zeros((max(1, pos.size), max(1, ncols)), np.float64)
+        keep.append((where, pos, minus, mine))
+        tab[i].d_v, tab[i].n, tab[i].device, tab[i].stream = src[i].d_v, src[i].n, src[i].device, stream
+        tab[i].h_pos, tab[i].h_minus, tab[i].nanchors = pos.ctypes.data, minus.ctypes.data, pos.size
+        rows[i] = mine.ctypes.data
+    call("gdsp_genome_matrix", tab, len(vecs), int(off_lo), noffsets, bin, _matrix_figure(what), float(lo), float(hi), rows)
+    out = np.zeros((a.shape[0], ncols), np.float64)
+    for where, pos, _, mine in keep:
+        out[where] = mine[:pos.size, :ncols]
+    return out
+
+
+def genome_matrix_last():
+    """What the last genome_matrix did: its rows, its cells, the cells the host finished, and the launches."""
+    out = (C.c_uint64 * 4)()
+    lib().gdsp_genome_matrix_last(out)
+    return dict(zip(("rows", "cells", "host cells", "launches"), [int(x) for x in out]))
+
+
 # ------------------------------------------------------ histogram (not in the reference) ----
 
 HISTOGRAM_MAX_BINS = 65536

@@ -190,6 +190,11 @@ SIGNATURES = {
     "gdsp_genome_profile": (_int, [_vp, _int, C.c_int32, _u32, _u32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gdsp_genome_profile_use_comm": (_int, [_vp]),
     "gdsp_genome_profile_last": (None, [_vp]),
+    # matrixover (not in the reference)
+    "gdsp_matrix_rows_batch": (_int, [_vp, _int, _vp, _vp, _u32, C.c_int32, _u32, _u32, _int, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "gdsp_genome_matrix": (_int, [_vp, _int, C.c_int32, _u32, _u32, _int, _f64, _f64, _vp]),
+    "gdsp_matrix_set_launch_rows": (_int, [_u32]),
+    "gdsp_genome_matrix_last": (None, [_vp]),
     # statsover (not in the reference)
     "gdsp_interval_stats_tile": (_u32, []),
     "gdsp_interval_stats": (_int, [_vp, _u32, _vp, _vp, _u32, _f64, _f64, _vp, _vp]),

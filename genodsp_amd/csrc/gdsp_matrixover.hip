@@ -1,0 +1,635 @@
+// gdsp_matrixover.hip -- matrixover (not in the reference): the signal around every anchor of a list, one row per anchor
+// and one double per cell of `bin` offsets (include/genodsp_hip.h has the definitions) -- profileover's picture before the
+// anchors are added up.  A cell is one interval of its chromosome, and its figure is statsover's for that interval.
+//
+// A wave takes whole anchors, by stride over the launch's rows, and walks each window in ascending base order whatever
+// the strand: the strand only decides which column a cell lands in (a minus anchor's ascending cell c is column
+// ncols - 1 - c).  Every base of a window is read from HBM once with plain 8-byte loads, the lanes of the wave on
+// consecutive doubles, which is right at any 8-byte alignment of the vector.  Three routes, by the bin width b:
+//   b == 1       a clipped, strand-ordered copy: lane l reads base g0 + t and writes column t (or noffsets - 1 - t).
+//   2 <= b < 256 the wave stages a stretch of 64 / G cells in its own piece of LDS with coalesced loads, eight in flight
+//                per lane (a base outside the chromosome is staged as NaN, which nothing samples), and a group of G lanes
+//                owns a whole cell: G = 1 below 16 bases, 4 below 64, else 16, so that a stretch is at most MX_STAGE
+//                doubles and all 64 lanes work.  The stretch is stored with one double of padding per 32 (index i lives
+//                at i + i / 32): lanes a power of two of doubles apart would otherwise meet on one bank.  A group folds
+//                its lanes with log2 G steps of the shuffle tree.
+//   b >= 256     the wave strides over the cell, two expansions per lane, and folds its 64 lanes with the shuffle tree of
+//                interval_stats_kernel.
+// The kernel is a template on the figure: min, max and count carry no expansions.  A sum is a lane's two-term expansion
+// grown with xs_grow_or_flag; an unflagged cell's a0 + a1 is its exact sum, so fl(a0 + a1) is the sum rounded once.  The
+// mean is finished here where the exact sum is one double (TwoSum of a0 and a1 leaves no error term, as it always does on
+// read depth): one IEEE division of two exact values is the exact quotient rounded once; and where the sum takes two
+// doubles, when a candidate quotient can be PROVEN to be the exact quotient rounded once from its exact remainder
+// (mx_finish has the argument: all but ties, near-ties within 2^-40, powers of two and extreme exponents).  Every other
+// cell -- flagged, overflowing, or a mean that cannot be proven -- is appended to the launch's to-do list, one atomic per
+// wave and stretch, and computed by the host half through gdsp_interval_stats_batch.  One double is written per cell, by one lane; no
+// atomics on cells, no wave or workgroup waits for another (the LDS piece is a wave's own), no scratch.
+
+#include <float.h>
+#include <math.h>
+#include <string.h>
+#include <vector>
+#include <algorithm>
+#include "gdsp_common.h"
+#include "gdsp_xsum_dev.h"
+
+#define MX_THREADS      256
+#define MX_WAVES        (MX_THREADS / 64)
+#define MX_STAGE        1024                          // doubles of a wave's stretch: 64 cells of up to 15, 16 of up to 63, 4 of up to 255
+#define MX_STAGE_PAD    (MX_STAGE + MX_STAGE / 32)
+#define MX_STAGE_DEPTH  8                             // loads a lane issues before its first LDS store
+#define MX_WG_TARGET    2048                          // workgroups of a launch (33 KiB of LDS each: four on a CU)
+#define MX_LAUNCH_CELLS (1u << 25)                    // cells of one launch of the host half (256 MiB of rows)
+#define MX_MAX_OFFSETS  GDSP_PROFILE_MAX_OFFSETS
+
+#define MX_NARROW_BELOW 256                           // bins from here on take the wide route
+
+enum { MX_ROUTE_COPY = 0, MX_ROUTE_NARROW = 1, MX_ROUTE_WIDE = 2 };
+
+struct MxBatch
+	{
+	const double* v[GDSP_BATCH_MAX];
+	uint32_t      n[GDSP_BATCH_MAX];
+	uint32_t      vec0;                                   // the table holds the vectors vec0 .. vec0 + nvec - 1 of the call
+	uint32_t      nvec;
+	};
+
+// what a lane (then a group, then a cell) knows of its sample
+struct MxAcc { double a[XS_K];  double m;  uint32_t cnt, flag; };
+
+template <int WHAT>
+__device__ __forceinline__ void mx_clear (MxAcc& c)
+	{
+	c.a[0] = c.a[1] = 0.0;  c.cnt = 0;  c.flag = 0;
+	c.m = (WHAT == GDSP_MATRIX_MIN)? HUGE_VAL : -HUGE_VAL;
+	}
+
+template <int WHAT>
+__device__ __forceinline__ void mx_take (MxAcc& c, double x, double lo, double hi)
+	{
+	const bool in = !(x < lo) && !(x > hi) && xs_finite (x);          // stats' tests; NaN and +-inf never
+	if ((WHAT == GDSP_MATRIX_SUM) || (WHAT == GDSP_MATRIX_MEAN)) xs_grow_or_flag (c.a, in? x : 0.0, c.flag);
+	if ((WHAT == GDSP_MATRIX_COUNT) || (WHAT == GDSP_MATRIX_MEAN)) c.cnt += in? 1u : 0u;
+	if (WHAT == GDSP_MATRIX_MIN) c.m = (in && (x < c.m))? x : c.m;
+	if (WHAT == GDSP_MATRIX_MAX) c.m = (in && (x > c.m))? x : c.m;
+	}
+
+// lane l takes lane l + off's share when `mine`
+template <int WHAT>
+__device__ __forceinline__ void mx_fold (MxAcc& c, int off, bool mine)
+	{
+	if ((WHAT == GDSP_MATRIX_SUM) || (WHAT == GDSP_MATRIX_MEAN))
+		{
+		double tt[XS_K];
+#pragma unroll
+		for (int j=0 ; j<XS_K ; j++) tt[j] = __shfl_down (c.a[j], off, 64);
+#pragma unroll
+		for (int j=0 ; j<XS_K ; j++) xs_grow_or_flag (c.a, mine? tt[j] : 0.0, c.flag);
+		const uint32_t of = __shfl_down (c.flag, off, 64);
+		c.flag |= mine? of : 0u;
+		}
+	if ((WHAT == GDSP_MATRIX_COUNT) || (WHAT == GDSP_MATRIX_MEAN))
+		{
+		const uint32_t oc = __shfl_down (c.cnt, off, 64);
+		c.cnt += mine? oc : 0u;
+		}
+	if ((WHAT == GDSP_MATRIX_MIN) || (WHAT == GDSP_MATRIX_MAX))
+		{
+		const double om = __shfl_down (c.m, off, 64);
+		const bool better = (WHAT == GDSP_MATRIX_MIN)? (om < c.m) : (om > c.m);
+		c.m = (mine && better)? om : c.m;
+		}
+	}
+
+// the cell's figure; `later` when the host has to compute it
+template <int WHAT>
+__device__ __forceinline__ double mx_finish (const MxAcc& c, bool& later)
+	{
+	later = false;
+	if (WHAT == GDSP_MATRIX_COUNT) return (double) c.cnt;
+	if (WHAT == GDSP_MATRIX_MIN) return (c.m ==  HUGE_VAL)? NAN : __dadd_rn (c.m, 0.0);     // (-0.0 + 0.0 is +0.0)
+	if (WHAT == GDSP_MATRIX_MAX) return (c.m == -HUGE_VAL)? NAN : __dadd_rn (c.m, 0.0);
+	// a0 + a1 is the exact sum: s is it rounded once, e what the rounding left
+	const double s  = __dadd_rn (c.a[0], c.a[1]);
+	const double bp = __dsub_rn (s, c.a[0]);
+	const double e  = __dadd_rn (__dsub_rn (c.a[0], __dsub_rn (s, bp)), __dsub_rn (c.a[1], bp));
+	if (WHAT == GDSP_MATRIX_SUM)
+		{
+		later = (c.flag != 0) || !xs_finite (s);
+		return later? NAN : __dadd_rn (s, 0.0);
+		}
+	if (c.cnt == 0) return NAN;                                          // (only +0.0 was added: nothing is flagged)
+	later = (c.flag != 0) || !xs_finite (s);
+	const double n = (double) c.cnt;                                     // an integer below 2^32: exact
+	const double q = __ddiv_rn (s, n);
+	// e == 0: the exact sum is the double s, so the division's operands are exact and q is the exact quotient rounded once
+	if (later || (e == 0.0)) return later? NAN : q;
+	// a count that is a power of two: dividing by it moves the exponent alone (s is far from the subnormals), so rounding
+	// and dividing commute and S / n rounded once is s / n.  (Half of these are ties the test below would give away.)
+	const uint32_t sExp = (uint32_t) ((unsigned long long) __double_as_longlong (s) >> 52) & 0x7FF;
+	if (((c.cnt & (c.cnt - 1)) == 0) && (sExp >= 128)) return q;
+	// The exact sum is S = s + e with e != 0, |e| <= ulp(s)/2, and the mean is S / n.  Take a candidate q1 -- q moved by
+	// the remainder it left, fl(fl(r + e) / n) with r = s - q n from one fma; how good that step is decides only how
+	// often the test below passes, not what it proves -- and test the candidate itself:
+	//   r1 = fma (-q1, n, s) is s - q1 n EXACTLY.  q1 lies within three ulps of s / n, so |s - q1 n| <= 3 ulp(q1) n, and
+	//   the value is a multiple of ulp(q1): q1 n is one, and s is a multiple of ulp(s) >= ulp(q1) because |q1| <= |s|
+	//   up to that rounding.  A multiple of ulp(q1) below 2^34 ulp(q1) is a double (everything here is far from the
+	//   subnormals and from overflow: the exponents of s and q1 are held to 128 .. 1900 of 2047), so the fma rounds nothing.
+	//   (An fma that did round would have met a remainder of 2^53 ulp(q1) or more, which fails the test below: nothing
+	//   is accepted on the strength of the candidate being close.)
+	//   Then S / n - q1 = (r1 + e) / n, and q1 is S / n rounded to nearest iff |r1 + e| < h n, h = ulp(q1)/2, provided q1
+	//   is not a power of two (below one the doubles lie twice as dense, and the bound on that side would be h/2).
+	//   h n is exact (a power of two times an integer below 2^32).  t = fl(r1 + e) is off by at most 2^-53 of itself, and
+	//   so is the product with 1 - 2^-40: t < fl(h n (1 - 2^-40)) implies |r1 + e| < h n strictly.  A tie, |r1 + e| = h n,
+	//   and everything within 2^-40 of one fails the test and goes to the host, as does a power of two.
+	const double r  = __fma_rn (-q, n, s);
+	const double q1 = __dadd_rn (q, __ddiv_rn (__dadd_rn (r, e), n));
+	const double r1 = __fma_rn (-q1, n, s);
+	const double t  = fabs (__dadd_rn (r1, e));
+	const unsigned long long qb = (unsigned long long) __double_as_longlong (q1), sb = (unsigned long long) __double_as_longlong (s);
+	const uint32_t qe = (uint32_t) (qb >> 52) & 0x7FF, se = (uint32_t) (sb >> 52) & 0x7FF;
+	const bool inRange = (qe >= 128) && (qe <= 1900) && (se >= 128) && (se <= 1900) && ((qb & 0xFFFFFFFFFFFFFull) != 0);
+	const double h = __longlong_as_double ((long long) ((unsigned long long) ((qe >= 128)? qe - 53 : 75) << 52));   // 2^(qe - 1076) = ulp(q1)/2
+	later = !(inRange && (t < __dmul_rn (__dmul_rn (h, n), 1.0 - 0x1p-40)));
+	return later? NAN : q1;
+	}
+
+// the figure of a cell with an empty sample
+template <int WHAT>
+__device__ __forceinline__ double mx_empty (void)
+	{ return ((WHAT == GDSP_MATRIX_COUNT) || (WHAT == GDSP_MATRIX_SUM))? 0.0 : NAN; }
+
+__device__ __forceinline__ void mx_later (uint32_t* __restrict__ todo, uint32_t* __restrict__ ntodo, uint32_t cell)
+	{ todo[atomicAdd (ntodo, 1u)] = cell; }                                // (a cell is finished once: at most the launch's cells)
+
+// the same for the cells of a whole wave, which calls it with all its lanes: one atomic for all that are `later`
+__device__ __forceinline__ void mx_later_wave (uint32_t* __restrict__ todo, uint32_t* __restrict__ ntodo, bool later, uint32_t cell)
+	{
+	const unsigned long long mask = __ballot (later);
+	if (mask == 0) return;
+	const uint32_t lane   = threadIdx.x & 63;
+	const uint32_t leader = (uint32_t) __ffsll ((long long) mask) - 1;
+	uint32_t base = 0;
+	if (lane == leader) base = atomicAdd (ntodo, (uint32_t) __popcll (mask));
+	base = __shfl (base, (int) leader, 64);
+	if (later) todo[base + (uint32_t) __popcll (mask & ((1ull << lane) - 1))] = cell;
+	}
+
+template <int WHAT, int ROUTE>
+__global__ __launch_bounds__(MX_THREADS)
+void matrix_kernel (MxBatch P, const uint32_t* __restrict__ d_pos, const uint32_t* __restrict__ d_code, uint32_t count,
+                    int32_t offLo, uint32_t noffsets, uint32_t bin, uint32_t group, double lo, double hi,
+                    double* __restrict__ out, uint32_t* __restrict__ todo, uint32_t* __restrict__ ntodo)
+	{
+	__shared__ double stage[(ROUTE == MX_ROUTE_NARROW)? MX_WAVES * MX_STAGE_PAD : 1];
+	const uint32_t lane  = threadIdx.x & 63;
+	const uint32_t wave  = threadIdx.x >> 6;
+	const uint32_t ncols = noffsets / bin;
+	const uint32_t nwave = gridDim.x * MX_WAVES;
+
+	for (uint32_t row=blockIdx.x*MX_WAVES+wave ; row<count ; row+=nwave)
+		{
+		const uint32_t code = __builtin_amdgcn_readfirstlane (d_code[row]);
+		const uint32_t vec  = (code >> 1) - P.vec0;
+		if (vec >= P.nvec) continue;                                  // (a vector of another launch sequence)
+		const double* __restrict__ v = P.v[vec];
+		const int64_t n     = (int64_t) P.n[vec];
+		const int64_t p     = (int64_t) __builtin_amdgcn_readfirstlane (d_pos[row]);
+		const bool    minus = (code & 1) != 0;
+		// the window is the bases g0 .. g0 + noffsets - 1; ascending cell c is column c, or ncols - 1 - c on the minus strand
+		const int64_t g0    = minus? p - (int64_t) offLo - (int64_t) (noffsets - 1) : p + (int64_t) offLo;
+		const uint32_t cell0 = row * ncols;                           // (the call's cells fit 32 bits: the host half sees to it)
+		double* __restrict__ rowOut = out + (size_t) row * ncols;
+		if (n == 0) continue;                                         // (no anchor lies in an empty vector)
+
+		if (ROUTE == MX_ROUTE_COPY)
+			{
+			for (uint32_t t=lane ; t<noffsets ; t+=64)
+				{
+				const int64_t g  = g0 + t;
+				const bool    in = (g >= 0) && (g < n);
+				const double  x  = in? v[g] : NAN;
+				const bool    take = !(x < lo) && !(x > hi) && xs_finite (x);
+				const uint32_t j = minus? noffsets - 1 - t : t;
+				double y;
+				if      (WHAT == GDSP_MATRIX_COUNT) y = take? 1.0 : 0.0;
+				else if (WHAT == GDSP_MATRIX_SUM)   y = take? __dadd_rn (x, 0.0) : 0.0;
+				else                                y = take? __dadd_rn (x, 0.0) : NAN;     // (one value is its own mean, min and max)
+				rowOut[j] = y;
+				}
+			}
+
+		if (ROUTE == MX_ROUTE_NARROW)
+			{
+			double* __restrict__ mine = stage + wave * MX_STAGE_PAD;
+			const uint32_t perPass = 64 / group;                           // cells of a stretch
+			const uint32_t cell = lane / group, r = lane % group;
+			for (uint32_t c0=0 ; c0<ncols ; c0+=perPass)
+				{
+				const uint32_t cells = (ncols - c0 < perPass)? ncols - c0 : perPass;
+				const uint32_t len   = cells * bin;                        // <= MX_STAGE
+				const int64_t  gc    = g0 + (int64_t) c0 * bin;
+				const bool     live  = cell < cells;
+				const uint32_t j     = minus? ncols - 1 - (c0 + cell) : c0 + cell;
+				if ((gc + len <= 0) || (gc >= n))                       // nothing of the stretch lies in the chromosome
+					{
+					if (live && (r == 0)) rowOut[j] = mx_empty<WHAT> ();
+					continue;
+					}
+				for (uint32_t i0=0 ; i0<len ; i0+=64*MX_STAGE_DEPTH)
+					{
+					double x[MX_STAGE_DEPTH];
+#pragma unroll
+					for (int u=0 ; u<MX_STAGE_DEPTH ; u++)                 // (every lane loads, index clamped: see gdsp_stage_f64)
+						{
+						const int64_t g  = gc + i0 + u*64 + lane;
+						const int64_t gi = (g < 0)? 0 : ((g >= n)? n - 1 : g);
+						const double  y  = v[gi];
+						x[u] = (g == gi)? y : NAN;
+						}
+#pragma unroll
+					for (int u=0 ; u<MX_STAGE_DEPTH ; u++)
+						{
+						const uint32_t i = i0 + u*64 + lane;
+						if (i < len) mine[i + (i >> 5)] = x[u];
+						}
+					}
+				__builtin_amdgcn_fence (__ATOMIC_RELEASE, "wavefront");     // the wave's stores, then the wave's loads
+				__builtin_amdgcn_wave_barrier ();
+				__builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "wavefront");
+
+				MxAcc c;
+				mx_clear<WHAT> (c);
+				const uint32_t base = live? cell * bin : 0;
+				for (uint32_t u=r ; u<bin ; u+=group)
+					{
+					const uint32_t i = base + u;
+					mx_take<WHAT> (c, mine[i + (i >> 5)], lo, hi);
+					}
+				for (uint32_t off=1 ; off<group ; off<<=1)
+					mx_fold<WHAT> (c, (int) off, (r & (2*off - 1)) == 0);
+				bool later;
+				const double y     = mx_finish<WHAT> (c, later);
+				const bool   owner = live && (r == 0);
+				if (owner) rowOut[j] = y;
+				if ((WHAT == GDSP_MATRIX_SUM) || (WHAT == GDSP_MATRIX_MEAN)) mx_later_wave (todo, ntodo, owner && later, cell0 + j);
+				__builtin_amdgcn_fence (__ATOMIC_RELEASE, "wavefront");     // the wave's loads, then the next stretch's stores
+				__builtin_amdgcn_wave_barrier ();
+				__builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "wavefront");
+				}
+			}
+
+		if (ROUTE == MX_ROUTE_WIDE)
+			{
+			for (uint32_t c0=0 ; c0<ncols ; c0++)
+				{
+				// offsets [tLo, tHi) of the window, cut to the chromosome
+				int64_t tLo = (int64_t) c0 * bin, tHi = tLo + bin;
+				if (tLo < -g0)    tLo = -g0;
+				if (tHi > n - g0) tHi = n - g0;
+				const uint32_t j = minus? ncols - 1 - c0 : c0;
+				if (tLo >= tHi)
+					{
+					if (lane == 0) rowOut[j] = mx_empty<WHAT> ();
+					continue;
+					}
+				MxAcc c, d;
+				mx_clear<WHAT> (c);
+				mx_clear<WHAT> (d);
+				int64_t i = tLo + lane;
+				for ( ; i+192<tHi ; i+=256)
+					{
+					const double x0 = v[g0+i], x1 = v[g0+i+64], x2 = v[g0+i+128], x3 = v[g0+i+192];
+					mx_take<WHAT> (c, x0, lo, hi);  mx_take<WHAT> (d, x1, lo, hi);
+					mx_take<WHAT> (c, x2, lo, hi);  mx_take<WHAT> (d, x3, lo, hi);
+					}
+				for ( ; i+64<tHi ; i+=128)
+					{
+					const double x0 = v[g0+i], x1 = v[g0+i+64];
+					mx_take<WHAT> (c, x0, lo, hi);  mx_take<WHAT> (d, x1, lo, hi);
+					}
+				if (i < tHi) mx_take<WHAT> (c, v[g0+i], lo, hi);
+				// the lane's two shares, then the wave's 64 as a tree
+				if ((WHAT == GDSP_MATRIX_SUM) || (WHAT == GDSP_MATRIX_MEAN))
+					{
+#pragma unroll
+					for (int k=0 ; k<XS_K ; k++) xs_grow_or_flag (c.a, d.a[k], c.flag);
+					c.flag |= d.flag;
+					}
+				c.cnt += d.cnt;
+				if (WHAT == GDSP_MATRIX_MIN) c.m = (d.m < c.m)? d.m : c.m;
+				if (WHAT == GDSP_MATRIX_MAX) c.m = (d.m > c.m)? d.m : c.m;
+				for (int off=1 ; off<64 ; off<<=1)
+					mx_fold<WHAT> (c, off, (lane & (2*off - 1)) == 0);
+				if (lane == 0)
+					{
+					bool later;
+					rowOut[j] = mx_finish<WHAT> (c, later);
+					if (later) mx_later (todo, ntodo, cell0 + j);
+					}
+				}
+			}
+		}
+	}
+
+// *d_bad = 1 when some anchor names a vector the call does not have or a position outside its vector
+__global__ void matrix_check_kernel (const uint32_t* __restrict__ d_pos, const uint32_t* __restrict__ d_code, uint32_t count,
+                                     const uint32_t* __restrict__ d_n, uint32_t nvec, uint32_t* __restrict__ d_bad)
+	{
+	bool bad = false;
+	for (uint32_t i=blockIdx.x*blockDim.x+threadIdx.x ; i<count ; i+=gridDim.x*blockDim.x)
+		{
+		const uint32_t vec = d_code[i] >> 1;
+		bad |= (vec >= nvec) || (d_pos[i] >= d_n[(vec < nvec)? vec : 0]);
+		}
+	if (bad) atomicOr (d_bad, 1u);
+	}
+
+// ---------------------------------------------------------------------------------------------- host ----
+static uint32_t mxLaunchRows = 0;                            // see gdsp_matrix_set_launch_rows
+static uint64_t mxLast[4];                                   // see gdsp_genome_matrix_last
+
+static int mx_check_shape (int32_t offLo, uint32_t noffsets, uint32_t bin, int what)
+	{
+	GDSP_REQUIRE ((noffsets >= 1) && (noffsets <= MX_MAX_OFFSETS), "the number of offsets must be 1 .. 16384");
+	GDSP_REQUIRE ((int64_t) offLo + noffsets - 1 <= INT32_MAX, "the last offset is beyond int32");
+	GDSP_REQUIRE ((bin >= 1) && (noffsets % bin == 0), "the bin must divide the number of offsets");
+	GDSP_REQUIRE ((what >= GDSP_MATRIX_MEAN) && (what <= GDSP_MATRIX_MAX), "the figure is one of GDSP_MATRIX_*");
+	return GDSP_OK;
+	}
+
+template <int WHAT>
+static void mx_launch_route (const MxBatch& B, dim3 grid, hipStream_t s, const uint32_t* d_pos, const uint32_t* d_code, uint32_t count,
+                             int32_t offLo, uint32_t noffsets, uint32_t bin, double lo, double hi, double* d_out, uint32_t* d_todo,
+                             uint32_t* d_ntodo)
+	{
+	const uint32_t group = (bin < 16)? 1u : ((bin < 64)? 4u : 16u);
+	if (bin == 1)
+		hipLaunchKernelGGL ((matrix_kernel<WHAT, MX_ROUTE_COPY>), grid, dim3 (MX_THREADS), 0, s, B, d_pos, d_code, count, offLo, noffsets,
+		                    bin, group, lo, hi, d_out, d_todo, d_ntodo);
+	else if (bin < MX_NARROW_BELOW)
+		hipLaunchKernelGGL ((matrix_kernel<WHAT, MX_ROUTE_NARROW>), grid, dim3 (MX_THREADS), 0, s, B, d_pos, d_code, count, offLo, noffsets,
+		                    bin, group, lo, hi, d_out, d_todo, d_ntodo);
+	else
+		hipLaunchKernelGGL ((matrix_kernel<WHAT, MX_ROUTE_WIDE>), grid, dim3 (MX_THREADS), 0, s, B, d_pos, d_code, count, offLo, noffsets,
+		                    bin, group, lo, hi, d_out, d_todo, d_ntodo);
+	}
+
+// the launch sequences of one call (arguments checked, every anchor inside its vector); *launches counts them
+static int mx_launch (const gdsp_batch_item* items, int nitems, const uint32_t* d_pos, const uint32_t* d_code, uint32_t count,
+                      int32_t offLo, uint32_t noffsets, uint32_t bin, int what, double lo, double hi, double* d_out,
+                      uint32_t* d_todo, uint32_t* d_ntodo, hipStream_t s, uint64_t* launches)
+	{
+	static_assert ((MX_STAGE % 32 == 0) && (64 * 15 <= MX_STAGE) && (16 * 63 <= MX_STAGE) && (4 * (MX_NARROW_BELOW - 1) <= MX_STAGE), "a stretch holds 64 / G cells");
+	const dim3 grid (std::min<uint32_t> ((count + MX_WAVES - 1) / MX_WAVES, MX_WG_TARGET));
+	for (int i0=0 ; i0<nitems ; i0+=GDSP_BATCH_MAX)
+		{
+		MxBatch B;
+		B.vec0 = (uint32_t) i0;
+		B.nvec = (uint32_t) std::min (nitems - i0, GDSP_BATCH_MAX);
+		for (int j=0 ; j<GDSP_BATCH_MAX ; j++)
+			{
+			const bool have = (uint32_t) j < B.nvec;
+			B.v[j] = have? items[i0+j].d_in : NULL;
+			B.n[j] = have? items[i0+j].n    : 0;
+			}
+		switch (what)
+			{
+			case GDSP_MATRIX_MEAN:  mx_launch_route<GDSP_MATRIX_MEAN>  (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
+			case GDSP_MATRIX_SUM:   mx_launch_route<GDSP_MATRIX_SUM>   (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
+			case GDSP_MATRIX_COUNT: mx_launch_route<GDSP_MATRIX_COUNT> (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
+			case GDSP_MATRIX_MIN:   mx_launch_route<GDSP_MATRIX_MIN>   (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
+			default:                mx_launch_route<GDSP_MATRIX_MAX>   (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
+			}
+		GDSP_LAUNCH_CHECK ();
+		if (launches != NULL) (*launches)++;
+		}
+	return GDSP_OK;
+	}
+
+static int mx_check_items (const gdsp_batch_item* items, int nitems)
+	{
+	GDSP_REQUIRE (nitems >= 0, "a negative number of vectors");
+	GDSP_REQUIRE ((nitems == 0) || (items != NULL), "NULL items");
+	for (int i=0 ; i<nitems ; i++)
+		GDSP_REQUIRE ((items[i].n == 0) || ((items[i].d_in != NULL) && ((((uintptr_t) items[i].d_in) & 7) == 0)), "a vector must be 8-byte aligned");
+	return GDSP_OK;
+	}
+
+extern "C" {
+
+int gdsp_matrix_set_launch_rows (uint32_t rows) { mxLaunchRows = rows;  return GDSP_OK; }
+
+void gdsp_genome_matrix_last (uint64_t out[4]) { memcpy (out, mxLast, sizeof(mxLast)); }
+
+int gdsp_matrix_rows_batch (const gdsp_batch_item* items, int nitems, const uint32_t* d_pos, const uint32_t* d_code, uint32_t count,
+                            int32_t offLo, uint32_t noffsets, uint32_t bin, int what, double lo, double hi, double* d_out,
+                            uint32_t* d_todo, uint32_t* d_ntodo, void* stream)
+	{
+	int rc = mx_check_shape (offLo, noffsets, bin, what);
+	if (rc == GDSP_OK) rc = mx_check_items (items, nitems);
+	if (rc != GDSP_OK) return rc;
+	GDSP_REQUIRE ((count == 0) || ((d_pos != NULL) && (d_code != NULL)), "NULL anchors");
+	GDSP_REQUIRE ((count == 0) || (nitems > 0), "anchors without a vector");
+	GDSP_REQUIRE ((count == 0) || ((d_out != NULL) && (d_todo != NULL) && (d_ntodo != NULL)), "NULL rows or to-do list");
+	GDSP_REQUIRE ((uint64_t) count * (noffsets / bin) <= UINT32_MAX, "more than 2^32 - 1 cells in one call");
+	hipStream_t s = gdsp_stream (stream);
+	if (count == 0) return GDSP_OK;
+
+	// every anchor inside its vector, decided on the device, where the anchors are
+	{
+	std::vector<uint32_t> h_n (nitems);
+	for (int i=0 ; i<nitems ; i++) h_n[i] = items[i].n;
+	uint32_t* d_work = NULL;                                    // the flag, then the lengths
+	if (hipMalloc ((void**) &d_work, (size_t) (nitems + 1) * sizeof(uint32_t)) != hipSuccess)
+		{ gdsp_set_error ("%s: no device memory for the anchor check", __func__);  return GDSP_ENOMEM; }
+	uint32_t bad = 0;
+	hipError_t e = hipMemsetAsync (d_work, 0, sizeof(uint32_t), s);
+	if (e == hipSuccess) e = hipMemcpyAsync (d_work + 1, h_n.data (), (size_t) nitems * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+	if (e == hipSuccess) e = hipStreamSynchronize (s);           // (h_n is pageable: the copy has left it)
+	if (e == hipSuccess)
+		{
+		uint32_t g = (count + 255) / 256;
+		if (g > 1024) g = 1024;
+		hipLaunchKernelGGL (matrix_check_kernel, dim3 (g), dim3 (256), 0, s, d_pos, d_code, count, d_work + 1, (uint32_t) nitems, d_work);
+		e = hipGetLastError ();
+		}
+	if (e == hipSuccess) e = hipMemcpyAsync (&bad, d_work, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess) e = hipStreamSynchronize (s);
+	(void) hipFree (d_work);
+	GDSP_HIP_TRY (e);
+	GDSP_REQUIRE (bad == 0, "an anchor lies outside its vector");
+	}
+	return mx_launch (items, nitems, d_pos, d_code, count, offLo, noffsets, bin, what, lo, hi, d_out, d_todo, d_ntodo, s, NULL);
+	}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------- end to end ----
+namespace {
+
+// what a device holds during its share of the call
+struct MxHeld
+	{
+	std::vector<void*> bufs;
+	int alloc (void** p, size_t bytes, const char* what)
+		{
+		if (hipMalloc (p, bytes) != hipSuccess)
+			{ *p = NULL;  gdsp_set_error ("gdsp_genome_matrix: no device memory for the %s", what);  return GDSP_ENOMEM; }
+		bufs.push_back (*p);
+		return GDSP_OK;
+		}
+	~MxHeld () { for (void* b : bufs) (void) hipFree (b); }
+	};
+
+double mx_figure_of (const gdsp_interval_stat& st, int what)
+	{
+	switch (what)
+		{
+		case GDSP_MATRIX_MEAN:  return st.mean;
+		case GDSP_MATRIX_SUM:   return st.sum;
+		case GDSP_MATRIX_COUNT: return (double) st.count;
+		case GDSP_MATRIX_MIN:   return st.min;
+		default:                return st.max;
+		}
+	}
+
+// the current device's sources mine[0 .. nmine) (indices into `sources`, the caller's order) and all their rows
+int mx_on_device (const gdsp_profile_source* sources, const int* mine, int nmine, int32_t offLo, uint32_t noffsets, uint32_t bin,
+                  int what, double lo, double hi, double* const* h_rows)
+	{
+	const uint32_t ncols = noffsets / bin;
+	std::vector<gdsp_batch_item> items (nmine);
+	std::vector<uint64_t> first (nmine + 1, 0);                   // the device's rows: source k owns first[k] .. first[k+1]
+	std::vector<uint32_t> pos, code;
+	for (int k=0 ; k<nmine ; k++)
+		{
+		const gdsp_profile_source& S = sources[mine[k]];
+		memset (&items[k], 0, sizeof(items[k]));
+		items[k].d_in = S.d_v;  items[k].n = S.n;
+		for (uint32_t a=0 ; a<S.nanchors ; a++)
+			{
+			pos.push_back (S.h_pos[a]);
+			code.push_back ((uint32_t) k * 2 + (((S.h_minus != NULL) && (S.h_minus[a] != 0))? 1u : 0u));
+			}
+		first[k+1] = first[k] + S.nanchors;
+		}
+	const uint64_t na = first[nmine];
+	if (na == 0) return GDSP_OK;
+	GDSP_REQUIRE (na <= UINT32_MAX, "more than 2^32 - 1 anchors on a device");
+	hipStream_t s = gdsp_stream (sources[mine[0]].stream);
+
+	uint64_t perLaunch = std::max<uint64_t> (1, MX_LAUNCH_CELLS / ncols);
+	if (mxLaunchRows != 0) perLaunch = std::min<uint64_t> (perLaunch, mxLaunchRows);
+	perLaunch = std::min (perLaunch, na);
+	const size_t cells = (size_t) perLaunch * ncols;
+
+	MxHeld held;
+	uint32_t *d_anchors = NULL, *d_todo = NULL;
+	double*   d_out = NULL;
+	int rc = held.alloc ((void**) &d_anchors, 2 * na * sizeof(uint32_t), "anchors");
+	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_out, cells * sizeof(double), "rows");
+	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_todo, (cells + 1) * sizeof(uint32_t), "to-do list");     // the counter, then the list
+	if (rc != GDSP_OK) return rc;
+	GDSP_HIP_TRY (hipMemcpyAsync (d_anchors,      pos.data (),  na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+	GDSP_HIP_TRY (hipMemcpyAsync (d_anchors + na, code.data (), na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+
+	std::vector<uint32_t> todo, tVec, tStart, tEnd;
+	std::vector<double*>  tWhere;
+	std::vector<gdsp_interval_stat> tStat;
+	for (uint64_t r0=0 ; r0<na ; r0+=perLaunch)
+		{
+		const uint32_t nr = (uint32_t) std::min<uint64_t> (perLaunch, na - r0);
+		uint32_t ntodo = 0;
+		GDSP_HIP_TRY (hipMemsetAsync (d_todo, 0, sizeof(uint32_t), s));
+		rc = mx_launch (items.data (), nmine, d_anchors + r0, d_anchors + na + r0, nr, offLo, noffsets, bin, what, lo, hi,
+		                d_out, d_todo + 1, d_todo, s, &mxLast[3]);
+		if (rc != GDSP_OK) return rc;
+		GDSP_HIP_TRY (hipMemcpyAsync (&ntodo, d_todo, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+		// the rows, to the sources that own them
+		int k = (int) (std::upper_bound (first.begin (), first.end (), r0) - first.begin ()) - 1;
+		for (uint64_t a=r0 ; a<r0+nr ; )
+			{
+			while (first[k+1] <= a) k++;
+			const uint64_t b = std::min<uint64_t> (first[k+1], r0 + nr);
+			GDSP_HIP_TRY (hipMemcpyAsync (h_rows[mine[k]] + (size_t) (a - first[k]) * ncols, d_out + (size_t) (a - r0) * ncols,
+			                              (size_t) (b - a) * ncols * sizeof(double), hipMemcpyDeviceToHost, s));
+			a = b;
+			}
+		GDSP_HIP_TRY (hipStreamSynchronize (s));
+		if (ntodo == 0) continue;
+
+		// the cells the device left: each is one interval of its chromosome, computed by the exact interval call
+		GDSP_REQUIRE (ntodo <= (uint64_t) nr * ncols, "the to-do list is longer than the launch");
+		todo.resize (ntodo);
+		GDSP_HIP_TRY (hipMemcpyAsync (todo.data (), d_todo + 1, (size_t) ntodo * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+		GDSP_HIP_TRY (hipStreamSynchronize (s));
+		tVec.clear ();  tStart.clear ();  tEnd.clear ();  tWhere.clear ();
+		for (uint32_t t=0 ; t<ntodo ; t++)
+			{
+			const uint64_t a = r0 + todo[t] / ncols;
+			const uint32_t j = todo[t] % ncols;
+			const int kk = (int) (std::upper_bound (first.begin (), first.end (), a) - first.begin ()) - 1;
+			const int64_t n = items[kk].n, p = pos[a];
+			const int64_t kLo = (int64_t) offLo + (int64_t) j * bin, kHi = kLo + bin - 1;
+			int64_t gLo = (code[a] & 1)? p - kHi : p + kLo;
+			int64_t gHi = (code[a] & 1)? p - kLo : p + kHi;
+			gLo = std::max<int64_t> (gLo, 0);  gHi = std::min<int64_t> (gHi, n - 1);
+			double* where = h_rows[mine[kk]] + (size_t) (a - first[kk]) * ncols + j;
+			if (gLo > gHi) { *where = ((what == GDSP_MATRIX_COUNT) || (what == GDSP_MATRIX_SUM))? 0.0 : NAN;  continue; }
+			tVec.push_back ((uint32_t) kk);  tStart.push_back ((uint32_t) gLo);  tEnd.push_back ((uint32_t) (gHi + 1));
+			tWhere.push_back (where);
+			}
+		tStat.resize (tWhere.size ());
+		rc = gdsp_interval_stats_batch (items.data (), nmine, tVec.data (), tStart.data (), tEnd.data (), (uint32_t) tWhere.size (),
+		                                lo, hi, tStat.data (), (void*) s);
+		if (rc != GDSP_OK) return rc;
+		for (size_t t=0 ; t<tWhere.size () ; t++) *tWhere[t] = mx_figure_of (tStat[t], what);
+		mxLast[2] += ntodo;
+		}
+	return GDSP_OK;
+	}
+
+} // namespace
+
+extern "C" {
+
+int gdsp_genome_matrix (const gdsp_profile_source* sources, int nsources, int32_t offLo, uint32_t noffsets, uint32_t bin, int what,
+                        double lo, double hi, double* const* h_rows)
+	{
+	GDSP_REQUIRE (nsources >= 0, "a negative number of sources");
+	GDSP_REQUIRE ((nsources == 0) || ((sources != NULL) && (h_rows != NULL)), "NULL sources or rows");
+	int rc = mx_check_shape (offLo, noffsets, bin, what);
+	if (rc != GDSP_OK) return rc;
+	memset (mxLast, 0, sizeof(mxLast));
+	const uint32_t ncols = noffsets / bin;
+	for (int i=0 ; i<nsources ; i++)
+		{
+		GDSP_REQUIRE ((sources[i].nanchors == 0) || ((sources[i].h_pos != NULL) && (h_rows[i] != NULL)), "NULL anchors or rows");
+		GDSP_REQUIRE ((sources[i].n == 0) || ((sources[i].d_v != NULL) && ((((uintptr_t) sources[i].d_v) & 7) == 0)), "a vector must be 8-byte aligned");
+		for (uint32_t k=0 ; k<sources[i].nanchors ; k++)
+			GDSP_REQUIRE (sources[i].h_pos[k] < sources[i].n, "an anchor lies outside its vector");
+		mxLast[0] += sources[i].nanchors;
+		}
+	mxLast[1] = mxLast[0] * ncols;
+
+	int home = 0;
+	GDSP_HIP_TRY (hipGetDevice (&home));
+	std::vector<int> devices;
+	for (int i=0 ; i<nsources ; i++) devices.push_back (sources[i].device);
+	std::sort (devices.begin (), devices.end ());
+	devices.erase (std::unique (devices.begin (), devices.end ()), devices.end ());
+	std::vector<int> mine;
+	for (size_t d=0 ; (d<devices.size ()) && (rc == GDSP_OK) ; d++)
+		{
+		mine.clear ();
+		for (int i=0 ; i<nsources ; i++) { if (sources[i].device == devices[d]) mine.push_back (i); }
+		if (hipSetDevice (devices[d]) != hipSuccess)
+			{ gdsp_set_error ("gdsp_genome_matrix: device %d cannot be selected", devices[d]);  rc = GDSP_EHIP;  break; }
+		rc = mx_on_device (sources, mine.data (), (int) mine.size (), offLo, noffsets, bin, what, lo, hi, h_rows);
+		}
+	(void) hipSetDevice (home);
+	return rc;
+	}
+
+} // extern "C"

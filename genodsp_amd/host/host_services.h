@@ -70,6 +70,31 @@ char* put_value         (char* p, valtype v, int precision);
 /* count, sum and then mean, min, max, summit or four NA, each behind a tab, and the newline: at most 1647 characters */
 char* put_interval_figures (char* p, const gdsp_interval_stat* stat, u32 chromStart, int originOne, int precision);
 
+/* what profileover and matrixover share: the options that name the anchors of a file and the offsets around them
+ * (--flank= | --upstream= --downstream=, --bin=, --anchor=, --strand=, --origin=, and the refusal of a window), the
+ * complaints of the finished command line (check sets upstream and downstream), and the reader of the file: every
+ * interval gives one anchor, from the interval as the file has it; an anchor outside its chromosome's vector is skipped
+ * and counted.  anc[i] are the anchors of parts[i], as the library takes them */
+enum { anchor_start = 0, anchor_end = 1, anchor_center = 2 };
+typedef struct anchor_opts
+	{
+	int       originOne;
+	int       haveFlank, haveUp, haveDown;
+	long long flank, upstream, downstream;
+	int       anchor, strandColumn;           /* strandColumn: zero-based, -1 when every anchor is plus */
+	long long bin;
+	} anchor_opts;
+typedef struct anchors { u32 *pos, *minus;  u32 count, cap; } anchors;
+typedef void (*anchor_used_fn) (void* ctx, int part, u32 index, u32 start, u32 end, int minus);   /* start, end: as the file has them */
+void  anchor_opts_init  (anchor_opts* o);
+int   anchor_opts_take  (anchor_opts* o, char* name, char* arg);
+void  anchor_opts_check (anchor_opts* o, char* name);
+int   read_anchor_line  (char* name, char* filename, FILE* f, char* line, int lineLen, u64* lineNumber, int strandCol,
+                         char** chrom, u32* start, u32* end, int* minus);
+long long anchor_of     (long long s, long long e, int minus, int anchor);
+void  read_anchor_file  (char* name, char* filename, const anchor_opts* o, const sigpart* parts, int nsrc, anchors* anc,
+                         u64* numRead, u64* numUsed, u64* numSkipped, anchor_used_fn used, void* usedCtx);
+
 /* ops_fused.c: run op (and the operators after it, up to stopOp) as one fused kernel when
  * the chain is one the device library fuses; returns how many operators were consumed (0 = none) */
 int   try_fused_apply   (dspop* op, dspop* stopOp, spec* s);

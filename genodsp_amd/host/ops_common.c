@@ -231,3 +231,177 @@ char* put_interval_figures (char* p, const gdsp_interval_stat* stat, u32 chromSt
 	*(p++) = '\n';
 	return p;
 	}
+
+/* ------------------------------------------------------------- anchors of a file (profileover, matrixover) ---- */
+static long long bases_arg (char* name, char* arg, char* argVal, const char* what)
+	{
+	int n = string_to_unitized_int (argVal, /*thousands*/ true);
+	if (n < 0) chastise ("[%s] %s can't be negative (\"%s\")\n", name, what, arg);
+	return n;
+	}
+
+void anchor_opts_init (anchor_opts* o)
+	{
+	memset (o, 0, sizeof(*o));
+	o->originOne    = (int) get_named_global ("originOne", false);
+	o->strandColumn = -1;
+	o->anchor       = anchor_start;
+	o->bin          = 1;
+	}
+
+int anchor_opts_take (anchor_opts* o, char* name, char* arg)
+	{
+	char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
+	if (strcmp_prefix (arg, "--flank=") == 0)      { o->flank      = bases_arg (name, arg, argVal, "the flank");            o->haveFlank = true;  return true; }
+	if (strcmp_prefix (arg, "--upstream=") == 0)   { o->upstream   = bases_arg (name, arg, argVal, "the upstream reach");   o->haveUp    = true;  return true; }
+	if (strcmp_prefix (arg, "--downstream=") == 0) { o->downstream = bases_arg (name, arg, argVal, "the downstream reach"); o->haveDown  = true;  return true; }
+	if (strcmp_prefix (arg, "--bin=") == 0)
+		{
+		int b = string_to_unitized_int (argVal, /*thousands*/ true);
+		if (b < 1) chastise ("[%s] the bin must be at least one base (\"%s\")\n", name, arg);
+		o->bin = b;
+		return true;
+		}
+	if (strcmp_prefix (arg, "--anchor=") == 0)
+		{
+		if      (strcmp (argVal, "start")  == 0) o->anchor = anchor_start;
+		else if (strcmp (argVal, "end")    == 0) o->anchor = anchor_end;
+		else if ((strcmp (argVal, "center") == 0) || (strcmp (argVal, "centre") == 0)) o->anchor = anchor_center;
+		else chastise ("[%s] the anchor is the interval's start, end or center (\"%s\")\n", name, arg);
+		return true;
+		}
+	if (strcmp_prefix (arg, "--strand=") == 0)
+		{
+		int col = string_to_int (argVal) - 1;
+		if (col == -1) chastise ("[%s] strand column can't be 0 (\"%s\")\n", name, arg);
+		if (col < 0)   chastise ("[%s] strand column can't be negative (\"%s\")\n", name, arg);
+		if (col < 3)   chastise ("[%s] strand column can't be 1, 2 or 3 (\"%s\")\n", name, arg);
+		o->strandColumn = col;
+		return true;
+		}
+	if (is_opt3 (arg, "window", "W"))
+		chastise ("[%s] every base the anchors reach is looked at: no window (\"%s\")\n", name, arg);
+	return origin_opt_take (arg, &o->originOne);
+	}
+
+void anchor_opts_check (anchor_opts* o, char* name)
+	{
+	if (o->haveFlank && (o->haveUp || o->haveDown))
+		chastise ("[%s] Can't use --flank with --upstream or --downstream\n", name);
+	if (!o->haveFlank && !(o->haveUp && o->haveDown))
+		chastise ("[%s] no offsets were provided (--flank=<bases>, or --upstream=<bases> and --downstream=<bases>)\n", name);
+	if (o->haveFlank) o->upstream = o->downstream = o->flank;
+	const long long noffsets = o->upstream + o->downstream + 1;
+	if (noffsets > GDSP_PROFILE_MAX_OFFSETS)
+		chastise ("[%s] at most %d offsets can be computed at once (%lld..%lld)\n", name, GDSP_PROFILE_MAX_OFFSETS, -o->upstream, o->downstream);
+	if (noffsets % o->bin != 0)
+		chastise ("[%s] the bin must divide the number of offsets (%lld does not divide %lld)\n", name, o->bin, noffsets);
+	}
+
+/* a line of the file as read_interval's serial loop (ingest.c) takes it -- track lines, blank lines and comments are
+ * passed over; chromosome, start and end are the first three fields -- and with it the strand: minus when field
+ * strandCol (zero-based; -1: none) begins with '-'.  false at the end of the file */
+int read_anchor_line (char* name, char* filename, FILE* f, char* line, int lineLen, u64* lineNumber, int strandCol,
+                      char** _chrom, u32* _start, u32* _end, int* _minus)
+	{
+	char *scan, *mark, *field;
+	for (;;)
+		{
+		if (fgets (line, lineLen, f) == NULL) return false;
+		(*lineNumber)++;
+		size_t len = strlen (line);
+		if ((len != 0) && (line[len-1] != '\n') && !feof (f))
+			{ fprintf (stderr, "[%s] in \"%s\", line %llu is longer than internal buffer\n", name, filename, (unsigned long long) *lineNumber);  exit (EXIT_FAILURE); }
+		if (strcmp_prefix (line, "track ") == 0) continue;
+		scan = skip_whitespace (line);
+		if ((*scan == 0) || (*scan == '#')) continue;
+		break;
+		}
+	const char* missing = NULL;
+	char* chrom = scan = line;
+	if (*scan == ' ') missing = "chromosome";
+	mark = skip_darkspace (scan);  scan = skip_whitespace (mark);  if (*mark != 0) *mark = 0;
+	if ((missing == NULL) && (*scan == 0)) missing = "interval start";
+	field = scan;
+	mark = skip_darkspace (scan);  scan = skip_whitespace (mark);  if (*mark != 0) *mark = 0;
+	u32 start = (missing == NULL)? (u32) string_to_u32 (field) : 0;
+	if ((missing == NULL) && (*scan == 0)) missing = "interval end";
+	field = scan;
+	mark = skip_darkspace (scan);  scan = skip_whitespace (mark);  if (*mark != 0) *mark = 0;
+	u32 end = (missing == NULL)? (u32) string_to_u32 (field) : 0;
+	int minus = false;
+	for (int col=3 ; (missing == NULL) && (col<=strandCol) ; col++)
+		{
+		if (*scan == 0) { missing = "strand";  break; }
+		field = scan;
+		mark = skip_darkspace (scan);  scan = skip_whitespace (mark);
+		if (col == strandCol) minus = (field[0] == '-');
+		}
+	if (missing != NULL)
+		{
+		fprintf (stderr, "[%s] in \"%s\", line %llu contains no %s\n", name, filename, (unsigned long long) *lineNumber, missing);
+		exit (EXIT_FAILURE);
+		}
+	*_chrom = chrom;  *_start = start;  *_end = end;  *_minus = minus;
+	return true;
+	}
+
+/* where the anchor of the zero-based half-open interval [s, e), s < e, lies */
+long long anchor_of (long long s, long long e, int minus, int anchor)
+	{
+	const long long half = (e - s - 1) / 2;
+	switch (anchor)
+		{
+		case anchor_end:    return minus? s : e - 1;
+		case anchor_center: return minus? e - 1 - half : s + half;
+		default:            return minus? e - 1 : s;
+		}
+	}
+
+/* the file: every interval's anchor, to its chromosome (parts[i] of the whole-chromosome signal; anc[i] zeroed by the
+ * caller).  `used`, when not NULL, sees every anchor that is used, in the file's order */
+void read_anchor_file (char* name, char* filename, const anchor_opts* o, const sigpart* parts, int nsrc, anchors* anc,
+                       u64* _numRead, u64* _numUsed, u64* _numSkipped, anchor_used_fn used, void* usedCtx)
+	{
+	const long long org = o->originOne? 1 : 0;
+	FILE* f = fopen (filename, "rt");
+	if (f == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for reading\n", name, filename);  exit (EXIT_FAILURE); }
+	for (int i=0 ; chromsSorted[i]!=NULL ; i++) chromsSorted[i]->flag = false;
+	char  line[1001], prevChrom[1001];
+	char* chrom;
+	u32   start, end;
+	int   minus, at = -1;
+	u64   lineNumber = 0, numRead = 0, numUsed = 0, numSkipped = 0;
+	spec* s = NULL;
+	prevChrom[0] = 0;
+	while (read_anchor_line (name, filename, f, line, sizeof(line), &lineNumber, o->strandColumn, &chrom, &start, &end, &minus))
+		{
+		if (strcmp (chrom, prevChrom) != 0)
+			{
+			s = find_chromosome_spec (chrom);  safe_strncpy (prevChrom, chrom, sizeof(prevChrom)-1);
+			at = -1;
+			for (int i=0 ; (s!=NULL) && (i<nsrc) ; i++) { if (parts[i].s == s) { at = i;  break; } }
+			if (at < 0) s = NULL;
+			}
+		if (s == NULL) continue;
+		if (!s->flag) { if (trackOperations) fprintf (stderr, "%s(%s)\n", name, chrom);  s->flag = true; }
+		numRead++;
+		const long long is = (long long) start - org, ie = (long long) end;
+		long long p = -1;
+		if (is < ie) p = anchor_of (is, ie, minus, o->anchor) - (long long) s->start;
+		if ((is >= ie) || (p < 0) || (p >= (long long) parts[at].n)) { numSkipped++;  continue; }
+		anchors* a = &anc[at];
+		if (a->count == a->cap)
+			{
+			if (a->cap >= (1u << 31)) { fprintf (stderr, "[%s] too many anchors on %s\n", name, chrom);  exit (EXIT_FAILURE); }
+			a->cap   = (a->cap == 0)? 1024 : 2*a->cap;
+			a->pos   = (u32*) must_alloc (realloc (a->pos,   a->cap * sizeof(u32)), name);
+			a->minus = (u32*) must_alloc (realloc (a->minus, a->cap * sizeof(u32)), name);
+			}
+		if (used != NULL) used (usedCtx, at, a->count, start, end, minus);
+		a->pos[a->count] = (u32) p;  a->minus[a->count] = (u32) minus;  a->count++;
+		numUsed++;
+		}
+	fclose (f);
+	*_numRead = numRead;  *_numUsed = numUsed;  *_numSkipped = numSkipped;
+	}

@@ -690,6 +690,46 @@ int gdsp_genome_profile_use_comm (gdsp_comm* comm);   /* NULL switches back to h
  * images (both passes), [3] q that were not finite */
 void gdsp_genome_profile_last (uint64_t out[4]);
 
+/* ---- matrixover (not in the reference): the signal around each anchor of a list, one row per anchor, exact -----------
+ * Anchors, offsets and bins are profileover's: an anchor is (vector, position p, strand s) with 0 <= p < n of its WHOLE
+ * chromosome vector; the offsets are offLo .. offLo + noffsets - 1 (1 .. GDSP_PROFILE_MAX_OFFSETS of them, the range inside
+ * int32); a bin b >= 1 divides noffsets and ncols = noffsets / b; offset k of an anchor looks at base p + s k.  Nothing is
+ * added up over the anchors here: the CELL (anchor, column j) is the set of bases p + s k, offLo + j b <= k <
+ * offLo + (j+1) b, that lie in [0, n) -- one interval of the chromosome, possibly empty; for a minus anchor column 0 holds
+ * the highest bases.  A cell's figures are exactly what the statsover section below defines for that interval and the
+ * limits lo, hi: count; sum (the exact sum rounded once, an exact zero +0.0); mean (the exact sum over count, rounded
+ * once); min and max (a zero result is +0.0); an empty sample has count 0, sum +0.0 and mean, min, max NaN.  One call
+ * computes ONE figure, `what`, as one double per cell (a count is exact in a double).  Each value is a function of its
+ * cell's sample alone: nothing depends on the launch split, grid, dispatch order or devices, on chromosome order or on
+ * the order of the anchors; a duplicated anchor gives two equal rows; nothing crosses a chromosome's end.
+ *
+ * gdsp_matrix_rows_batch writes the rows of `count` anchors -- items, d_pos and d_code as gdsp_profile_accumulate_batch
+ * takes them -- into d_out, count x ncols doubles, row-major, in the anchors' order (at most 2^32 - 1 cells).  A cell the
+ * device cannot finish exactly (a lane's two-term expansion was flagged or overflowed; a mean it cannot prove to be
+ * rounded once) is left to the caller: its index row * ncols + column is appended to d_todo (room for count x ncols entries)
+ * and counted in *d_ntodo, which the caller zeroes; what d_out holds there means nothing.  count, min and max are always
+ * finished, and so is every figure of integer read depth whose sums stay below 2^53.  One launch sequence per 32 vectors.
+ * GDSP_EINVAL for a bad range, a bin that does not divide noffsets, a figure that is none of the five, or an anchor
+ * outside its vector (decided on the device: the call waits for the stream once).
+ * gdsp_genome_matrix is the host half over profileover's source table: per device it uploads the anchors, launches
+ * bounded pieces (at most 2^25 cells of device output per launch; gdsp_matrix_set_launch_rows lowers the rows of a
+ * piece so that tests can force several, 0 restores the library's own number), reads the rows back into h_rows[i]
+ * (a HOST array of sources[i].nanchors x ncols doubles, in that source's anchor order) and computes the to-do cells with
+ * gdsp_interval_stats_batch over their intervals, which is exact on any input.  Nothing is reduced across devices. */
+#define GDSP_MATRIX_MEAN  0
+#define GDSP_MATRIX_SUM   1
+#define GDSP_MATRIX_COUNT 2
+#define GDSP_MATRIX_MIN   3
+#define GDSP_MATRIX_MAX   4
+int gdsp_matrix_rows_batch (const gdsp_batch_item* items, int nitems, const uint32_t* d_pos, const uint32_t* d_code, uint32_t count,
+                            int32_t offLo, uint32_t noffsets, uint32_t bin, int what, double lo, double hi, double* d_out,
+                            uint32_t* d_todo, uint32_t* d_ntodo, void* stream);
+int gdsp_genome_matrix (const gdsp_profile_source* sources, int nsources, int32_t offLo, uint32_t noffsets, uint32_t bin, int what,
+                        double lo, double hi, double* const* h_rows);
+int gdsp_matrix_set_launch_rows (uint32_t rows);
+/* what the last gdsp_genome_matrix did: [0] rows, [1] cells, [2] cells the host finished, [3] launches */
+void gdsp_genome_matrix_last (uint64_t out[4]);
+
 /* ---- statsover (not in the reference): one signal quantified over many intervals, exact ---------------------------
  * For a vector v of n doubles, an interval [s, e) with 0 <= s < e <= n, and limits lo, hi:
  *   the sample of the interval is stats' sample restricted to it: the bases i in [s, e) with !(v[i] < lo) &&
