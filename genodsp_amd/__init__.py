@@ -327,6 +327,40 @@ def local_stats(v, W, as_="zscore", floor=None, minsd=None, out=None, stream=Non
     return out
 
 
+# ------------------------------------------- localmad / hampel (not in the reference) ----
+
+LOCALMAD_MAX_WINDOW = 4095                    # GDSP_LOCALMAD_MAX_WINDOW
+LOCALMAD_WHAT = {"zscore": 0, "median": 1, "mad": 2, "difference": 3, "clean": 4, "outlier": 5}        # GDSP_LOCALMAD_*
+
+
+def _localmad_params(W, as_, scale, threshold, minmad):
+    if as_ not in LOCALMAD_WHAT:
+        raise ValueError("as_ must be one of %s, not %r" % (", ".join(LOCALMAD_WHAT), as_))
+    return (int(W), LOCALMAD_WHAT[as_], float(scale), float(threshold), int(minmad is not None), float(minmad or 0.0))
+
+
+def localmad_tile(W):
+    """outputs per workgroup tile of the kernel for window W; 0 outside 1 .. LOCALMAD_MAX_WINDOW (host code)"""
+    return lib().gdsp_localmad_tile(int(W))
+
+
+def local_mad(v, W, as_="zscore", scale=1.4826, threshold=3.0, minmad=None, out=None, stream=None):
+    """out[i] = v[i] against the median and the median absolute deviation (MAD) of slidingpercentile's window around i,
+    cut off at the ends of the vector (gdsp_localmad in include/genodsp_hip.h): the robust z-score
+    (v - median) / (scale * MAD), or with as_ the median, mad, difference, clean (the median where |difference| >
+    threshold * scale * MAD, else v: the Hampel filter) or outlier (1 there, else 0).  minmad: max(MAD, minmad) stands
+    for the MAD."""
+    params = _localmad_params(W, as_, scale, threshold, minmad)
+    out = out if out is not None else v.like()
+    call("gdsp_localmad", v.ptr, out.ptr, v.n, *params, _sp(stream))
+    return out
+
+
+def hampel(v, W, as_="clean", scale=1.4826, threshold=3.0, minmad=None, out=None, stream=None):
+    """the Hampel filter: local_mad with as_="clean" """
+    return local_mad(v, W, as_=as_, scale=scale, threshold=threshold, minmad=minmad, out=out, stream=stream)
+
+
 # ----------------------------------------------- localcorrelate (not in the reference) ----
 
 LOCALCORR_MAX_WINDOW = 4097                   # GDSP_LOCALCORR_MAX_WINDOW
@@ -1679,6 +1713,10 @@ def prominence_batch(vecs, W, as_="prominence", outs=None, stream=None):
 
 def local_stats_batch(vecs, W, as_="zscore", floor=None, minsd=None, outs=None, stream=None):
     return _batch("gdsp_localstats_batch", vecs, outs, *_localstats_params(W, as_, floor, minsd), stream=stream)
+
+
+def local_mad_batch(vecs, W, as_="zscore", scale=1.4826, threshold=3.0, minmad=None, outs=None, stream=None):
+    return _batch("gdsp_localmad_batch", vecs, outs, *_localmad_params(W, as_, scale, threshold, minmad), stream=stream)
 
 
 def local_correlation_batch(xs, ys, W, as_="correlation", stream=None):

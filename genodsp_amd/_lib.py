@@ -148,6 +148,10 @@ SIGNATURES = {
     "gdsp_localstats_tile": (_u32, [_u32]),
     "gdsp_localstats": (_int, [_vp, _vp, _u32, _u32, _int, _int, _f64, _int, _f64, _vp]),
     "gdsp_localstats_batch": (_int, [_vp, _int, _u32, _int, _int, _f64, _int, _f64, _vp]),
+    # localmad / hampel (not in the reference)
+    "gdsp_localmad_tile": (_u32, [_u32]),
+    "gdsp_localmad": (_int, [_vp, _vp, _u32, _u32, _int, _f64, _f64, _int, _f64, _vp]),
+    "gdsp_localmad_batch": (_int, [_vp, _int, _u32, _int, _f64, _f64, _int, _f64, _vp]),
     # localcorrelate (not in the reference)
     "gdsp_localcorr_tile": (_u32, [_u32]),
     "gdsp_localcorr": (_int, [_vp, _vp, _u32, _u32, _int, _vp]),

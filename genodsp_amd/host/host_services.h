@@ -49,6 +49,8 @@ u32   window_arg       (char* name, char* arg, char* argVal, const char* what);
 /* "--x=<value|variable>": number now, or a named variable resolved at first apply */
 void  value_or_variable (char* argVal, valtype* val, char** varName);
 void  resolve_variable  (dspop* op, char** varName, valtype* val, const char* role);
+/* the same for a level: a number that is not NaN, or what can be a variable's name; anything else is refused at once */
+void  level_arg         (char* name, char* arg, char* argVal, valtype* val, char** varName);
 /* what percentile, stats, normalize, histogram and statsover let the user say about the sample and its report; init
  * gives today's defaults (the named global windowSize, 0 meaning 1; no limits; every digit; not quiet), take consumes
  * --min= / --max= and those of the other options that `accepts` names, with the complaints they have always made */

@@ -2,6 +2,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
+#include <ctype.h>
 #include <float.h>
 #include <math.h>
 #include "genodsp_interface.h"
@@ -67,6 +68,22 @@ u32 window_arg (char* name, char* arg, char* argVal, const char* what)
 void value_or_variable (char* argVal, valtype* val, char** varName)
 	{
 	if (!try_string_to_valtype (argVal, val)) *varName = copy_string (argVal);
+	}
+
+/* <value|variable> for a level (localstats, localmad): a number, or something that can be the name of a variable (a
+ * letter or underscore, then letters, digits, underscores and dots) */
+void level_arg (char* name, char* arg, char* argVal, valtype* val, char** varName)
+	{
+	if (*varName != NULL) { free (*varName);  *varName = NULL; }
+	value_or_variable (argVal, val, varName);
+	if (*varName == NULL)
+		{
+		if (*val != *val) chastise ("[%s] \"%s\" is not a number\n", name, arg);
+		return;
+		}
+	int ok = (isalpha ((unsigned char) argVal[0]) || (argVal[0] == '_'));
+	for (char* c=argVal ; ok && (*c != 0) ; c++) ok = (isalnum ((unsigned char) *c) || (*c == '_') || (*c == '.'));
+	if (!ok) chastise ("[%s] \"%s\" is neither a number nor the name of a variable\n", name, arg);
 	}
 
 /* logical.c:234-243: fetch the variable at first apply, say so, then forget the name */

@@ -8,7 +8,6 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
-#include <ctype.h>
 #include "genodsp_interface.h"
 #include "genodsp_hip.h"
 #include "utilities.h"
@@ -54,22 +53,6 @@ void op_localstats_usage (char* name, FILE* f, char* indent)
 	fprintf (f, "%s  --floor=<value|variable> use max(mean, this) as the mean of --as=mean, difference and\n", indent);
 	fprintf (f, "%s                           ratio (as in: = stats = %s --as=ratio --floor=mean)\n", indent, name);
 	fprintf (f, "%s  --minsd=<value|variable> use max(stddev, this) as the stddev of --as=stddev and zscore\n", indent);
-	}
-
-/* <value|variable>: a number, or something that can be the name of a variable (a letter or underscore, then letters,
- * digits, underscores and dots) */
-static void level_arg (char* name, char* arg, char* argVal, valtype* val, char** varName)
-	{
-	if (*varName != NULL) { free (*varName);  *varName = NULL; }
-	value_or_variable (argVal, val, varName);
-	if (*varName == NULL)
-		{
-		if (*val != *val) chastise ("[%s] \"%s\" is not a number\n", name, arg);
-		return;
-		}
-	int ok = (isalpha ((unsigned char) argVal[0]) || (argVal[0] == '_'));
-	for (char* c=argVal ; ok && (*c != 0) ; c++) ok = (isalnum ((unsigned char) *c) || (*c == '_') || (*c == '.'));
-	if (!ok) chastise ("[%s] \"%s\" is neither a number nor the name of a variable\n", name, arg);
 	}
 
 dspop* op_localstats_parse (char* name, int argc, char** argv)

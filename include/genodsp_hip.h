@@ -296,6 +296,50 @@ int gdsp_localstats       (const double* d_in, double* d_out, uint32_t n, uint32
 int gdsp_localstats_batch (const gdsp_batch_item* items, int nitems, uint32_t W, int what,
                            int haveFloor, double floor, int haveMinSd, double minSd, void* stream);
 
+/* ---- localmad / hampel (not in the reference): each base against the median and the MAD of the window around it ---
+ * Take a vector v of n values and a window W with 1 <= W <= GDSP_LOCALMAD_MAX_WINDOW.  Window, centring and rank are
+ * slidingpercentile's: wL = (W-1)/2, wR = W-1-wL; the window of base i is [max(0, i-wL), min(n-1, i+wR)] with m bases
+ * in it, and k = gdsp_percentile_rank(m, 50000) = m/2 counted from 0: the upper median for even m.
+ *   med   = what gdsp_sliding_percentile at P = 50000 writes for base i: the k-th smallest key of the window, -0.0
+ *           folded onto +0.0
+ *   d_j   = |fl(v_j - med)| for every base j of the window: one rounded subtraction, then the sign cleared
+ *   mad   = the k-th smallest d_j, counted from 0, with the same k (the median absolute deviation)
+ *   madf  = minMad if haveMinMad and minMad > mad, else mad
+ *   sigma = fl(scale madf)                      (scale 1.4826 makes sigma estimate a normal distribution's stddev)
+ *   diff  = +0.0 where v_i == med, else fl(v_i - med)
+ *   limit = fl(threshold sigma)
+ *   base i is an outlier where |diff| > limit; with sigma == 0 every base that differs from its median is one, which
+ *   is Hampel's own behaviour (minMad is there to temper it).
+ * Every step is one rounded IEEE operation on doubles, in this order and never fused.
+ * what:  GDSP_LOCALMAD_ZSCORE     writes fl(diff / sigma), +0.0 where sigma == 0 (localstats' rule)
+ *        GDSP_LOCALMAD_MEDIAN     writes med
+ *        GDSP_LOCALMAD_MAD        writes madf
+ *        GDSP_LOCALMAD_DIFFERENCE writes diff
+ *        GDSP_LOCALMAD_CLEAN      writes med where the base is an outlier, else v_i bit for bit (the Hampel filter)
+ *        GDSP_LOCALMAD_OUTLIER    writes 1.0 where the base is an outlier, else 0.0
+ * The definition holds where every value of the window is finite (a deviation may overflow to +inf: that is still
+ * ordered).  Where a window holds a NaN or an infinity the figure at that base is unspecified (some double); the call
+ * still ends, and every base whose window holds none gets the definition's figure.  At W = 1 mad is 0, CLEAN is the
+ * input and OUTLIER is 0.
+ * Out-of-place; GDSP_EINVAL for d_in == d_out, W == 0, W above the maximum, an unknown `what`, a scale that is not
+ * finite and positive, or a threshold or minMad that is NaN or negative; n == 0 is a no-op.  One kernel launch covers
+ * every vector of a batch (gdsp_localmad.hip: slidingpercentile's tile -- one sort and one wavelet matrix in LDS --
+ * then per base the median's range-quantile query and a binary search for the block of the k+1 smallest deviations,
+ * two such queries per probe: at most 2 + 2 ceil(log2(k+1)) queries, whatever the values). */
+#define GDSP_LOCALMAD_MAX_WINDOW 4095          /* GDSP_SLIDING_PERCENTILE_MAX_WINDOW: the same tile */
+#define GDSP_LOCALMAD_ZSCORE     0
+#define GDSP_LOCALMAD_MEDIAN     1
+#define GDSP_LOCALMAD_MAD        2
+#define GDSP_LOCALMAD_DIFFERENCE 3
+#define GDSP_LOCALMAD_CLEAN      4
+#define GDSP_LOCALMAD_OUTLIER    5
+/* Host: outputs per workgroup tile of the kernel for window W (0 outside 1..the maximum); results never depend on it */
+uint32_t gdsp_localmad_tile  (uint32_t W);
+int gdsp_localmad       (const double* d_in, double* d_out, uint32_t n, uint32_t W, int what,
+                         double scale, double threshold, int haveMinMad, double minMad, void* stream);
+int gdsp_localmad_batch (const gdsp_batch_item* items, int nitems, uint32_t W, int what,
+                         double scale, double threshold, int haveMinMad, double minMad, void* stream);
+
 /* ---- localcorrelate (not in the reference): the signal against a second track over the window centred on each base -
  * Take x (the signal) and y (the track) of n values each and a window W with 1 <= W <= GDSP_LOCALCORR_MAX_WINDOW.
  * The window is localstats' and slidingsum's: with rgt = (W-1)/2 and lft = W-1-rgt, base c has lo = max(0, c-lft),
