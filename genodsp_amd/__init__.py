@@ -410,6 +410,31 @@ def distance(v, T=0.0, ties_above=False, to="nearest", signed=False, cap=None, s
     return v
 
 
+# --------------------------------------------------- fillgaps (not in the reference) ----
+
+FILL_KNOWN = {"above": 0, "nonzero": 1}                           # GDSP_FILL_KNOWN_*
+FILL_HOW = {"linear": 0, "nearest": 1, "left": 2, "right": 3}     # GDSP_FILL_LINEAR ..
+FILL_ENDS = {"extend": 0, "keep": 1}                              # GDSP_FILL_ENDS_*
+
+
+def _fill_params(T, ties_above, known, how, ends, maxgap):
+    for what, value, names in (("known", known, FILL_KNOWN), ("how", how, FILL_HOW), ("ends", ends, FILL_ENDS)):
+        if value not in names:
+            raise ValueError("%s must be one of %s, not %r" % (what, ", ".join(names), value))
+    if maxgap is not None and int(maxgap) < 1:
+        raise ValueError("maxgap must be at least 1 (None: no limit), not %r" % (maxgap,))
+    return float(T), int(bool(ties_above)), FILL_KNOWN[known], FILL_HOW[how], FILL_ENDS[ends], int(maxgap or 0)
+
+
+def fill_gaps(v, T=0.0, ties_above=False, known="above", how="linear", ends="extend", maxgap=None, stream=None):
+    """the unknown bases of v (not above T, or >= with ties_above; with known="nonzero": zero or NaN) take their values from
+    the known bases before and behind their gap: on the line between the two, or the nearest's, the left's, the right's;
+    ends: what a base does whose side does not exist; maxgap: longer gaps are left alone (gdsp_fillgaps in
+    include/genodsp_hip.h).  In place."""
+    call("gdsp_fillgaps", v.ptr, v.n, *_fill_params(T, ties_above, known, how, ends, maxgap), _sp(stream))
+    return v
+
+
 # ---------------------------------------------------------- morphology.c ----
 
 def split_length(length):
@@ -1729,6 +1754,11 @@ def local_correlation_batch(xs, ys, W, as_="correlation", stream=None):
 
 def distance_batch(vecs, T=0.0, ties_above=False, to="nearest", signed=False, cap=None, stream=None):
     return _batch("gdsp_distance_batch", vecs, None, *_distance_params(T, ties_above, to, signed, cap), stream=stream,
+                  in_place=True)
+
+
+def fill_gaps_batch(vecs, T=0.0, ties_above=False, known="above", how="linear", ends="extend", maxgap=None, stream=None):
+    return _batch("gdsp_fillgaps_batch", vecs, None, *_fill_params(T, ties_above, known, how, ends, maxgap), stream=stream,
                   in_place=True)
 
 

@@ -162,6 +162,11 @@ SIGNATURES = {
     "gdsp_distance": (_int, [_vp, _u32, _f64, _int, _int, _int, _u32, _vp]),
     "gdsp_distance_batch": (_int, [_vp, _int, _f64, _int, _int, _int, _u32, _vp]),
     "gdsp_distance_times": (None, [_vp]),
+    # fillgaps (not in the reference)
+    "gdsp_fillgaps_tile": (_u32, []),
+    "gdsp_fillgaps": (_int, [_vp, _u32, _f64, _int, _int, _int, _int, _u32, _vp]),
+    "gdsp_fillgaps_batch": (_int, [_vp, _int, _f64, _int, _int, _int, _int, _u32, _vp]),
+    "gdsp_fillgaps_times": (None, [_vp]),
     # stats / normalize / multiplyconst / divideconst (not in the reference)
     "gdsp_xsum_init": (_int, [_vp, _vp]),
     "gdsp_xsum_accumulate_batch": (_int, [_vp, _int, _u32, _f64, _f64, _vp, _vp]),

@@ -3,8 +3,9 @@
 // The definition is at gdsp_distance (include/genodsp_hip.h).  With S = {i : v[i] above T}, dilate asks "is a member of
 // S within r of here" and erode "does S cover everything within r of here" (gdsp_morph.hip); this is the figure under
 // both, for every r at once.  A distance has no bounded reach, so nothing can be answered from one tile and its halo.
-// Three launches in stream order over every vector of a table (gdsp_common.h: GdspBatch), in place:
-//   1. bits    8 B/base read.  A workgroup turns its tile of the signal into membership bits -- lanes load 16 bytes each,
+// Three launches in stream order over every vector of a table (gdsp_common.h: GdspBatch), in place; the first two are
+// gdsp_member_tile.h's, which fillgaps (gdsp_fillgaps.hip) runs with its own predicate and its own third launch:
+//   1. bits   8 B/base read.  A workgroup turns its tile of the signal into membership bits -- lanes load 16 bytes each,
 //              wave ballots gather the predicate, 128 bases become two 64-bit words, as gdsp_morph.hip stages them
 //              (here a lane shuffle puts the predicates in base order before the ballot; interleaving the even and odd
 //              ballots with scalar shifts, and the extents beside them, held this launch at 4.9 TB/s where it now reads
@@ -24,171 +25,20 @@
 // as position + 1 with 0 for none, so that max joins them as min joins the "first" ones.
 
 #include <stdlib.h>
-#include <algorithm>
 #include "gdsp_common.h"
 #include "gdsp_pieces.h"
+#include "gdsp_member_tile.h"
 
-#define DT_THREADS      256
-#define DT_TILE         8192                     // bases per workgroup: 64 KiB read by launch 1, 64 KiB written by launch 3
-#define DT_WORDS        (DT_TILE / 64)           // 128 mask words per tile
-#define DT_CHUNKS       (DT_TILE / 128)          // wave-steps per tile
-#define DT_UNROLL       8                        // 16-byte loads in flight per lane
-#define DT_JOIN_THREADS 1024
-#define DT_NONE         0xFFFFFFFFu
 #define DT_FAR          0x7FFFFFFF               // "no set bit in the words behind" inside a tile
 
-__device__ __forceinline__ bool dt_member (double x, double T, int ties) { return ties? (x >= T) : (x > T); }   // segments' test: a NaN is never a member
-
-// a tile's extent: x = first member, y = last member + 1, z = first non-member, w = last non-member + 1
-struct DtExtent { uint32_t firstM, lastM1, firstN, lastN1; };
-
-// the word of the bases [start, start+64): its members, and those of its clear bits that are bases of the vector
-__device__ __forceinline__ void dt_extend (DtExtent& e, uint64_t word, uint64_t start, uint32_t n)
-	{
-	if (word != 0)
-		{
-		e.firstM = min (e.firstM, (uint32_t) (start + __builtin_ctzll (word)));
-		e.lastM1 = max (e.lastM1, (uint32_t) (start + 64 - __builtin_clzll (word)));
-		}
-	if (start >= n) return;
-	const uint64_t inside = (start + 64 <= n)? ~0ULL : ((1ULL << (n - start)) - 1);
-	const uint64_t clear  = ~word & inside;
-	if (clear != 0)
-		{
-		e.firstN = min (e.firstN, (uint32_t) (start + __builtin_ctzll (clear)));
-		e.lastN1 = max (e.lastN1, (uint32_t) (start + 64 - __builtin_clzll (clear)));
-		}
-	}
-
-// ---- launch 1: tile `gt` of the table -> its DT_WORDS mask words (bits past the vector's end are clear) and its extent.
-// Tiles that lie wholly inside the vector load unconditionally (a predicated load gets its own branch and wait).
+// ---- launches 1 and 2: gdsp_member_tile.h, with segments' test as the predicate
 __global__ __launch_bounds__(DT_THREADS)
 void dt_bits_kernel (GdspBatch B, double T, int tiesAbove, unsigned long long* __restrict__ words, uint4* __restrict__ extent)
-	{
-	__shared__ DtExtent part[DT_THREADS/64];
-	__shared__ uint64_t tileWords[DT_WORDS];
-	const double* unused;  double* v;  uint32_t n;
-	const uint32_t t         = gdsp_batch_tile (B, unused, v, n);
-	const uint32_t gt        = gdsp_xcd_tile (blockIdx.x, B.tile0[GDSP_BATCH_MAX]);       // the tile's index in the table
-	const uint64_t tileStart = (uint64_t) t * DT_TILE;
-	const int      lane      = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const bool     interior  = (tileStart + DT_TILE <= (uint64_t) n);
+	{ dt_bits_tile (B, DtAbove { T, tiesAbove }, words, extent); }
 
-	for (int c0 = wave*DT_UNROLL ; c0 < DT_CHUNKS ; c0 += (DT_THREADS/64)*DT_UNROLL)
-		{
-		double2 d[DT_UNROLL];
-		bool    hx[DT_UNROLL], hy[DT_UNROLL];
-		if (interior)
-			{
-#pragma unroll
-			for (int u=0 ; u<DT_UNROLL ; u++)
-				{
-				d[u]  = gdsp_ld2 (reinterpret_cast<const double2*> (v + tileStart + 128*(c0+u) + 2*lane));
-				hx[u] = hy[u] = true;
-				}
-			}
-		else
-			{
-#pragma unroll
-			for (int u=0 ; u<DT_UNROLL ; u++)
-				{
-				const uint64_t g = tileStart + 128*(c0+u) + 2*lane;
-				hx[u] = (g < (uint64_t) n);
-				hy[u] = (g + 1 < (uint64_t) n);
-				d[u].x = hx[u]? v[g]   : 0.0;
-				d[u].y = hy[u]? v[g+1] : 0.0;
-				}
-			}
-#pragma unroll
-		for (int u=0 ; u<DT_UNROLL ; u++)
-			{
-			// base k of the chunk's first 64 sits in lane k/2, of its last 64 in lane 32 + k/2: one shuffle each brings
-			// its predicate to lane k, and the ballots are the two mask words (no bit interleave on the scalar unit)
-			const int c      = c0 + u;
-			const int packed = (int) (hx[u] && dt_member (d[u].x, T, tiesAbove)) | ((int) (hy[u] && dt_member (d[u].y, T, tiesAbove)) << 1);
-			const int lower  = __shfl (packed, lane >> 1, 64), upper = __shfl (packed, 32 + (lane >> 1), 64);
-			const uint64_t wA = __ballot (((lower >> (lane & 1)) & 1) != 0);
-			const uint64_t wB = __ballot (((upper >> (lane & 1)) & 1) != 0);
-			if (lane == 0) { tileWords[2*c] = wA;  tileWords[2*c+1] = wB; }
-			}
-		}
-	__syncthreads ();
-
-	// one thread per word: the word goes to the workspace, its set and clear bits into the tile's extent
-	DtExtent e = { DT_NONE, 0, DT_NONE, 0 };
-	if (threadIdx.x < DT_WORDS)
-		{
-		const uint64_t word = tileWords[threadIdx.x];
-		words[(size_t) gt * DT_WORDS + threadIdx.x] = word;
-		dt_extend (e, word, tileStart + 64*(uint64_t) threadIdx.x, n);
-		}
-	for (int off=32 ; off>0 ; off>>=1)
-		{
-		e.firstM = min (e.firstM, (uint32_t) __shfl_xor ((int) e.firstM, off, 64));
-		e.lastM1 = max (e.lastM1, (uint32_t) __shfl_xor ((int) e.lastM1, off, 64));
-		e.firstN = min (e.firstN, (uint32_t) __shfl_xor ((int) e.firstN, off, 64));
-		e.lastN1 = max (e.lastN1, (uint32_t) __shfl_xor ((int) e.lastN1, off, 64));
-		}
-	if (lane == 0) part[wave] = e;
-	__syncthreads ();
-	if (threadIdx.x == 0)
-		{
-		for (int w=1 ; w<DT_THREADS/64 ; w++)
-			{
-			e.firstM = min (e.firstM, part[w].firstM);  e.lastM1 = max (e.lastM1, part[w].lastM1);
-			e.firstN = min (e.firstN, part[w].firstN);  e.lastN1 = max (e.lastN1, part[w].lastN1);
-			}
-		extent[gt] = make_uint4 (e.firstM, e.lastM1, e.firstN, e.lastN1);
-		}
-	}
-
-// ---- launch 2: workgroup s joins the extents of vector s (the scan never crosses into another vector's tiles).
-// carry[tile]: x = first member behind the tile, y = last member before it + 1, z and w the same for non-members;
-// DT_NONE / 0 where the vector has none there.  Every thread owns a stretch of consecutive tiles.
 __global__ __launch_bounds__(DT_JOIN_THREADS)
 void dt_join_kernel (GdspBatch B, const uint4* __restrict__ extent, uint4* __restrict__ carry)
-	{
-	__shared__ uint32_t a[4][DT_JOIN_THREADS];
-	const uint32_t t0  = B.tile0[blockIdx.x], nt = B.tile0[blockIdx.x + 1] - t0;
-	const uint32_t per = (nt + DT_JOIN_THREADS - 1) / DT_JOIN_THREADS;
-	const uint32_t lo  = min (threadIdx.x * per, nt), hi = min (lo + per, nt);
-	const int      me  = (int) threadIdx.x;
-	uint32_t firstM = DT_NONE, lastM1 = 0, firstN = DT_NONE, lastN1 = 0;
-	for (uint32_t b=lo ; b<hi ; b++)
-		{
-		const uint4 e = extent[t0 + b];
-		firstM = min (firstM, e.x);  lastM1 = max (lastM1, e.y);  firstN = min (firstN, e.z);  lastN1 = max (lastN1, e.w);
-		}
-	a[0][me] = firstM;  a[1][me] = lastM1;  a[2][me] = firstN;  a[3][me] = lastN1;
-	__syncthreads ();
-	for (int d=1 ; d<DT_JOIN_THREADS ; d*=2)                   // min from the right for the firsts, max from the left for the lasts
-		{
-		const uint32_t fm = (me + d < DT_JOIN_THREADS)? a[0][me + d] : DT_NONE;
-		const uint32_t lm = (me - d >= 0)?              a[1][me - d] : 0;
-		const uint32_t fn = (me + d < DT_JOIN_THREADS)? a[2][me + d] : DT_NONE;
-		const uint32_t ln = (me - d >= 0)?              a[3][me - d] : 0;
-		__syncthreads ();
-		a[0][me] = min (a[0][me], fm);  a[1][me] = max (a[1][me], lm);
-		a[2][me] = min (a[2][me], fn);  a[3][me] = max (a[3][me], ln);
-		__syncthreads ();
-		}
-	lastM1 = (me > 0)? a[1][me - 1] : 0;
-	lastN1 = (me > 0)? a[3][me - 1] : 0;
-	for (uint32_t b=lo ; b<hi ; b++)
-		{
-		const uint4 e = extent[t0 + b];
-		carry[t0 + b].y = lastM1;  carry[t0 + b].w = lastN1;
-		lastM1 = max (lastM1, e.y);  lastN1 = max (lastN1, e.w);
-		}
-	firstM = (me + 1 < DT_JOIN_THREADS)? a[0][me + 1] : DT_NONE;
-	firstN = (me + 1 < DT_JOIN_THREADS)? a[2][me + 1] : DT_NONE;
-	for (uint32_t b=hi ; b>lo ; b--)
-		{
-		const uint4 e = extent[t0 + b - 1];
-		carry[t0 + b - 1].x = firstM;  carry[t0 + b - 1].z = firstN;
-		firstM = min (firstM, e.x);  firstN = min (firstN, e.z);
-		}
-	}
+	{ dt_join_vector (B, extent, carry); }
 
 // ---- launch 3.  Tables per mask word w of the tile, for the set (entries 0 .. DT_WORDS-1) and for its complement
 // (DT_WORDS ..): before[w] = bases from the word's first bit back to the set bit before the word, behind[w] = bases
@@ -296,17 +146,8 @@ void dt_write_kernel (GdspBatch B, const unsigned long long* __restrict__ words,
 	}
 
 // ---------------------------------------------------------------------------------------------- host ----
-// per device: the mask words, extents and carries of one table of vectors; grown on demand and kept.  gdsp_malloc's
-// (poisoned under GDSP_POISON): launch 1 writes every word and extent of every tile, launch 2 every carry, before
-// anything is read.  Calls on one device share it: each call's stream first waits for the event the call before it
-// recorded behind its last launch (a dependency between streams that the runtime keeps; the host does not wait), so calls
-// on several streams of a device -- the driver's shards of one GPU -- take the workspace in turn.
-struct DtWork { void* d;  size_t cap;  hipEvent_t done; };
-static DtWork dtWork[64];
+// the workspace of launches 1 and 2, and how calls take it in turn: gdsp_member_tile.h
 static double dtTimes[3];
-#define DT_TILE_BYTES ((size_t) DT_WORDS * 8 + 2 * sizeof(uint4))
-
-static uint64_t dt_tiles (uint32_t n) { return ((uint64_t) n + DT_TILE - 1) / DT_TILE; }
 
 // GDSP_DISTANCE_TIMES=1: the three launches are timed with events (profiles/distance.txt); the call then waits for them
 static bool dt_timed (void)
@@ -335,38 +176,12 @@ static int dt_run (const gdsp_batch_item* items, int nitems, double T, int tiesA
 	if (rc != GDSP_OK) return rc;
 	dtTimes[0] = dtTimes[1] = dtTimes[2] = 0;
 
-	// the largest table of the call decides the workspace (gdsp_batch_run: GDSP_BATCH_MAX vectors at a time)
-	uint64_t most = 0;
-		{
-		uint64_t sum = 0;
-		int      k = 0;
-		for (int i=0 ; i<nitems ; i++)
-			{
-			if (items[i].n == 0) continue;
-			if (k == GDSP_BATCH_MAX) { k = 0;  sum = 0; }
-			sum += dt_tiles (items[i].n);  k++;
-			most = std::max (most, sum);
-			}
-		}
+	const uint64_t most = dt_most_tiles (items, nitems);
 	if (most == 0) return GDSP_OK;
-	int dev = 0;
-	rc = gdsp_device_slot (&dev);
-	if (rc != GDSP_OK) return rc;
-	DtWork& W = dtWork[dev];
-	if (most * DT_TILE_BYTES > W.cap)
-		{
-		if (W.d != NULL) { (void) gdsp_free (W.d);  W.d = NULL;  W.cap = 0; }
-		rc = gdsp_malloc (&W.d, most * DT_TILE_BYTES);
-		if (rc != GDSP_OK) { W.d = NULL;  return rc; }
-		W.cap = most * DT_TILE_BYTES;
-		}
-	unsigned long long* words  = (unsigned long long*) W.d;
-	uint4*              extent = (uint4*) (words + most * DT_WORDS);
-	uint4*              carry  = extent + most;
-
 	hipStream_t s = gdsp_stream (stream);
-	if (W.done == NULL) GDSP_HIP_TRY (hipEventCreateWithFlags (&W.done, hipEventDisableTiming));
-	else                GDSP_HIP_TRY (hipStreamWaitEvent (s, W.done, 0));
+	DtWork* W;  unsigned long long* words;  uint4 *extent, *carry;
+	rc = dt_work_take (most, s, &W, &words, &extent, &carry);
+	if (rc != GDSP_OK) return rc;
 	const bool  timed = dt_timed ();
 	hipEvent_t  ev[4] = { NULL, NULL, NULL, NULL };
 	if (timed) { for (int k=0 ; k<4 ; k++) GDSP_HIP_TRY (hipEventCreate (&ev[k])); }
@@ -389,8 +204,7 @@ static int dt_run (const gdsp_batch_item* items, int nitems, double T, int tiesA
 	if (timed) { for (int k=0 ; k<4 ; k++) (void) hipEventDestroy (ev[k]); }
 	GDSP_LAUNCH_CHECK ();
 	GDSP_HIP_TRY (late);
-	GDSP_HIP_TRY (hipEventRecord (W.done, s));
-	return GDSP_OK;
+	return dt_work_done (W, s);
 	}
 
 extern "C" {

@@ -119,10 +119,11 @@ extern const opgroup opgroup_profileover __attribute__((weak));     /* the avera
 extern const opgroup opgroup_localcorrelate __attribute__((weak));  /* the signal against a second track, window by window */
 extern const opgroup opgroup_matrixover __attribute__((weak));      /* the signal around each anchor of a file, row by row */
 extern const opgroup opgroup_localmad   __attribute__((weak));      /* each base against the median and MAD of the window around it */
+extern const opgroup opgroup_fillgaps   __attribute__((weak));      /* the signal interpolated across its uncovered bases */
 static const opgroup* const opGroups[] =
 	{ &opgroup_rankfilt, &opgroup_stats, &opgroup_statsover, &opgroup_histogram, &opgroup_correlate, &opgroup_lagcorr,
 	  &opgroup_segments, &opgroup_prominence, &opgroup_localstats, &opgroup_distance, &opgroup_profileover,
-	  &opgroup_localcorrelate, &opgroup_matrixover, &opgroup_localmad };
+	  &opgroup_localcorrelate, &opgroup_matrixover, &opgroup_localmad, &opgroup_fillgaps };
 #define numOpGroups ((int) (sizeof(opGroups)/sizeof(opGroups[0])))
 
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS

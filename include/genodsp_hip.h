@@ -423,6 +423,53 @@ int gdsp_distance_batch (const gdsp_batch_item* items, int nitems, double T, int
                          uint32_t cap, void* stream);
 void gdsp_distance_times (double ms[3]);
 
+/* ---- fillgaps (not in the reference): the signal interpolated across its uncovered bases ------------------------------
+ * Take a vector v of n values, a test `known` with its threshold T and tiesAbove, a way to fill `how`, a treatment of the
+ * ends `ends` and a longest gap G (maxgap; 0: no limit).
+ * Known bases.  GDSP_FILL_KNOWN_ABOVE: base i is known iff v[i] > T, or v[i] >= T with tiesAbove (the test of
+ * gdsp_segments_batch).  GDSP_FILL_KNOWN_NONZERO: iff v[i] != 0 and v[i] == v[i]; negative values count, both zeros do
+ * not, and T and tiesAbove are not used.  A NaN is never known under either test.  A known base keeps its value bit for
+ * bit, infinities included.
+ * Gaps.  A gap is a maximal run of unknown bases.  An interior gap has a known base l just before it and a known base r
+ * just behind it; for its base i let a = v[l], b = v[r], d = r - l, k = i - l.  An end gap touches the vector's start or
+ * its end and has one known neighbour.  A vector without a known base is left untouched, bit for bit.
+ *   how:  GDSP_FILL_LINEAR   interior: a where a == b (bit for bit); otherwise x = fl(a + fl(fl(fl(b - a) * k) / d)),
+ *                            every step rounded once and none fused, k and d exact doubles, and then clamped:
+ *                            x < lo ? lo : (x > hi ? hi : x) with lo = min(a, b), hi = max(a, b).  A NaN (from
+ *                            inf - inf) passes through the clamp as NaN.
+ *         GDSP_FILL_NEAREST  interior: a where k <= d - k, else b; a tie goes to the lower coordinate
+ *         GDSP_FILL_LEFT     a: forward fill
+ *         GDSP_FILL_RIGHT    b
+ *   ends: GDSP_FILL_ENDS_EXTEND  a base whose mode needs a side that does not exist takes the value of the side that
+ *                            does: the end gaps under every mode; under LEFT the bases before the first known base,
+ *                            under RIGHT those behind the last
+ *         GDSP_FILL_ENDS_KEEP    such a base keeps its own value, bit for bit
+ *   G >= 1: a gap of more than G bases is left as it is, bit for bit, interior gaps and end gaps alike.  With G, out[i]
+ *   depends on v[i-G-1 .. i+G+1] only (ops_fillgaps.c has the argument).
+ * Only the four operations above touch values, so the result is the definition's bit for bit on any input.
+ * In place.  gdsp_fillgaps_batch uses d_out only, as the other in-place batch calls.  GDSP_EINVAL for an unknown `known`,
+ * `how` or `ends`, or a NaN T under GDSP_FILL_KNOWN_ABOVE; n == 0 is a no-op.  Three launches in stream order cover every
+ * vector of the batch, 32 vectors at a time (gdsp_fillgaps.hip: the known bases as bits, and tile extents; a join of the
+ * extents per vector; the write, which skips every tile that has nothing to fill), in the workspace that gdsp_distance
+ * uses (one per device, kept); calls on several streams of a device take it in turn.
+ * gdsp_fillgaps_times: with GDSP_FILLGAPS_TIMES=1 in the environment, the milliseconds of the last call's three
+ * launches, from events (the call then waits for them); zeros otherwise. */
+#define GDSP_FILL_KNOWN_ABOVE   0
+#define GDSP_FILL_KNOWN_NONZERO 1
+#define GDSP_FILL_LINEAR        0
+#define GDSP_FILL_NEAREST       1
+#define GDSP_FILL_LEFT          2
+#define GDSP_FILL_RIGHT         3
+#define GDSP_FILL_ENDS_EXTEND   0
+#define GDSP_FILL_ENDS_KEEP     1
+/* Host: bases per workgroup tile; results never depend on it */
+uint32_t gdsp_fillgaps_tile  (void);
+int gdsp_fillgaps       (double* d_v, uint32_t n, double T, int tiesAbove, int known, int how, int ends, uint32_t maxgap,
+                         void* stream);
+int gdsp_fillgaps_batch (const gdsp_batch_item* items, int nitems, double T, int tiesAbove, int known, int how, int ends,
+                         uint32_t maxgap, void* stream);
+void gdsp_fillgaps_times (double ms[3]);
+
 /* ---- logical.c, mask.c, add.c (in place) ---------------------------------------- */
 int gdsp_binarize     (double* d_v, uint32_t n, double T, int tiesAbove, double one, double zero,
                        void* stream);                                 /* logical.c:216-268 */
