@@ -966,20 +966,42 @@ def _profile_anchors(anchors, nvecs):
     return a
 
 
+def _anchor_items(vecs, stream):
+    """-> (src, items): vecs as xsum_sources, and the same whole chromosomes as the read-only BatchItem table"""
+    return xsum_sources(vecs, stream), _read_only_items(vecs)
+
+
+def _anchor_upload(a, stream):
+    """-> (buffer, count): the anchors on the device, their positions and then their code words (vector * 2 + minus)"""
+    anc = DeviceBuffer(max(1, 2 * len(a)) * 4)
+    if len(a):
+        anc.upload(np.concatenate([a[:, 1].astype(np.uint32), (a[:, 0] * 2 + (a[:, 2] < 0)).astype(np.uint32)]), stream=stream)
+    return anc, len(a)
+
+
+def _anchor_sources(src, a, stream, with_rows=None):
+    """-> (tab, keep): the ProfileSource table, each vector with its own anchors in their order, and per vector the arrays
+    the table points into: (where in a, positions, minus flags, rows to fill: with_rows columns each, or None)"""
+    tab = (ProfileSource * len(src))()
+    keep = []
+    for i in range(len(src)):
+        where = np.flatnonzero(a[:, 0] == i)
+        pos = np.ascontiguousarray(a[where, 1], dtype=np.uint32)
+        minus = np.ascontiguousarray(a[where, 2] < 0, dtype=np.uint32)
+        mine = None if with_rows is None else np.zeros((max(1, pos.size), max(1, with_rows)), np.float64)
+        keep.append((where, pos, minus, mine))
+        tab[i].d_v, tab[i].n, tab[i].device, tab[i].stream = src[i].d_v, src[i].n, src[i].device, stream
+        tab[i].h_pos, tab[i].h_minus, tab[i].nanchors = pos.ctypes.data, minus.ctypes.data, pos.size
+    return tab, keep
+
+
 def profile_images(vecs, anchors, off_lo, noffsets, lo=-DBL_MAX, hi=DBL_MAX, mean=None, stream=None):
     """The canonical images of one pass of gdsp_profile_accumulate_batch, np.uint64[noffsets, XSUM_WORDS]: image k sums the
     sampled values at offset off_lo + k from the anchors -- or, with mean (one per offset), their fl(fl(v - mean[k])^2).
     vecs: as xsum_sources, whole chromosomes; anchors: rows (vector index, position, strand +1 / -1)."""
     noffsets = int(noffsets)
-    src = xsum_sources(vecs, stream)
-    a = _profile_anchors(anchors, len(vecs))
-    items = (BatchItem * max(len(vecs), 1))()
-    for i in range(len(vecs)):
-        items[i].d_in, items[i].d_out, items[i].n = src[i].d_v, None, src[i].n
-    na = int(a.shape[0])
-    anc = DeviceBuffer(max(1, 2 * na) * 4)
-    if na:
-        anc.upload(np.concatenate([a[:, 1].astype(np.uint32), (a[:, 0] * 2 + (a[:, 2] < 0)).astype(np.uint32)]), stream=stream)
+    _, items = _anchor_items(vecs, stream)
+    anc, na = _anchor_upload(_profile_anchors(anchors, len(vecs)), stream)
     acc = DeviceBuffer(max(1, noffsets) * XSUM_WORDS * 8)
     acc.upload(np.zeros(max(1, noffsets) * XSUM_WORDS, np.uint64), stream=stream)
     d_mean = None
@@ -1001,17 +1023,7 @@ def genome_profile(vecs, anchors, off_lo, noffsets, bin=1, lo=-DBL_MAX, hi=DBL_M
     xsum_sources, whole chromosomes; anchors: rows (vector index, position, strand +1 / -1); allreduce: genome_stats'
     hook.  Returns a dict of np arrays, one entry per column ("offsets": each column's lowest offset)."""
     noffsets, bin = int(noffsets), int(bin)
-    src = xsum_sources(vecs, stream)
-    a = _profile_anchors(anchors, len(vecs))
-    tab = (ProfileSource * max(1, len(vecs)))()
-    keep = []
-    for i in range(len(vecs)):
-        mine = a[a[:, 0] == i]
-        pos = np.ascontiguousarray(mine[:, 1], dtype=np.uint32)
-        minus = np.ascontiguousarray(mine[:, 2] < 0, dtype=np.uint32)
-        keep.append((pos, minus))
-        tab[i].d_v, tab[i].n, tab[i].device, tab[i].stream = src[i].d_v, src[i].n, src[i].device, stream
-        tab[i].h_pos, tab[i].h_minus, tab[i].nanchors = pos.ctypes.data, minus.ctypes.data, pos.size
+    tab, keep = _anchor_sources(xsum_sources(vecs, stream), _profile_anchors(anchors, len(vecs)), stream)
     ncols = noffsets // bin if bin >= 1 and noffsets >= 1 else 0
     count = np.zeros(max(1, ncols), np.uint64)
     figs = [np.zeros(max(1, ncols), np.float64) for _ in range(4)]
@@ -1060,16 +1072,10 @@ def matrix_rows(vecs, anchors, off_lo, noffsets, bin=1, what="mean", lo=-DBL_MAX
     whose entries of rows mean nothing.  vecs: as xsum_sources, whole chromosomes; anchors: rows (vector index, position,
     strand +1 / -1)."""
     noffsets, bin = int(noffsets), int(bin)
-    src = xsum_sources(vecs, stream)
-    a = _profile_anchors(anchors, len(vecs))
-    items = (BatchItem * max(len(vecs), 1))()
-    for i in range(len(vecs)):
-        items[i].d_in, items[i].d_out, items[i].n = src[i].d_v, None, src[i].n
-    na, ncols = int(a.shape[0]), _matrix_columns(noffsets, bin)
+    _, items = _anchor_items(vecs, stream)
+    anc, na = _anchor_upload(_profile_anchors(anchors, len(vecs)), stream)
+    ncols = _matrix_columns(noffsets, bin)
     cells = na * ncols
-    anc = DeviceBuffer(max(1, 2 * na) * 4)
-    if na:
-        anc.upload(np.concatenate([a[:, 1].astype(np.uint32), (a[:, 0] * 2 + (a[:, 2] < 0)).astype(np.uint32)]), stream=stream)
     out = DeviceBuffer(max(1, cells) * 8)
     todo = DeviceBuffer((max(1, cells) + 1) * 4)                        # the counter, then the list
     todo.upload(np.zeros(1, np.uint32), stream=stream)
@@ -1090,21 +1096,10 @@ def genome_matrix(vecs, anchors, off_lo, noffsets, bin=1, what="mean", lo=-DBL_M
     min or max has nothing to look at.  vecs: as xsum_sources, whole chromosomes; anchors: rows (vector index, position,
     strand +1 / -1), and the rows come back in their order."""
     noffsets, bin = int(noffsets), int(bin)
-    src = xsum_sources(vecs, stream)
     a = _profile_anchors(anchors, len(vecs))
     ncols = _matrix_columns(noffsets, bin)
-    tab = (ProfileSource * max(1, len(vecs)))()
-    rows = (C.c_void_p * max(1, len(vecs)))()
-    keep = []
-    for i in range(len(vecs)):
-        where = np.flatnonzero(a[:, 0] == i)
-        pos = np.ascontiguousarray(a[where, 1], dtype=np.uint32)
-        minus = np.ascontiguousarray(a[where, 2] < 0, dtype=np.uint32)
-        mine = np.zeros((max(1, pos.size), max(1, ncols)), np.float64)
-        keep.append((where, pos, minus, mine))
-        tab[i].d_v, tab[i].n, tab[i].device, tab[i].stream = src[i].d_v, src[i].n, src[i].device, stream
-        tab[i].h_pos, tab[i].h_minus, tab[i].nanchors = pos.ctypes.data, minus.ctypes.data, pos.size
-        rows[i] = mine.ctypes.data
+    tab, keep = _anchor_sources(xsum_sources(vecs, stream), a, stream, with_rows=ncols)
+    rows = (C.c_void_p * len(keep))(*[mine.ctypes.data for _, _, _, mine in keep])
     call("gdsp_genome_matrix", tab, len(vecs), int(off_lo), noffsets, bin, _matrix_figure(what), float(lo), float(hi), rows)
     out = np.zeros((a.shape[0], ncols), np.float64)
     for where, pos, _, mine in keep:

@@ -24,6 +24,8 @@
 // cell -- flagged, overflowing, or a mean that cannot be proven -- is appended to the launch's to-do list, one atomic per
 // wave and stretch, and computed by the host half through gdsp_interval_stats_batch.  One double is written per cell, by one lane; no
 // atomics on cells, no wave or workgroup waits for another (the LDS piece is a wave's own), no scratch.
+// What concerns the anchors rather than the figures -- their code word, the table of vectors a launch takes, the checks, the
+// gather of a device's sources, the holder of its allocations -- is gdsp_anchors.h's, shared with profileover.
 
 #include <float.h>
 #include <math.h>
@@ -31,6 +33,7 @@
 #include <vector>
 #include <algorithm>
 #include "gdsp_common.h"
+#include "gdsp_anchors.h"
 #include "gdsp_xsum_dev.h"
 
 #define MX_THREADS      256
@@ -40,19 +43,10 @@
 #define MX_STAGE_DEPTH  8                             // loads a lane issues before its first LDS store
 #define MX_WG_TARGET    2048                          // workgroups of a launch (33 KiB of LDS each: four on a CU)
 #define MX_LAUNCH_CELLS (1u << 25)                    // cells of one launch of the host half (256 MiB of rows)
-#define MX_MAX_OFFSETS  GDSP_PROFILE_MAX_OFFSETS
 
 #define MX_NARROW_BELOW 256                           // bins from here on take the wide route
 
 enum { MX_ROUTE_COPY = 0, MX_ROUTE_NARROW = 1, MX_ROUTE_WIDE = 2 };
-
-struct MxBatch
-	{
-	const double* v[GDSP_BATCH_MAX];
-	uint32_t      n[GDSP_BATCH_MAX];
-	uint32_t      vec0;                                   // the table holds the vectors vec0 .. vec0 + nvec - 1 of the call
-	uint32_t      nvec;
-	};
 
 // what a lane (then a group, then a cell) knows of its sample
 struct MxAcc { double a[XS_K];  double m;  uint32_t cnt, flag; };
@@ -177,7 +171,7 @@ __device__ __forceinline__ void mx_later_wave (uint32_t* __restrict__ todo, uint
 
 template <int WHAT, int ROUTE>
 __global__ __launch_bounds__(MX_THREADS)
-void matrix_kernel (MxBatch P, const uint32_t* __restrict__ d_pos, const uint32_t* __restrict__ d_code, uint32_t count,
+void matrix_kernel (GdspAnchorTable P, const uint32_t* __restrict__ d_pos, const uint32_t* __restrict__ d_code, uint32_t count,
                     int32_t offLo, uint32_t noffsets, uint32_t bin, uint32_t group, double lo, double hi,
                     double* __restrict__ out, uint32_t* __restrict__ todo, uint32_t* __restrict__ ntodo)
 	{
@@ -190,12 +184,12 @@ void matrix_kernel (MxBatch P, const uint32_t* __restrict__ d_pos, const uint32_
 	for (uint32_t row=blockIdx.x*MX_WAVES+wave ; row<count ; row+=nwave)
 		{
 		const uint32_t code = __builtin_amdgcn_readfirstlane (d_code[row]);
-		const uint32_t vec  = (code >> 1) - P.vec0;
+		const uint32_t vec  = gdsp_anchor_vec (code) - P.vec0;
 		if (vec >= P.nvec) continue;                                  // (a vector of another launch sequence)
 		const double* __restrict__ v = P.v[vec];
 		const int64_t n     = (int64_t) P.n[vec];
 		const int64_t p     = (int64_t) __builtin_amdgcn_readfirstlane (d_pos[row]);
-		const bool    minus = (code & 1) != 0;
+		const bool    minus = gdsp_anchor_minus (code);
 		// the window is the bases g0 .. g0 + noffsets - 1; ascending cell c is column c, or ncols - 1 - c on the minus strand
 		const int64_t g0    = minus? p - (int64_t) offLo - (int64_t) (noffsets - 1) : p + (int64_t) offLo;
 		const uint32_t cell0 = row * ncols;                           // (the call's cells fit 32 bits: the host half sees to it)
@@ -332,34 +326,21 @@ void matrix_kernel (MxBatch P, const uint32_t* __restrict__ d_pos, const uint32_
 		}
 	}
 
-// *d_bad = 1 when some anchor names a vector the call does not have or a position outside its vector
-__global__ void matrix_check_kernel (const uint32_t* __restrict__ d_pos, const uint32_t* __restrict__ d_code, uint32_t count,
-                                     const uint32_t* __restrict__ d_n, uint32_t nvec, uint32_t* __restrict__ d_bad)
-	{
-	bool bad = false;
-	for (uint32_t i=blockIdx.x*blockDim.x+threadIdx.x ; i<count ; i+=gridDim.x*blockDim.x)
-		{
-		const uint32_t vec = d_code[i] >> 1;
-		bad |= (vec >= nvec) || (d_pos[i] >= d_n[(vec < nvec)? vec : 0]);
-		}
-	if (bad) atomicOr (d_bad, 1u);
-	}
-
 // ---------------------------------------------------------------------------------------------- host ----
 static uint32_t mxLaunchRows = 0;                            // see gdsp_matrix_set_launch_rows
 static uint64_t mxLast[4];                                   // see gdsp_genome_matrix_last
 
-static int mx_check_shape (int32_t offLo, uint32_t noffsets, uint32_t bin, int what)
+static int mx_check_shape (int32_t offLo, uint32_t noffsets, uint32_t bin, int what, const char* who = __builtin_FUNCTION ())
 	{
-	GDSP_REQUIRE ((noffsets >= 1) && (noffsets <= MX_MAX_OFFSETS), "the number of offsets must be 1 .. 16384");
-	GDSP_REQUIRE ((int64_t) offLo + noffsets - 1 <= INT32_MAX, "the last offset is beyond int32");
-	GDSP_REQUIRE ((bin >= 1) && (noffsets % bin == 0), "the bin must divide the number of offsets");
-	GDSP_REQUIRE ((what >= GDSP_MATRIX_MEAN) && (what <= GDSP_MATRIX_MAX), "the figure is one of GDSP_MATRIX_*");
+	const int rc = gdsp_anchor_check_offsets (offLo, noffsets, who);
+	if (rc != GDSP_OK) return rc;
+	if ((bin < 1) || (noffsets % bin != 0)) return gdsp_anchor_refuse (who, "the bin must divide the number of offsets");
+	if ((what < GDSP_MATRIX_MEAN) || (what > GDSP_MATRIX_MAX)) return gdsp_anchor_refuse (who, "the figure is one of GDSP_MATRIX_*");
 	return GDSP_OK;
 	}
 
 template <int WHAT>
-static void mx_launch_route (const MxBatch& B, dim3 grid, hipStream_t s, const uint32_t* d_pos, const uint32_t* d_code, uint32_t count,
+static void mx_launch_route (const GdspAnchorTable& B, dim3 grid, hipStream_t s, const uint32_t* d_pos, const uint32_t* d_code, uint32_t count,
                              int32_t offLo, uint32_t noffsets, uint32_t bin, double lo, double hi, double* d_out, uint32_t* d_todo,
                              uint32_t* d_ntodo)
 	{
@@ -382,17 +363,8 @@ static int mx_launch (const gdsp_batch_item* items, int nitems, const uint32_t* 
 	{
 	static_assert ((MX_STAGE % 32 == 0) && (64 * 15 <= MX_STAGE) && (16 * 63 <= MX_STAGE) && (4 * (MX_NARROW_BELOW - 1) <= MX_STAGE), "a stretch holds 64 / G cells");
 	const dim3 grid (std::min<uint32_t> ((count + MX_WAVES - 1) / MX_WAVES, MX_WG_TARGET));
-	for (int i0=0 ; i0<nitems ; i0+=GDSP_BATCH_MAX)
+	return gdsp_anchor_tables (items, nitems, [&] (const GdspAnchorTable& B) -> int
 		{
-		MxBatch B;
-		B.vec0 = (uint32_t) i0;
-		B.nvec = (uint32_t) std::min (nitems - i0, GDSP_BATCH_MAX);
-		for (int j=0 ; j<GDSP_BATCH_MAX ; j++)
-			{
-			const bool have = (uint32_t) j < B.nvec;
-			B.v[j] = have? items[i0+j].d_in : NULL;
-			B.n[j] = have? items[i0+j].n    : 0;
-			}
 		switch (what)
 			{
 			case GDSP_MATRIX_MEAN:  mx_launch_route<GDSP_MATRIX_MEAN>  (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
@@ -403,17 +375,8 @@ static int mx_launch (const gdsp_batch_item* items, int nitems, const uint32_t* 
 			}
 		GDSP_LAUNCH_CHECK ();
 		if (launches != NULL) (*launches)++;
-		}
-	return GDSP_OK;
-	}
-
-static int mx_check_items (const gdsp_batch_item* items, int nitems)
-	{
-	GDSP_REQUIRE (nitems >= 0, "a negative number of vectors");
-	GDSP_REQUIRE ((nitems == 0) || (items != NULL), "NULL items");
-	for (int i=0 ; i<nitems ; i++)
-		GDSP_REQUIRE ((items[i].n == 0) || ((items[i].d_in != NULL) && ((((uintptr_t) items[i].d_in) & 7) == 0)), "a vector must be 8-byte aligned");
-	return GDSP_OK;
+		return GDSP_OK;
+		});
 	}
 
 extern "C" {
@@ -427,7 +390,10 @@ int gdsp_matrix_rows_batch (const gdsp_batch_item* items, int nitems, const uint
                             uint32_t* d_todo, uint32_t* d_ntodo, void* stream)
 	{
 	int rc = mx_check_shape (offLo, noffsets, bin, what);
-	if (rc == GDSP_OK) rc = mx_check_items (items, nitems);
+	if (rc != GDSP_OK) return rc;
+	GDSP_REQUIRE (nitems >= 0, "a negative number of vectors");
+	GDSP_REQUIRE ((nitems == 0) || (items != NULL), "NULL items");
+	rc = gdsp_anchor_check_aligned (items, nitems);
 	if (rc != GDSP_OK) return rc;
 	GDSP_REQUIRE ((count == 0) || ((d_pos != NULL) && (d_code != NULL)), "NULL anchors");
 	GDSP_REQUIRE ((count == 0) || (nitems > 0), "anchors without a vector");
@@ -436,30 +402,8 @@ int gdsp_matrix_rows_batch (const gdsp_batch_item* items, int nitems, const uint
 	hipStream_t s = gdsp_stream (stream);
 	if (count == 0) return GDSP_OK;
 
-	// every anchor inside its vector, decided on the device, where the anchors are
-	{
-	std::vector<uint32_t> h_n (nitems);
-	for (int i=0 ; i<nitems ; i++) h_n[i] = items[i].n;
-	uint32_t* d_work = NULL;                                    // the flag, then the lengths
-	if (hipMalloc ((void**) &d_work, (size_t) (nitems + 1) * sizeof(uint32_t)) != hipSuccess)
-		{ gdsp_set_error ("%s: no device memory for the anchor check", __func__);  return GDSP_ENOMEM; }
-	uint32_t bad = 0;
-	hipError_t e = hipMemsetAsync (d_work, 0, sizeof(uint32_t), s);
-	if (e == hipSuccess) e = hipMemcpyAsync (d_work + 1, h_n.data (), (size_t) nitems * sizeof(uint32_t), hipMemcpyHostToDevice, s);
-	if (e == hipSuccess) e = hipStreamSynchronize (s);           // (h_n is pageable: the copy has left it)
-	if (e == hipSuccess)
-		{
-		uint32_t g = (count + 255) / 256;
-		if (g > 1024) g = 1024;
-		hipLaunchKernelGGL (matrix_check_kernel, dim3 (g), dim3 (256), 0, s, d_pos, d_code, count, d_work + 1, (uint32_t) nitems, d_work);
-		e = hipGetLastError ();
-		}
-	if (e == hipSuccess) e = hipMemcpyAsync (&bad, d_work, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess) e = hipStreamSynchronize (s);
-	(void) hipFree (d_work);
-	GDSP_HIP_TRY (e);
-	GDSP_REQUIRE (bad == 0, "an anchor lies outside its vector");
-	}
+	rc = gdsp_anchor_check (items, nitems, d_pos, d_code, count, s, __func__);     // on the device, where the anchors are
+	if (rc != GDSP_OK) return rc;
 	return mx_launch (items, nitems, d_pos, d_code, count, offLo, noffsets, bin, what, lo, hi, d_out, d_todo, d_ntodo, s, NULL);
 	}
 
@@ -467,20 +411,6 @@ int gdsp_matrix_rows_batch (const gdsp_batch_item* items, int nitems, const uint
 
 // ------------------------------------------------------------------------------------------- end to end ----
 namespace {
-
-// what a device holds during its share of the call
-struct MxHeld
-	{
-	std::vector<void*> bufs;
-	int alloc (void** p, size_t bytes, const char* what)
-		{
-		if (hipMalloc (p, bytes) != hipSuccess)
-			{ *p = NULL;  gdsp_set_error ("gdsp_genome_matrix: no device memory for the %s", what);  return GDSP_ENOMEM; }
-		bufs.push_back (*p);
-		return GDSP_OK;
-		}
-	~MxHeld () { for (void* b : bufs) (void) hipFree (b); }
-	};
 
 double mx_figure_of (const gdsp_interval_stat& st, int what)
 	{
@@ -499,21 +429,10 @@ int mx_on_device (const gdsp_profile_source* sources, const int* mine, int nmine
                   int what, double lo, double hi, double* const* h_rows)
 	{
 	const uint32_t ncols = noffsets / bin;
-	std::vector<gdsp_batch_item> items (nmine);
+	std::vector<gdsp_batch_item> items;
 	std::vector<uint64_t> first (nmine + 1, 0);                   // the device's rows: source k owns first[k] .. first[k+1]
 	std::vector<uint32_t> pos, code;
-	for (int k=0 ; k<nmine ; k++)
-		{
-		const gdsp_profile_source& S = sources[mine[k]];
-		memset (&items[k], 0, sizeof(items[k]));
-		items[k].d_in = S.d_v;  items[k].n = S.n;
-		for (uint32_t a=0 ; a<S.nanchors ; a++)
-			{
-			pos.push_back (S.h_pos[a]);
-			code.push_back ((uint32_t) k * 2 + (((S.h_minus != NULL) && (S.h_minus[a] != 0))? 1u : 0u));
-			}
-		first[k+1] = first[k] + S.nanchors;
-		}
+	gdsp_anchor_gather (sources, mine, nmine, items, pos, code, first.data ());
 	const uint64_t na = first[nmine];
 	if (na == 0) return GDSP_OK;
 	GDSP_REQUIRE (na <= UINT32_MAX, "more than 2^32 - 1 anchors on a device");
@@ -524,12 +443,13 @@ int mx_on_device (const gdsp_profile_source* sources, const int* mine, int nmine
 	perLaunch = std::min (perLaunch, na);
 	const size_t cells = (size_t) perLaunch * ncols;
 
-	MxHeld held;
+	GdspAnchorHeld held;
+	const char* const who = "gdsp_genome_matrix";
 	uint32_t *d_anchors = NULL, *d_todo = NULL;
 	double*   d_out = NULL;
-	int rc = held.alloc ((void**) &d_anchors, 2 * na * sizeof(uint32_t), "anchors");
-	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_out, cells * sizeof(double), "rows");
-	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_todo, (cells + 1) * sizeof(uint32_t), "to-do list");     // the counter, then the list
+	int rc = held.alloc ((void**) &d_anchors, 2 * na * sizeof(uint32_t), who, "anchors");
+	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_out, cells * sizeof(double), who, "rows");
+	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_todo, (cells + 1) * sizeof(uint32_t), who, "to-do list");     // the counter, then the list
 	if (rc != GDSP_OK) return rc;
 	GDSP_HIP_TRY (hipMemcpyAsync (d_anchors,      pos.data (),  na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
 	GDSP_HIP_TRY (hipMemcpyAsync (d_anchors + na, code.data (), na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -572,8 +492,8 @@ int mx_on_device (const gdsp_profile_source* sources, const int* mine, int nmine
 			const int kk = (int) (std::upper_bound (first.begin (), first.end (), a) - first.begin ()) - 1;
 			const int64_t n = items[kk].n, p = pos[a];
 			const int64_t kLo = (int64_t) offLo + (int64_t) j * bin, kHi = kLo + bin - 1;
-			int64_t gLo = (code[a] & 1)? p - kHi : p + kLo;
-			int64_t gHi = (code[a] & 1)? p - kLo : p + kHi;
+			int64_t gLo = gdsp_anchor_minus (code[a])? p - kHi : p + kLo;
+			int64_t gHi = gdsp_anchor_minus (code[a])? p - kLo : p + kHi;
 			gLo = std::max<int64_t> (gLo, 0);  gHi = std::min<int64_t> (gHi, n - 1);
 			double* where = h_rows[mine[kk]] + (size_t) (a - first[kk]) * ncols + j;
 			if (gLo > gHi) { *where = ((what == GDSP_MATRIX_COUNT) || (what == GDSP_MATRIX_SUM))? 0.0 : NAN;  continue; }
@@ -603,14 +523,13 @@ int gdsp_genome_matrix (const gdsp_profile_source* sources, int nsources, int32_
 	if (rc != GDSP_OK) return rc;
 	memset (mxLast, 0, sizeof(mxLast));
 	const uint32_t ncols = noffsets / bin;
-	for (int i=0 ; i<nsources ; i++)
+	rc = gdsp_anchor_check_sources (sources, nsources, [&, who = __func__] (int i) -> int
 		{
-		GDSP_REQUIRE ((sources[i].nanchors == 0) || ((sources[i].h_pos != NULL) && (h_rows[i] != NULL)), "NULL anchors or rows");
-		GDSP_REQUIRE ((sources[i].n == 0) || ((sources[i].d_v != NULL) && ((((uintptr_t) sources[i].d_v) & 7) == 0)), "a vector must be 8-byte aligned");
-		for (uint32_t k=0 ; k<sources[i].nanchors ; k++)
-			GDSP_REQUIRE (sources[i].h_pos[k] < sources[i].n, "an anchor lies outside its vector");
-		mxLast[0] += sources[i].nanchors;
-		}
+		if ((sources[i].nanchors != 0) && ((sources[i].h_pos == NULL) || (h_rows[i] == NULL))) return gdsp_anchor_refuse (who, "NULL anchors or rows");
+		if ((sources[i].n != 0) && ((sources[i].d_v == NULL) || ((((uintptr_t) sources[i].d_v) & 7) != 0))) return gdsp_anchor_refuse (who, "a vector must be 8-byte aligned");
+		return GDSP_OK;
+		}, &mxLast[0]);
+	if (rc != GDSP_OK) return rc;
 	mxLast[1] = mxLast[0] * ncols;
 
 	int home = 0;

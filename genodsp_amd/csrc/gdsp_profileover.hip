@@ -8,13 +8,15 @@
 // PF_LPL = 2 offsets t and t + 256 of the block, so that for one anchor the 64 lanes of a wave read 64 consecutive
 // doubles -- ascending for a plus anchor (base p + k), descending for a minus one (base p - k) -- with plain 8-byte
 // loads, which are right at any 8-byte alignment of the vector.  The workgroups of one block share the anchors of a
-// launch by stride (blockIdx.x); an anchor (position, vector * 2 + minus) is the same for every lane, so the walk is
-// uniform, and it runs one anchor ahead of the sums.  An anchor whose block of offsets lies inside its chromosome reads
+// launch by stride (blockIdx.x); an anchor (its position and gdsp_anchors.h's code word) is the same for every lane, so
+// the walk is uniform, and it runs one anchor ahead of the sums.  An anchor whose block of offsets lies inside its chromosome reads
 // without a test; any other anchor tests 0 <= g < n per lane.  Values that are not sampled (outside the chromosome, not finite, outside lo .. hi) are added as
 // +0.0, which leaves no residual.  Pass 2 is the same walk over fl(fl(v - mean_k)^2), mean_k read once per lane; a q that
 // is not finite is counted and not added.  Expansions, counts and INF counts stay in registers over the whole share and
 // are deposited once at its end: grid x offsets atomics, not anchors x offsets.  No LDS, no barrier, no workgroup waits
 // for another.
+// What concerns the anchors rather than the sums -- their code word, the table of vectors a launch takes, the checks, the
+// gather of a device's sources, the holder of its allocations -- is gdsp_anchors.h's, shared with matrixover.
 
 #include <float.h>
 #include <math.h>
@@ -22,12 +24,12 @@
 #include <vector>
 #include <algorithm>
 #include "gdsp_common.h"
+#include "gdsp_anchors.h"
 #include "gdsp_xsum_dev.h"
 
 #define PF_THREADS   256
 #define PF_LPL       2                                // offsets of a lane: t and t + PF_THREADS
 #define PF_BLOCK     (PF_THREADS * PF_LPL)            // offsets of a workgroup
-#define PF_MAX_OFFSETS GDSP_PROFILE_MAX_OFFSETS
 #define PF_WG_TARGET (256 * 8)                        // workgroups of a launch: all resident (8 waves per SIMD), equal shares
 #define PF_LAUNCH_ANCHORS (1u << 28)                  // anchors of a launch: an anchor gives an offset one value; were every
                                                       // one of them to flush (two deposits, each less than 2^32 into a
@@ -36,17 +38,9 @@
                                                       // (2 per workgroup) and a lane's u32 counts are far below that
 #define PF_W         GDSP_XSUM_WORDS
 
-struct ProfBatch
-	{
-	const double* v[GDSP_BATCH_MAX];
-	uint32_t      n[GDSP_BATCH_MAX];
-	uint32_t      vec0;                                   // the table holds the vectors vec0 .. vec0 + nvec - 1 of the call
-	uint32_t      nvec;
-	};
-
 template <bool SQ>
 __global__ __launch_bounds__(PF_THREADS)
-void profile_kernel (ProfBatch P, const uint32_t* __restrict__ d_pos, const uint32_t* __restrict__ d_code, uint32_t aLo, uint32_t aHi,
+void profile_kernel (GdspAnchorTable P, const uint32_t* __restrict__ d_pos, const uint32_t* __restrict__ d_code, uint32_t aLo, uint32_t aHi,
                      int32_t offLo, uint32_t noffsets, double lo, double hi, const double* __restrict__ d_mean,
                      unsigned long long* __restrict__ d_acc)
 	{
@@ -77,12 +71,12 @@ void profile_kernel (ProfBatch P, const uint32_t* __restrict__ d_pos, const uint
 	auto fetch = [&] (uint64_t i)
 		{
 		const uint32_t code = d_code[i];
-		const uint32_t vec  = (code >> 1) - P.vec0;
+		const uint32_t vec  = gdsp_anchor_vec (code) - P.vec0;
 		const bool     mine = vec < P.nvec;                               // (or a vector of another launch sequence)
 		nv = P.v[mine? vec : 0];
 		nn = mine? (int64_t) P.n[vec] : 0;
 		np = d_pos[i];
-		ns = (code & 1)? -1 : 1;
+		ns = gdsp_anchor_minus (code)? -1 : 1;
 		};
 	uint64_t i = (uint64_t) aLo + blockIdx.x;
 	if (i < aHi) fetch (i);
@@ -152,27 +146,7 @@ __global__ void profile_carry_kernel (unsigned long long* __restrict__ d_acc, ui
 	if (k < noffsets) xs_carry (d_acc + (size_t) k * PF_W);
 	}
 
-// *d_bad = 1 when some anchor names a vector the call does not have or a position outside its vector
-__global__ void profile_check_kernel (const uint32_t* __restrict__ d_pos, const uint32_t* __restrict__ d_code, uint32_t count,
-                                      const uint32_t* __restrict__ d_n, uint32_t nvec, uint32_t* __restrict__ d_bad)
-	{
-	bool bad = false;
-	for (uint32_t i=blockIdx.x*blockDim.x+threadIdx.x ; i<count ; i+=gridDim.x*blockDim.x)
-		{
-		const uint32_t vec = d_code[i] >> 1;
-		bad |= (vec >= nvec) || (d_pos[i] >= d_n[(vec < nvec)? vec : 0]);
-		}
-	if (bad) atomicOr (d_bad, 1u);
-	}
-
 static uint32_t pfLaunchAnchors = PF_LAUNCH_ANCHORS;
-
-static int pf_check_range (int32_t offLo, uint32_t noffsets)
-	{
-	GDSP_REQUIRE ((noffsets >= 1) && (noffsets <= PF_MAX_OFFSETS), "the number of offsets must be 1 .. 16384");
-	GDSP_REQUIRE ((int64_t) offLo + noffsets - 1 <= INT32_MAX, "the last offset is beyond int32");
-	return GDSP_OK;
-	}
 
 extern "C" {
 
@@ -194,51 +168,19 @@ int gdsp_profile_accumulate_batch (const gdsp_batch_item* items, int nitems, con
 	GDSP_REQUIRE ((nitems == 0) || (items != NULL), "NULL items");
 	GDSP_REQUIRE ((count == 0) || ((d_pos != NULL) && (d_code != NULL)), "NULL anchors");
 	GDSP_REQUIRE ((count == 0) || (nitems > 0), "anchors without a vector");
-	int rc = pf_check_range (offLo, noffsets);
+	int rc = gdsp_anchor_check_offsets (offLo, noffsets);
+	if (rc == GDSP_OK) rc = gdsp_anchor_check_aligned (items, nitems);
 	if (rc != GDSP_OK) return rc;
-	for (int i=0 ; i<nitems ; i++)
-		GDSP_REQUIRE ((items[i].n == 0) || ((items[i].d_in != NULL) && ((((uintptr_t) items[i].d_in) & 7) == 0)), "a vector must be 8-byte aligned");
 	hipStream_t s = gdsp_stream (stream);
 	unsigned long long* acc = reinterpret_cast<unsigned long long*> (d_acc);
 	if (count == 0) return GDSP_OK;                              // (zeroed images are canonical)
 
-	// every anchor inside its vector, decided on the device, where the anchors are
-	{
-	std::vector<uint32_t> h_n (nitems);
-	for (int i=0 ; i<nitems ; i++) h_n[i] = items[i].n;
-	uint32_t* d_work = NULL;                                    // the flag, then the lengths
-	if (hipMalloc ((void**) &d_work, (size_t) (nitems + 1) * sizeof(uint32_t)) != hipSuccess)
-		{ gdsp_set_error ("%s: no device memory for the anchor check", __func__);  return GDSP_ENOMEM; }
-	uint32_t bad = 0;
-	hipError_t e = hipMemsetAsync (d_work, 0, sizeof(uint32_t), s);
-	if (e == hipSuccess) e = hipMemcpyAsync (d_work + 1, h_n.data (), (size_t) nitems * sizeof(uint32_t), hipMemcpyHostToDevice, s);
-	if (e == hipSuccess) e = hipStreamSynchronize (s);           // (h_n is pageable: the copy has left it)
-	if (e == hipSuccess)
-		{
-		uint32_t g = (count + 255) / 256;
-		if (g > 1024) g = 1024;
-		hipLaunchKernelGGL (profile_check_kernel, dim3 (g), dim3 (256), 0, s, d_pos, d_code, count, d_work + 1, (uint32_t) nitems, d_work);
-		e = hipGetLastError ();
-		}
-	if (e == hipSuccess) e = hipMemcpyAsync (&bad, d_work, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess) e = hipStreamSynchronize (s);
-	(void) hipFree (d_work);
-	GDSP_HIP_TRY (e);
-	GDSP_REQUIRE (bad == 0, "an anchor lies outside its vector");
-	}
+	rc = gdsp_anchor_check (items, nitems, d_pos, d_code, count, s, __func__);     // on the device, where the anchors are
+	if (rc != GDSP_OK) return rc;
 
 	const uint32_t blocks = (noffsets + PF_BLOCK - 1) / PF_BLOCK;
-	for (int i0=0 ; i0<nitems ; i0+=GDSP_BATCH_MAX)
+	return gdsp_anchor_tables (items, nitems, [&] (const GdspAnchorTable& B) -> int
 		{
-		ProfBatch B;
-		B.vec0 = (uint32_t) i0;
-		B.nvec = (uint32_t) std::min (nitems - i0, GDSP_BATCH_MAX);
-		for (int j=0 ; j<GDSP_BATCH_MAX ; j++)
-			{
-			const bool have = (uint32_t) j < B.nvec;
-			B.v[j] = have? items[i0+j].d_in : NULL;
-			B.n[j] = have? items[i0+j].n    : 0;
-			}
 		for (uint64_t aLo=0 ; aLo<count ; aLo+=pfLaunchAnchors)
 			{
 			const uint32_t aHi = (uint32_t) std::min<uint64_t> (count, aLo + pfLaunchAnchors);
@@ -254,8 +196,8 @@ int gdsp_profile_accumulate_batch (const gdsp_batch_item* items, int nitems, con
 			hipLaunchKernelGGL (profile_carry_kernel, dim3 ((noffsets + 63) / 64), dim3 (64), 0, s, acc, noffsets);
 			GDSP_LAUNCH_CHECK ();
 			}
-		}
-	return GDSP_OK;
+		return GDSP_OK;
+		});
 	}
 
 } // extern "C"
@@ -266,19 +208,6 @@ static uint64_t   pfLast[4];                                 // see gdsp_genome_
 
 namespace {
 
-// what a device holds during a pass: freed once every device's stream has been waited for
-struct ProfHeld
-	{
-	std::vector<std::pair<int, void*>> bufs;                 // (device, allocation)
-	~ProfHeld ()
-		{
-		int home = 0;
-		if (hipGetDevice (&home) != hipSuccess) return;
-		for (auto& b : bufs) { (void) hipSetDevice (b.first);  (void) hipFree (b.second); }
-		(void) hipSetDevice (home);
-		}
-	};
-
 // one pass over every device's sources and anchors into img (noffsets images): pass 1, or with h_mean pass 2
 int pf_genome_pass (const gdsp_profile_source* sources, int nsources, int32_t offLo, uint32_t noffsets, double lo, double hi,
                     const double* h_mean, gdsp_reduce_fn reduce, void* reduceCtx, uint64_t* img)
@@ -287,29 +216,16 @@ int pf_genome_pass (const gdsp_profile_source* sources, int nsources, int32_t of
 	for (int i=0 ; i<nsources ; i++)
 		{ xs[i].d_v = sources[i].d_v;  xs[i].n = sources[i].n;  xs[i].first = 0;  xs[i].device = sources[i].device;  xs[i].stream = sources[i].stream; }
 	const size_t words = (size_t) noffsets * PF_W;
-	ProfHeld held;
+	GdspAnchorHeld held;                                         // freed once every device's stream has been waited for
 	std::vector<gdsp_batch_item> items;
 	std::vector<uint32_t> pos, code;
+	std::vector<int> mine;
 	auto onDevice = [&] (const gdsp_xsum_source* its, int nits, uint64_t* d_acc, void* stream) -> int
 		{
 		// (a device's sources are those of its number, in the caller's order: gdsp_reduce_sources hands them over so)
-		items.clear ();  pos.clear ();  code.clear ();
-		int device = 0;
-		GDSP_HIP_TRY (hipGetDevice (&device));
-		for (int i=0 ; (i<nsources) && (nits>0) ; i++)
-			{
-			if (sources[i].device != its[0].device) continue;
-			const uint32_t vec = (uint32_t) items.size ();
-			gdsp_batch_item it;
-			memset (&it, 0, sizeof(it));
-			it.d_in = sources[i].d_v;  it.n = sources[i].n;
-			items.push_back (it);
-			for (uint32_t k=0 ; k<sources[i].nanchors ; k++)
-				{
-				pos.push_back (sources[i].h_pos[k]);
-				code.push_back (vec * 2 + (((sources[i].h_minus != NULL) && (sources[i].h_minus[k] != 0))? 1u : 0u));
-				}
-			}
+		mine.clear ();
+		for (int i=0 ; (i<nsources) && (nits>0) ; i++) { if (sources[i].device == its[0].device) mine.push_back (i); }
+		gdsp_anchor_gather (sources, mine.data (), (int) mine.size (), items, pos, code);
 		GDSP_REQUIRE ((int) items.size () == nits, "the sources of a device are not what it was handed");
 		GDSP_REQUIRE (pos.size () <= UINT32_MAX, "more than 2^32 - 1 anchors on a device");
 		hipStream_t s = gdsp_stream (stream);
@@ -319,17 +235,15 @@ int pf_genome_pass (const gdsp_profile_source* sources, int nsources, int32_t of
 		double*   d_mean    = NULL;
 		if (na > 0)
 			{
-			if (hipMalloc ((void**) &d_anchors, 2 * na * sizeof(uint32_t)) != hipSuccess)
-				{ gdsp_set_error ("gdsp_genome_profile: no device memory for the anchors");  return GDSP_ENOMEM; }
-			held.bufs.push_back ({ device, d_anchors });
+			const int rc = held.alloc ((void**) &d_anchors, 2 * na * sizeof(uint32_t), "gdsp_genome_profile", "anchors");
+			if (rc != GDSP_OK) return rc;
 			GDSP_HIP_TRY (hipMemcpyAsync (d_anchors,      pos.data (),  na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
 			GDSP_HIP_TRY (hipMemcpyAsync (d_anchors + na, code.data (), na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
 			}
 		if (h_mean != NULL)
 			{
-			if (hipMalloc ((void**) &d_mean, noffsets * sizeof(double)) != hipSuccess)
-				{ gdsp_set_error ("gdsp_genome_profile: no device memory for the means");  return GDSP_ENOMEM; }
-			held.bufs.push_back ({ device, d_mean });
+			const int rc = held.alloc ((void**) &d_mean, noffsets * sizeof(double), "gdsp_genome_profile", "means");
+			if (rc != GDSP_OK) return rc;
 			GDSP_HIP_TRY (hipMemcpyAsync (d_mean, h_mean, noffsets * sizeof(double), hipMemcpyHostToDevice, s));
 			}
 		GDSP_HIP_TRY (hipStreamSynchronize (s));                 // (pos and code are reused for the next device)
@@ -363,18 +277,13 @@ int gdsp_genome_profile (const gdsp_profile_source* sources, int nsources, int32
 	GDSP_REQUIRE ((count != NULL) && (sum != NULL) && (mean != NULL) && (variance != NULL) && (stddev != NULL), "NULL result");
 	GDSP_REQUIRE (nsources >= 0, "a negative number of sources");
 	GDSP_REQUIRE ((nsources == 0) || (sources != NULL), "NULL sources");
-	int rc = pf_check_range (offLo, noffsets);
+	int rc = gdsp_anchor_check_offsets (offLo, noffsets);
 	if (rc != GDSP_OK) return rc;
 	GDSP_REQUIRE ((bin >= 1) && (noffsets % bin == 0), "the bin must divide the number of offsets");
 	GDSP_REQUIRE (!((pfComm != NULL) && (reduce != NULL)), "a host reduction hook next to a communicator");
 	memset (pfLast, 0, sizeof(pfLast));
-	for (int i=0 ; i<nsources ; i++)
-		{
-		GDSP_REQUIRE ((sources[i].nanchors == 0) || (sources[i].h_pos != NULL), "NULL anchors");
-		for (uint32_t k=0 ; k<sources[i].nanchors ; k++)
-			GDSP_REQUIRE (sources[i].h_pos[k] < sources[i].n, "an anchor lies outside its vector");
-		pfLast[0] += sources[i].nanchors;
-		}
+	rc = gdsp_anchor_check_sources (sources, nsources, [] (int) { return GDSP_OK; }, &pfLast[0]);
+	if (rc != GDSP_OK) return rc;
 
 	const uint32_t ncols = noffsets / bin;
 	std::vector<uint64_t> img ((size_t) noffsets * PF_W);

@@ -13,14 +13,11 @@ import math
 import numpy as np
 
 import xsum_ref as ref
+from anchor_cases import anchors_array
 
 DBL_MAX = ref.DBL_MAX
 MAX_OFFSETS = 16384
 FIGURES = ("mean", "sum", "count", "min", "max")              # GDSP_MATRIX_MEAN .. GDSP_MATRIX_MAX
-
-
-def anchors_array(anchors):
-    return np.asarray(anchors, dtype=np.int64).reshape(-1, 3)
 
 
 def cell_interval(n, p, s, off_lo, bin, j):

@@ -14,14 +14,11 @@ import math
 import numpy as np
 
 import xsum_ref as ref
+from anchor_cases import anchors_array
 
 DBL_MAX = ref.DBL_MAX
 MAX_OFFSETS = 16384
 CHUNK = 1 << 21                                  # (anchor, offset) pairs looked at in one numpy step
-
-
-def anchors_array(anchors):
-    return np.asarray(anchors, dtype=np.int64).reshape(-1, 3)
 
 
 def gather(vectors, anchors, off_lo, noffsets, lo=-DBL_MAX, hi=DBL_MAX, mutant=None):

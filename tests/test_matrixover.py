@@ -14,41 +14,13 @@ import math
 import numpy as np
 import pytest
 
+import anchor_cases as cases
 import matrixover_ref as mref
 import xsum_ref as ref
+from anchor_cases import depth, dev, every_base, random_anchors, real, up
 
 DBL_MAX = ref.DBL_MAX
 FIGURES = mref.FIGURES
-
-
-def dev():
-    import genodsp_amd as g
-    g.set_device(0)
-    return g
-
-
-def up(g, vectors):
-    return [g.DeviceVector.from_numpy(v) for v in vectors]
-
-
-def real(n, rng):
-    return rng.standard_normal(n) * 10.0
-
-
-def depth(n, rng):
-    return rng.integers(0, 60, n).astype(np.float64)
-
-
-def every_base(n, c=0):
-    return [(c, p, s) for p in range(n) for s in (1, -1)]
-
-
-def random_anchors(vectors, count, rng):
-    out = []
-    for _ in range(count):
-        c = int(rng.integers(0, len(vectors)))
-        out.append((c, int(rng.integers(0, vectors[c].size)), int(rng.choice([1, -1]))))
-    return out
 
 
 def check(g, d, v, anchors, off_lo, noffsets, bin, lo=-DBL_MAX, hi=DBL_MAX, what="", host=None, figures=FIGURES):
@@ -333,3 +305,17 @@ def test_what_is_refused():
     assert g.genome_matrix(v, ok, 2 ** 31 - 10, 10, what="count").tolist() == [[0.0] * 10]   # (the last offset is INT32_MAX)
     assert g.genome_matrix(v, ok, -3, 6, 2, what="sum").tolist() == [[47.0 + 48.0, 49.0 + 50.0, 51.0 + 52.0]]
     assert g.genome_matrix(v, [(0, 50, -1)], -3, 6, 2, what="sum").tolist() == [[53.0 + 52.0, 51.0 + 50.0, 49.0 + 48.0]]
+
+
+@pytest.mark.gpu
+def test_the_anchor_check_sees_every_anchor():
+    """the device's check of matrix_rows (genome_matrix refuses on the host before it): a bad last anchor among one
+    thread's, one workgroup's, the next workgroup's, and where only the check's stride loop reaches it"""
+    g = dev()
+    v = up(g, [np.arange(cases.CHECK_N, dtype=np.float64)])
+    most = cases.CHECK_COUNTS[-1]
+    rows, todo = g.matrix_rows(v, cases.check_anchors(most), 0, 1, 1)
+    assert most == 262145 and rows.shape == (most, 1) and np.all(rows == 50.0) and todo.size == 0
+    for count in cases.CHECK_COUNTS:
+        with pytest.raises(g.GdspError):
+            g.matrix_rows(v, cases.check_anchors(count, bad_last=True), 0, 1, 1)

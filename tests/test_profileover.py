@@ -8,23 +8,15 @@ import math
 import numpy as np
 import pytest
 
+import anchor_cases as cases
 import profileover_ref as pref
 import xsum_ref as ref
+from anchor_cases import depth, dev, every_base, random_anchors, real, up
 
 WORDS = 72
 B = 512                                            # gdsp_profile_block(): test_block_is_what_the_shapes_assume
 DBL_MAX = ref.DBL_MAX
 FIGURES = ("count", "sum", "mean", "variance", "stddev", "stderr")
-
-
-def dev():
-    import genodsp_amd as g
-    g.set_device(0)
-    return g
-
-
-def up(g, vectors):
-    return [g.DeviceVector.from_numpy(v) for v in vectors]
 
 
 def check(got, want, what=""):
@@ -41,26 +33,6 @@ def same_images(a, b):
 
 def same_bits(a, b):
     return all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in FIGURES)
-
-
-def real(n, rng):
-    return rng.standard_normal(n) * 10.0
-
-
-def depth(n, rng):
-    return rng.integers(0, 60, n).astype(np.float64)
-
-
-def every_base(n, c=0):
-    return [(c, p, s) for p in range(n) for s in (1, -1)]
-
-
-def random_anchors(vectors, count, rng):
-    out = []
-    for _ in range(count):
-        c = int(rng.integers(0, len(vectors)))
-        out.append((c, int(rng.integers(0, vectors[c].size)), int(rng.choice([1, -1]))))
-    return out
 
 
 @pytest.mark.gpu
@@ -301,6 +273,20 @@ def test_what_is_refused():
             g.profile_images(v, anchors, 0, noffsets)
     assert g.genome_profile(v, ok, 2 ** 31 - 10, 10)["count"].tolist() == [0] * 10     # (the last offset is INT32_MAX)
     assert g.genome_profile(v, ok, -2 ** 31, 16384, bin=16384)["count"].tolist() == [0]
+
+
+@pytest.mark.gpu
+def test_the_anchor_check_sees_every_anchor():
+    """the device's check of profile_images (genome_profile refuses on the host before it): a bad last anchor among one
+    thread's, one workgroup's, the next workgroup's, and where only the check's stride loop reaches it"""
+    g = dev()
+    v = up(g, [np.arange(cases.CHECK_N, dtype=np.float64)])
+    most = cases.CHECK_COUNTS[-1]
+    img = g.profile_images(v, cases.check_anchors(most), 0, 1)
+    assert img.shape == (1, WORDS) and int(img[0, 68]) == most == 262145
+    for count in cases.CHECK_COUNTS:
+        with pytest.raises(g.GdspError):
+            g.profile_images(v, cases.check_anchors(count, bad_last=True), 0, 1)
 
 
 # -------------------------------------------------------------------------------------- identities ----
