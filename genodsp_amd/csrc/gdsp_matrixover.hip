@@ -188,7 +188,7 @@ void matrix_kernel (GdspAnchorTable P, const uint32_t* __restrict__ d_pos, const
 		if (vec >= P.nvec) continue;                                  // (a vector of another launch sequence)
 		const double* __restrict__ v = P.v[vec];
 		const int64_t n     = (int64_t) P.n[vec];
-		const int64_t p     = (int64_t) __builtin_amdgcn_readfirstlane (d_pos[row]);
+		const int64_t p     = (int64_t) (uint32_t) __builtin_amdgcn_readfirstlane (d_pos[row]);   // (the builtin returns int: unsigned again before it widens, or a position from 2^31 on turns negative)
 		const bool    minus = gdsp_anchor_minus (code);
 		// the window is the bases g0 .. g0 + noffsets - 1; ascending cell c is column c, or ncols - 1 - c on the minus strand
 		const int64_t g0    = minus? p - (int64_t) offLo - (int64_t) (noffsets - 1) : p + (int64_t) offLo;

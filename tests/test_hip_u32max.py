@@ -18,13 +18,10 @@ import pytest
 
 from conftest import ROOT, bits_equal
 from oracle import cpu
+from u32max_cases import CHROM, M, N, SEED, check, fetch, places, regenerate
 
 pytestmark = pytest.mark.gpu
 
-SEED = 20240611
-N = 2 ** 32 - 1
-CHROM = 3
-M = 6000
 BIN = os.path.join(ROOT, "genodsp_amd", "genodsp_hip")
 
 
@@ -39,34 +36,6 @@ def real(gd):
     v = gd.synth_coverage(SEED, CHROM, 0, N, 1)
     gd.sync()
     return v
-
-
-def places():
-    top = []
-    for tile in (2304, 2304 - 10, 3984, 4096, 16384, 32768, 1 << 18):      # last seam of each tiling below 2^32
-        top.append(min(N - M, (N // tile) * tile - M // 2))
-    rng = np.random.default_rng(5)
-    return [0, 2 ** 31 - M // 2, 2 ** 31, N - M] + top + [int(s) for s in rng.integers(0, N - M, 6)]
-
-
-def fetch(vec, start, count):
-    return vec.buf.download(np.float64, count, vec.offset + 8 * start)
-
-
-def regenerate(start, count, halo, mode=1):
-    lo, hi = max(0, start - halo), min(N, start + count + halo)
-    return cpu.synth_coverage(SEED, CHROM, lo, hi - lo, mode), start - lo
-
-
-def check(vec, oracle_fn, halo, bound_fn=None):
-    for s in places():
-        x, left = regenerate(s, M, halo)
-        want = oracle_fn(x)[left:left + M]
-        got = fetch(vec, s, M)
-        if bound_fn is None:
-            assert bits_equal(got, want), (s, int(np.flatnonzero(got != want)[0]))
-        else:
-            assert np.all(np.abs(got - want) <= bound_fn(x)[left:left + M]), s
 
 
 def test_signal_regenerates(gd, real):
