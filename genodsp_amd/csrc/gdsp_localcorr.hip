@@ -14,69 +14,52 @@
 //              truncates the window at the chromosome ends.  Every slot of every record is written.
 //   2. main    one workgroup of LC_THREADS threads owns T outputs and stages the NS = 16 LC_THREADS positions they read
 //              (HL + T + HR, the reaches rounded up to even so that every tile starts on a 16-byte boundary): x whole
-//              from d_x, the tile's own T track values from d_y, the track's halos from the tile's record.  Then, as
-//              gdsp_localstats.hip does for its two sums:
-//                a. the staged values lie in LDS in blocks of 16 at a pitch of 17 doubles, x and y apart;
-//                b. thread p sums block p for all five sums, and one scan over the workgroup leaves b[s][k] = the sums
-//                   of blocks 0 .. k-1.  P(e), the sums of the staged positions below e, is b[.][e/16] plus up to 15
-//                   terms of block e/16;
-//                c. a thread takes `per` consecutive outputs, forms P(a) and P(a+W) for its first window and slides
-//                   both ends one base per output; S = P(a+W) - P(a).  No sum reaches further than the staged tile;
-//                d. the results wait in registers until every thread of the workgroup has read the inputs (a barrier),
-//                   go back to LDS and leave as 16-byte stores over the tile's own T bases of d_y.
+//              from d_x, the tile's own T track values from d_y, the track's halos from the tile's record.  From there
+//              the tile is gdsp_window_sums_tile.h's, which localstats shares -- the two LDS images, the block sums of
+//              all five sums and their scan, P(e), the slide, the results through LDS -- and its comments hold the
+//              layout and its reasons; the results leave over the tile's own T bases of d_y.
 // No workgroup reads a live base that another one writes; nothing is polled and nothing waits on another workgroup.
 // One form: 512 threads, 8192 staged positions of each input, 156.6 KiB of LDS, one workgroup per CU.  8192 staged
 // positions less a tile of 4096 outputs is what fixes GDSP_LOCALCORR_MAX_WINDOW at 4097.
 
 #include <stdlib.h>
 #include <algorithm>
-#include "gdsp_common.h"
+#include "gdsp_window_sums_tile.h"
 #include "gdsp_pieces.h"
 
-#define LC_G            16                                                // staged positions per block
-#define LC_PITCH        17                                                // doubles from one block to the next in LDS
 #define LC_THREADS      512
-#define LC_NS           (LC_THREADS * LC_G)                               // staged positions of each input
+#define LC_NS           (LC_THREADS * WS_G)                               // staged positions of each input
 #define LC_MIN_TILE     4096
 #define LC_COPY_THREADS 256
 #define LC_NWHAT        4
-#define LC_SUMS         5                                                 // x, y, fl(x x), fl(y y), fl(x y)
 
-struct LcLds
+struct LcTerms                                                            // x, y, fl(x x), fl(y y), fl(x y)
 	{
-	double x[(LC_THREADS + 1) * LC_PITCH];                                // staged signal (one spare block: P(NS) looks at none of it); the results in the end
-	double y[(LC_THREADS + 1) * LC_PITCH];                                // staged track
-	double b[LC_SUMS][LC_THREADS + 1];                                    // [s][k]: sum s over blocks 0 .. k-1
-	double w[LC_SUMS][LC_THREADS / 64];                                   // the waves' totals
+	static constexpr int INPUTS = 2, SUMS = 5;
+	static __device__ __forceinline__ void add (double p[SUMS], const double in[INPUTS])
+		{
+		const double x = in[0], y = in[1];
+		p[0] = __dadd_rn (p[0], x);                  p[1] = __dadd_rn (p[1], y);
+		p[2] = __dadd_rn (p[2], __dmul_rn (x, x));   p[3] = __dadd_rn (p[3], __dmul_rn (y, y));
+		p[4] = __dadd_rn (p[4], __dmul_rn (x, y));
+		}
 	};
+typedef WsLds<LC_THREADS, LcTerms::INPUTS, LcTerms::SUMS> LcLds;          // v[0]: the staged signal, v[1]: the staged track
 static_assert (sizeof (LcLds) <= 160 * 1024, "one workgroup per CU");
 
-// host and device: the reaches rounded up to even, the outputs per tile and per thread
-__host__ __device__ constexpr uint32_t lc_even (uint32_t w) { return (w + 1) & ~1u; }
-__host__ __device__ constexpr uint32_t lc_tile (uint32_t lft, uint32_t rgt) { return LC_NS - lc_even (lft) - lc_even (rgt); }
+__host__ __device__ constexpr uint32_t lc_tile (uint32_t lft, uint32_t rgt) { return ws_tile (LC_THREADS, lft, rgt); }
 static_assert (lc_tile ((GDSP_LOCALCORR_MAX_WINDOW - 1) - (GDSP_LOCALCORR_MAX_WINDOW - 1) / 2, (GDSP_LOCALCORR_MAX_WINDOW - 1) / 2) == LC_MIN_TILE,
                "the largest window leaves a tile of 4096 outputs");
-// localstats' choice (ls_per): lane l reads staged position c + l per, at c + l per + (c + l per) / 16 in LDS.  Over the
-// 32 lanes that share an LDS cycle those are 32 different banks for per = 16 and at most two to a bank for 7, 8, 11, 13
-// and 14, whatever c is; the other strides put six to eight on one bank.  T >= 4096 here, so per >= 8.
-__host__ __device__ __forceinline__ uint32_t lc_per (uint32_t T)
-	{
-	const uint32_t need = (T + LC_THREADS - 1) / LC_THREADS;              // <= LC_G, as T <= LC_NS
-	return (need <= 8)? 8 : (need <= 11)? 11 : (need <= 13)? 13 : (need <= 14)? 14 : LC_G;
-	}
-
-__device__ __forceinline__ int lc_at (int e) { return e + (e >> 4); }    // where staged position e lies in LcLds::x and ::y
-
-struct LcArgs { uint32_t W, lft, rgt, per; };
+static_assert (LC_MIN_TILE / LC_THREADS >= 8, "ws_per never takes its 7 here");
 
 // ---- launch 1: tile `gt` of the table -> its record: y[o0-HL .. o0) and y[o0+T .. o0+T+HR), 0.0 outside the vector
 __global__ __launch_bounds__(LC_COPY_THREADS)
-void localcorr_copy_kernel (GdspBatch B, LcArgs A, double* __restrict__ records)
+void localcorr_copy_kernel (GdspBatch B, WsArgs A, double* __restrict__ records)
 	{
 	const double* unused;  double* y;  uint32_t n;
 	const uint32_t tile = gdsp_batch_tile (B, unused, y, n);
 	const uint32_t gt   = gdsp_xcd_tile (blockIdx.x, B.tile0[GDSP_BATCH_MAX]);        // the tile's index in the table
-	const int      HL   = (int) lc_even (A.lft), HR = (int) lc_even (A.rgt);
+	const int      HL   = (int) ws_even (A.lft), HR = (int) ws_even (A.rgt);
 	const int      T    = LC_NS - HL - HR, len = HL + HR;
 	const int64_t  o0   = (int64_t) tile * T;                             // (even: a pair never straddles the two halves or an end of the tile)
 	double* rec = records + (size_t) gt * len;
@@ -96,36 +79,8 @@ void localcorr_copy_kernel (GdspBatch B, LcArgs A, double* __restrict__ records)
 	}
 
 // ---- launch 2
-// P(e): the five sums over the staged positions below e (e <= NS)
-__device__ __forceinline__ void lc_prefix (const LcLds& S, int e, double p[LC_SUMS])
-	{
-	const int blk = e >> 4, r = e & 15;
-	const double* xb = S.x + blk * LC_PITCH;
-	const double* yb = S.y + blk * LC_PITCH;
-#pragma unroll
-	for (int s=0 ; s<LC_SUMS ; s++) p[s] = S.b[s][blk];
-#pragma unroll
-	for (int k=0 ; k<LC_G-1 ; k++)
-		{
-		const double x = xb[k], y = yb[k];                                // (inside the arrays whatever r is)
-		if (k < r)
-			{
-			p[0] = __dadd_rn (p[0], x);                  p[1] = __dadd_rn (p[1], y);
-			p[2] = __dadd_rn (p[2], __dmul_rn (x, x));   p[3] = __dadd_rn (p[3], __dmul_rn (y, y));
-			p[4] = __dadd_rn (p[4], __dmul_rn (x, y));
-			}
-		}
-	}
-
-__device__ __forceinline__ void lc_add (double p[LC_SUMS], double x, double y)
-	{
-	p[0] = __dadd_rn (p[0], x);                  p[1] = __dadd_rn (p[1], y);
-	p[2] = __dadd_rn (p[2], __dmul_rn (x, x));   p[3] = __dadd_rn (p[3], __dmul_rn (y, y));
-	p[4] = __dadd_rn (p[4], __dmul_rn (x, y));
-	}
-
 template <int WHAT>
-__device__ __forceinline__ double lc_figure (const double S[LC_SUMS], double md)
+__device__ __forceinline__ double lc_figure (const double S[LcTerms::SUMS], double md)
 	{
 	const double Sx = S[0], Sy = S[1];
 	const double Nxy = __dsub_rn (__dmul_rn (md, S[4]), __dmul_rn (Sx, Sy));
@@ -147,55 +102,33 @@ __device__ __forceinline__ double lc_figure (const double S[LC_SUMS], double md)
 
 template <int WHAT>
 __global__ __launch_bounds__(LC_THREADS)
-void localcorr_kernel (GdspBatch B, LcArgs A, const double* __restrict__ records)      // one grid over every vector of the table (gdsp_common.h)
+void localcorr_kernel (GdspBatch B, WsArgs A, const double* __restrict__ records)      // one grid over every vector of the table (gdsp_common.h)
 	{
 	__shared__ __attribute__((aligned(16))) LcLds S;
 	const double* x;  double* y;  uint32_t n;
 	const uint32_t tile = gdsp_batch_tile (B, x, y, n);
 	const uint32_t gt   = gdsp_xcd_tile (blockIdx.x, B.tile0[GDSP_BATCH_MAX]);
-	const int     tid  = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int     HL   = (int) lc_even (A.lft);
-	const int     T    = LC_NS - HL - (int) lc_even (A.rgt);
-	const int64_t o0   = (int64_t) tile * T;                              // first output of the tile (even)
-	const int64_t g0   = o0 - HL;                                         // first staged base (even; negative in tile 0)
-	const double* rec  = records + (size_t) gt * (LC_NS - T);             // HL values before the tile, then HR behind it
+	const WsTile   t    = ws_tile_of<LC_THREADS> (A, tile);
+	const int      tid  = threadIdx.x, HL = t.HL, T = t.T;
+	const int64_t  o0   = t.o0;
+	const double*  rec  = records + (size_t) gt * (LC_NS - T);            // HL values before the tile, then HR behind it
 
-	// ---- 1. stage: x whole, y from the tile's own bases and from its record
-	if ((g0 >= 0) && (g0 + LC_NS <= (int64_t) n))
-		{
-		const double2* src = reinterpret_cast<const double2*> (x + g0);
-		double2 r[LC_G/2];
-#pragma unroll
-		for (int u=0 ; u<LC_G/2 ; u++) r[u] = gdsp_ld2 (&src[u*LC_THREADS + tid]);          // all loads in flight
-#pragma unroll
-		for (int u=0 ; u<LC_G/2 ; u++)
-			{
-			double* dst = S.x + lc_at (2 * (u*LC_THREADS + tid));         // (an even position and the next share a block)
-			dst[0] = r[u].x;  dst[1] = r[u].y;
-			}
-		}
-	else
-		{
-		for (int e=tid ; e<LC_NS ; e+=LC_THREADS)
-			{
-			const int64_t g = g0 + e;
-			S.x[lc_at (e)] = ((g >= 0) && (g < (int64_t) n))? x[g] : 0.0;
-			}
-		}
+	// ---- stage: x whole, y from the tile's own bases and from its record
+	ws_stage<LC_THREADS> (S.v[0], x, t.g0, n);
 	if (o0 + T <= (int64_t) n)
 		{
-		double2 r[LC_G/2];
+		double2 r[WS_G/2];
 #pragma unroll
-		for (int u=0 ; u<LC_G/2 ; u++)
+		for (int u=0 ; u<WS_G/2 ; u++)
 			{
 			const int e = 2 * (u*LC_THREADS + tid);                       // HL and T are even: a pair has one source
 			const double* src = (e < HL)? rec + e : (e < HL + T)? y + o0 + (e - HL) : rec + (e - T);
 			r[u] = *reinterpret_cast<const double2*> (src);
 			}
 #pragma unroll
-		for (int u=0 ; u<LC_G/2 ; u++)
+		for (int u=0 ; u<WS_G/2 ; u++)
 			{
-			double* dst = S.y + lc_at (2 * (u*LC_THREADS + tid));
+			double* dst = S.v[1] + ws_at (2 * (u*LC_THREADS + tid));
 			dst[0] = r[u].x;  dst[1] = r[u].y;
 			}
 		}
@@ -207,92 +140,11 @@ void localcorr_kernel (GdspBatch B, LcArgs A, const double* __restrict__ records
 			if (e < HL)          v = rec[e];
 			else if (e < HL + T) v = (o0 + (e - HL) < (int64_t) n)? y[o0 + (e - HL)] : 0.0;
 			else                 v = rec[e - T];
-			S.y[lc_at (e)] = v;
+			S.v[1][ws_at (e)] = v;
 			}
 		}
-	__syncthreads ();
-
-	// ---- 2. block sums and their running sums
-		{
-		const double* xb = S.x + tid * LC_PITCH;
-		const double* yb = S.y + tid * LC_PITCH;
-		double run[LC_SUMS];
-#pragma unroll
-		for (int s=0 ; s<LC_SUMS ; s++) run[s] = 0.0;
-#pragma unroll
-		for (int u=0 ; u<LC_G ; u++) lc_add (run, xb[u], yb[u]);
-		for (int d=1 ; d<64 ; d*=2)
-			{
-#pragma unroll
-			for (int s=0 ; s<LC_SUMS ; s++)
-				{
-				const double up = __shfl_up (run[s], d, 64);
-				if (lane >= d) run[s] = __dadd_rn (run[s], up);
-				}
-			}
-		if (lane == 63)
-			{
-#pragma unroll
-			for (int s=0 ; s<LC_SUMS ; s++) S.w[s][wave] = run[s];
-			}
-		if (tid < LC_SUMS) S.b[tid][0] = 0.0;
-		__syncthreads ();
-#pragma unroll
-		for (int s=0 ; s<LC_SUMS ; s++)
-			{
-			double before = 0.0;
-			for (int w=0 ; w<wave ; w++) before = __dadd_rn (before, S.w[s][w]);
-			S.b[s][tid + 1] = __dadd_rn (before, run[s]);
-			}
-		}
-	__syncthreads ();
-
-	// ---- 3. `per` consecutive outputs per thread
-	const int o  = tid * (int) A.per;                                     // my first output, in the tile
-	const int a0 = HL - (int) A.lft + o;                                  // its window is the staged positions [a0, a0+W)
-	double res[LC_G];
-	double l[LC_SUMS], r[LC_SUMS];
-#pragma unroll
-	for (int s=0 ; s<LC_SUMS ; s++) l[s] = r[s] = 0.0;
-	if ((o < T) && (o0 + o < (int64_t) n))
-		{
-		lc_prefix (S, a0, l);
-		lc_prefix (S, a0 + (int) A.W, r);
-		}
-#pragma unroll
-	for (int u=0 ; u<LC_G ; u++)
-		{
-		const int64_t c = o0 + o + u;                                     // the base
-		res[u] = 0.0;
-		if ((u >= (int) A.per) || (o + u >= T) || (c >= (int64_t) n)) continue;
-		if (u > 0)
-			{
-			const int el = lc_at (a0 + u - 1), er = lc_at (a0 + (int) A.W + u - 1);
-			lc_add (l, S.x[el], S.y[el]);
-			lc_add (r, S.x[er], S.y[er]);
-			}
-		const int64_t lo = (c > (int64_t) A.lft)? c - A.lft : 0;
-		const int64_t hi = (c + A.rgt < (int64_t) n - 1)? c + A.rgt : (int64_t) n - 1;
-		double sums[LC_SUMS];
-#pragma unroll
-		for (int s=0 ; s<LC_SUMS ; s++) sums[s] = __dsub_rn (r[s], l[s]);
-		res[u] = lc_figure<WHAT> (sums, (double) (hi - lo + 1));
-		}
-	__syncthreads ();                                                     // every thread has read the inputs
-
-	// ---- 4. the outputs, through LDS, two per lane (T and o0 are even), over the tile's own bases of the track
-#pragma unroll
-	for (int u=0 ; u<LC_G ; u++)
-		if ((u < (int) A.per) && (o + u < T)) S.x[lc_at (o + u)] = res[u];
-	__syncthreads ();
-	for (int q=tid ; 2*q<T ; q+=LC_THREADS)
-		{
-		const int64_t g = o0 + 2*q;
-		if (g >= (int64_t) n) break;
-		const double* v = S.x + lc_at (2*q);
-		if (g + 1 < (int64_t) n) gdsp_st2 (reinterpret_cast<double2*> (y + g), make_double2 (v[0], v[1]));
-		else                     y[g] = v[0];
-		}
+	ws_block_sums<LC_THREADS, LcTerms> (S);
+	ws_outputs<LC_THREADS, LcTerms> (S, A, t, n, y, [] (int, const double* sums, double md) { return lc_figure<WHAT> (sums, md); });
 	}
 
 // ---------------------------------------------------------------------------------------------- host ----
@@ -311,7 +163,7 @@ static bool lc_timed (void)
 	return value;
 	}
 
-static void lc_launch (const GdspBatch& B, uint32_t tiles, int what, const LcArgs& A, const double* records, hipStream_t s)
+static void lc_launch (const GdspBatch& B, uint32_t tiles, int what, const WsArgs& A, const double* records, hipStream_t s)
 	{
 	switch (what)
 		{
@@ -324,11 +176,10 @@ static void lc_launch (const GdspBatch& B, uint32_t tiles, int what, const LcArg
 
 static int localcorr_run (const gdsp_batch_item* items, int nitems, uint32_t W, int what, void* stream)
 	{
-	LcArgs A;
-	A.W = W;  A.rgt = (W - 1) / 2;  A.lft = (W - 1) - A.rgt;
+	WsArgs A = ws_window (W);
 	const uint64_t T   = lc_tile (A.lft, A.rgt);
 	const size_t   len = LC_NS - T;                                       // doubles per record (0 at W = 1: no halo, no launch 1)
-	A.per = lc_per ((uint32_t) T);
+	A.per = ws_per ((uint32_t) T, LC_THREADS);
 	lcTimes[0] = lcTimes[1] = 0;
 	auto tilesOf = [=] (uint32_t n) { return ((uint64_t) n + T - 1) / T; };
 
