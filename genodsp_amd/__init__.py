@@ -1247,6 +1247,53 @@ def interval_stats_last():
     return d
 
 
+# ------------------------------------------ percentilesover / medianover (not in the reference) ----
+
+def interval_percentiles_short():
+    """The longest interval the one-read (LDS sort) route takes; results never depend on it."""
+    return int(lib().gdsp_interval_percentiles_short())
+
+
+def interval_percentiles_piece():
+    """The piece a longer interval is cut into for the radix select; results never depend on it."""
+    return int(lib().gdsp_interval_percentiles_piece())
+
+
+def interval_percentiles_set_batch(long_queries=0):
+    """Long (interval, percentile) queries per batch of the radix select; 0: the default.  For tests."""
+    call("gdsp_interval_percentiles_set_batch", int(long_queries))
+
+
+def interval_percentiles(v, start, end, p_thousandths, lo=-DBL_MAX, hi=DBL_MAX, stream=None, vec=None):
+    """The sample's size and, for every percentile of p_thousandths, the exact order statistic of v over the intervals
+    [start[i], end[i]) (gdsp_interval_percentiles: statsover's sample, percentile's order and rank rule; NaN where the
+    sample is empty).  -> {"count": uint32[n], "values": float64[n, len(p_thousandths)]} in the caller's order.
+    v: a DeviceVector or a (vector, first, count) stretch of one; or a LIST of them with vec[i] naming interval i's
+    vector (gdsp_interval_percentiles_batch).  Waits."""
+    vecs = v if isinstance(v, list) else [v]
+    items = _read_only_items(vecs)
+    start = np.ascontiguousarray(start, dtype=np.uint32)
+    end = np.ascontiguousarray(end, dtype=np.uint32)
+    assert start.shape == end.shape and start.ndim == 1
+    which = None if vec is None else np.ascontiguousarray(vec, dtype=np.uint32)
+    assert which is None or which.shape == start.shape
+    pcts = np.ascontiguousarray(np.atleast_1d(p_thousandths), dtype=np.uint32)
+    count = np.zeros(start.size, np.uint32)
+    values = np.zeros((start.size, max(1, pcts.size)), np.float64)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    call("gdsp_interval_percentiles_batch", items, len(vecs), vp(which), vp(start), vp(end), start.size, vp(pcts), pcts.size,
+         float(lo), float(hi), vp(count), vp(values), _sp(stream))
+    return {"count": count, "values": values[:, :pcts.size]}
+
+
+def interval_percentiles_last():
+    """What the last interval_percentiles did: intervals, those of the short and of the long route, histogram passes,
+    batches of long queries, long queries that ended before the last digit."""
+    out = (C.c_uint64 * 6)()
+    lib().gdsp_interval_percentiles_last(out)
+    return dict(zip(("intervals", "short", "long", "passes", "batches", "ended_early"), [int(x) for x in out]))
+
+
 # ------------------------------------------------------- segments (not in the reference) ----
 
 RUN_PIECE = np.dtype([("vec", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32),

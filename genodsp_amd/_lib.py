@@ -211,6 +211,12 @@ SIGNATURES = {
     "gdsp_interval_stats_combine": (_int, [_vp, _u32, _vp, _vp]),
     "gdsp_interval_stats_last": (None, [_vp]),
     "gdsp_interval_stats_times": (None, [_vp]),
+    "gdsp_interval_percentiles_short": (_u32, []),
+    "gdsp_interval_percentiles_piece": (_u32, []),
+    "gdsp_interval_percentiles": (_int, [_vp, _u32, _vp, _vp, _u32, _vp, _int, _f64, _f64, _vp, _vp, _vp]),
+    "gdsp_interval_percentiles_batch": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _vp, _int, _f64, _f64, _vp, _vp, _vp]),
+    "gdsp_interval_percentiles_set_batch": (_int, [_u32]),
+    "gdsp_interval_percentiles_last": (None, [_vp]),
     # segments (not in the reference)
     "gdsp_segments_tile": (_u32, []),
     "gdsp_run_pieces_batch": (_int, [_vp, _int, _f64, _int, _vp, _vp, _vp]),

@@ -122,6 +122,7 @@ int   percentile_with_binarize (dspop* percentile, dspop* next);
 
 /* ops_percentile.c: a percentile as given on the command line -> thousandths of a percent (0 .. 100000) */
 u32   to_thousandths      (valtype pct);
+void  percentile_name     (char* varName, u32 percentile);   /* "percentile99", "percentile99.5": the variable of that P (ops_percentile.c) */
 /* what the driver knows about an operator, said once, beside the operator, and found by its apply function (traits_of).
  * An operator nobody described (a plugin's) gets the defaults: it may ask for a partner, needs its chromosome in one piece,
  * has no one-launch form, and as a stop operator takes whole chromosomes and is credited the genome's bases at 16 B each */

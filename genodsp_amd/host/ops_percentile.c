@@ -138,9 +138,7 @@ void op_percentile_free (dspop* _op)
 	free (op);
 	}
 
-static void percentile_name (char* varName, u32 percentile);
-
-static void percentile_name (char* varName, u32 percentile)     /* percentile.c:756-780 */
+void percentile_name (char* varName, u32 percentile)            /* percentile.c:756-780 */
 	{
 	if (percentile % percentileStepUnits == 0)
 		{ sprintf (varName, "percentile%d", percentile / percentileStepUnits);  return; }

@@ -858,6 +858,46 @@ int gdsp_interval_stats_combine (const gdsp_interval_piece* pieces, uint32_t npi
 void gdsp_interval_stats_last  (uint64_t out[4]);
 void gdsp_interval_stats_times (double ms[4]);
 
+/* ---- percentilesover / medianover (not in the reference): exact order statistics of every interval ----------------
+ * What statsover leaves out: the figures of an interval that take more than one reduction.  For a vector v of n doubles,
+ * an interval [s, e) with 0 <= s < e <= n, limits lo, hi and percentiles P_0 .. P_{q-1} in thousandths of a percent
+ * (0..100000, 1 <= q <= GDSP_INTERVAL_PERCENTILES_MAX):
+ *   the sample is statsover's: the bases i in [s, e) with !(v[i] < lo) && !(v[i] > hi) and v[i] finite;
+ *   count    m, the number of sampled bases;
+ *   value_j  for each P_j, with k_j = gdsp_percentile_rank(m, P_j): gdsp_key_to_double of the k_j-th smallest (from 0)
+ *            of the keys gdsp_double_to_key(v[i]) over the sample -- the order `percentile` and `slidingpercentile`
+ *            use.  The value is an input value bit for bit, -0.0 folded onto +0.0.  For even m, P = 50000 is the upper
+ *            median, as in `median` and `localmad`;
+ *   m == 0:  every value_j is NaN.
+ * Duplicate P_j are allowed and answered in the order given.  Intervals may overlap, repeat and come in any order.
+ * Every figure is a function of the interval's sample alone, chosen by integer comparisons: nothing depends on the
+ * route an interval takes, the grid, the dispatch order, the order of the intervals or how they are batched.
+ *
+ * The conventions are gdsp_interval_stats[_batch]'s: HOST arrays in (GDSP_EINVAL for start >= end or end > n, for np
+ * outside 1..16 and for a P above 100000; count == 0 is a no-op), HOST arrays out in the caller's order -- h_count[i],
+ * and h_values[i*np + j] for P_j --, vectors 8-byte aligned, the signal read on the current device and never written,
+ * and the call waits for the device.  Intervals of at most gdsp_interval_percentiles_short() bases are sorted in LDS
+ * after one read of the signal; longer ones are cut into pieces of gdsp_interval_percentiles_piece() bases and take a
+ * radix select over HBM for all their (interval, percentile) queries at once, a query ending as soon as every key it
+ * still considers is one value (gdsp_intervalpct.hip).  The histograms of that select are bounded workspace: a call
+ * with more long queries than fit runs them in batches of whole intervals, and gdsp_interval_percentiles_set_batch
+ * sets that number of queries (0: the default) so that a test can force many small batches. */
+#define GDSP_INTERVAL_PERCENTILES_MAX 16
+/* Host: the longest interval the one-read route takes, and the piece of the other; results never depend on them */
+uint32_t gdsp_interval_percentiles_short (void);
+uint32_t gdsp_interval_percentiles_piece (void);
+int gdsp_interval_percentiles       (const double* d_v, uint32_t n, const uint32_t* h_start, const uint32_t* h_end, uint32_t count,
+                                     const uint32_t* pThousandths, int np, double lo, double hi,
+                                     uint32_t* h_count, double* h_values, void* stream);
+int gdsp_interval_percentiles_batch (const gdsp_batch_item* items, int nitems, const uint32_t* h_vec, const uint32_t* h_start,
+                                     const uint32_t* h_end, uint32_t count, const uint32_t* pThousandths, int np,
+                                     double lo, double hi, uint32_t* h_count, double* h_values, void* stream);
+int  gdsp_interval_percentiles_set_batch (uint32_t longQueries);
+/* what the last gdsp_interval_percentiles[_batch] did: [0] intervals, [1] those of the short route, [2] of the long
+ * route, [3] histogram passes (per batch, those of the query that took most), [4] batches, [5] long queries that ended
+ * before the last digit */
+void gdsp_interval_percentiles_last (uint64_t out[6]);
+
 /* ---- segments (not in the reference): the signal's own thresholded regions, each with statsover's figures, exact ------
  * For a vector v of n doubles, a threshold T and tiesAbove:
  *   member   base i is a member iff v[i] > T, or v[i] >= T with ties above: binarize's test.  A NaN is never a member
