@@ -97,7 +97,7 @@ class State:
         return State(dict(self.sig), self.vars)             # (operators replace vectors, they never write into one)
 
     def vectors(self):
-        return [self.sig[c] for c in NAMES]
+        return list(self.sig.values())
 
     def whole(self):
         return np.concatenate(self.vectors())
@@ -105,17 +105,18 @@ class State:
 
 def each(f):
     def fn(st):
-        st.sig = {c: np.ascontiguousarray(f(st.sig[c]), np.float64) for c in NAMES}
+        st.sig = {c: np.ascontiguousarray(f(v), np.float64) for c, v in st.sig.items()}
     return fn
 
 
 def reference(name, args):
     """an operator of the reference's table, through tests/pipeline.py on the CPU oracle"""
     def fn(st):
-        r = Runner(OracleBackend(), GENOME, st.sig)
+        names = list(st.sig)
+        r = Runner(OracleBackend(), [(c, st.sig[c].size) for c in names], st.sig)
         r.globals = st.vars
         r.run(["=" + name] + [str(a) for a in args])
-        st.sig = {c: np.array(r.result(c), np.float64) for c in NAMES}
+        st.sig = {c: np.array(r.result(c), np.float64) for c in names}
     return fn
 
 
@@ -139,8 +140,8 @@ def counts_ok(st, W, track=None):
         return False
     big = max(float(np.abs(v).max()) for v in st.vectors())
     if track is not None:
-        big = max(big, max(float(np.abs(track[c]).max()) for c in NAMES))
-    n = max(n for _, n in GENOME)
+        big = max(big, max(float(np.abs(track[c]).max()) for c in st.sig))
+    n = max(v.size for v in st.vectors())
     return n * big < 2.0 ** 53 and float(W) * W * big * big < 2.0 ** 53 and n * big * big < 2.0 ** 62
 
 
@@ -419,7 +420,7 @@ def segment_options(rng, st, cx, var=None):
 
 
 def segment_variables(st, rows):
-    spans = [r[1] - r[0] for c in NAMES for r in rows[c]]
+    spans = [r[1] - r[0] for c in rows for r in rows[c]]
     st.vars.update(segments=float(len(spans)), covered=float(sum(spans)), longest=float(max(spans) if spans else 0))
 
 
@@ -439,8 +440,8 @@ def d_keepsegments(rng, st, cx, var=None):
         args.append("--zero=" + num(zero))
 
     def fn(st):
-        rows = {c: segments_ref.segments(st.sig[c], T, **kw) for c in NAMES}
-        st.sig = {c: keepsegments_ref.paint(st.sig[c], rows[c], mode, one, zero) for c in NAMES}
+        rows = {c: segments_ref.segments(v, T, **kw) for c, v in st.sig.items()}
+        st.sig = {c: keepsegments_ref.paint(v, rows[c], mode, one, zero) for c, v in st.sig.items()}
         segment_variables(st, rows)
     op = Op("keepsegments", args, fn)
     op.sets = ("segments", "covered", "longest")
@@ -466,7 +467,7 @@ def d_normalize(rng, st, cx):
         count, total, mean, var, sd = xsum_ref.genome(st.vectors())
         st.vars.update(count=count, sum=total, mean=mean, variance=var, stddev=sd)
         with np.errstate(all="ignore"):
-            st.sig = {c: (st.sig[c] / np.float64(mean)) if to == "mean" else ((st.sig[c] - np.float64(mean)) / np.float64(sd)) for c in NAMES}
+            st.sig = {c: (v / np.float64(mean)) if to == "mean" else ((v - np.float64(mean)) / np.float64(sd)) for c, v in st.sig.items()}
     if "sum" not in st.vars:                                             # (no stats in front of it yet)
         return None
     return Op("normalize", args, fn)
@@ -556,7 +557,7 @@ def d_localcorrelate(rng, st, cx):
     y = cx["track"]
 
     def fn(st):
-        st.sig = {c: np.ascontiguousarray(model_localcorrelate(st.sig[c], y[c], W, what)) for c in NAMES}
+        st.sig = {c: np.ascontiguousarray(model_localcorrelate(v, y[c], W, what)) for c, v in st.sig.items()}
     return Op("localcorrelate", args, fn)
 
 
@@ -606,7 +607,7 @@ def d_segments(rng, st, cx, var=None):
     args, T, kw = segment_options(rng, st, cx, var)
 
     def fn(st):
-        segment_variables(st, {c: segments_ref.segments(st.sig[c], T, **kw) for c in NAMES})
+        segment_variables(st, {c: segments_ref.segments(v, T, **kw) for c, v in st.sig.items()})
     return stop("segments", args + ["--quiet"], ("longest", "segments", "covered"), fn)
 
 
@@ -635,7 +636,7 @@ def d_correlate(rng, st, cx):
     y = cx["track"]
 
     def fn(st):
-        set_correlation_variables(st, correlate_ref.genome([(st.sig[c], y[c]) for c in NAMES]))
+        set_correlation_variables(st, correlate_ref.genome([(v, y[c]) for c, v in st.sig.items()]))
     return stop("correlate", [TRACK, "--quiet"], ("slope", "correlation", "stddev", "mean"), fn)
 
 
@@ -647,7 +648,7 @@ def d_lagcorr(name):
         y = cx["track"]
 
         def fn(st):
-            pairs = [(st.sig[c], y[c] if name == "crosscorrelate" else st.sig[c]) for c in NAMES]
+            pairs = [(v, y[c] if name == "crosscorrelate" else v) for c, v in st.sig.items()]
             fig, counts, cov, corr = lagcorr_ref.curve(pairs, lo, n - lo + 1)
             set_correlation_variables(st, fig)
             best = lagcorr_ref.best(list(range(lo, n + 1)), corr)
@@ -727,10 +728,10 @@ def depth(seed):
     return "\n".join(lines) + "\n"
 
 
-def signal_of(text, value_column=True):
+def signal_of(text, value_column=True, genome=GENOME):
     """what the driver ingests from interval text: overlapping intervals add up (numpy addition of dyadic values: exact in
     any order); a chromosome that is not in the genome is skipped"""
-    sig = {c: np.zeros(n) for c, n in GENOME}
+    sig = {c: np.zeros(n) for c, n in genome}
     for line in text.splitlines():
         f = line.split()
         if f and f[0] in sig:
@@ -758,8 +759,8 @@ def files_of(seed):
 # ---------------------------------------------------------------------------------------------- the chains ----
 
 class Chain:
-    def __init__(self, seed, stdin, files, ops):
-        self.seed, self.stdin, self.files, self.ops = seed, stdin, files, ops
+    def __init__(self, seed, stdin, files, ops, genome=GENOME):
+        self.seed, self.stdin, self.files, self.ops, self.genome = seed, stdin, files, ops, genome
 
     def args(self, upto=None):
         """the driver's arguments behind --chromosomes= for the first `upto` operators (default: all)"""
@@ -777,8 +778,7 @@ class Chain:
 
 def lines_of(sig):
     total = 0
-    for c in NAMES:
-        v = sig[c]
+    for v in sig.values():
         starts = np.concatenate(([True], v[1:] != v[:-1]))
         total += int(np.count_nonzero(starts & (v != 0)))
     return total
@@ -789,13 +789,12 @@ def acceptable(before, after, op):
     if op.stop:
         return all(np.isfinite(x) for x in (after.vars.get(k, 0.0) for k in op.sets))
     with np.errstate(all="ignore"):
-        for c in NAMES:
-            v = after.sig[c]
+        for v in after.sig.values():
             if not np.isfinite(v).all() or float(np.abs(v).max()) > LIMIT:
                 return False
-    if all(np.all(after.sig[c] == after.sig[c][0]) for c in NAMES):
+    if all(np.all(v == v[0]) for v in after.sig.values()):
         return False
-    if all(np.array_equal(after.sig[c], before.sig[c]) for c in NAMES):
+    if all(np.array_equal(after.sig[c], before.sig[c]) for c in after.sig):
         return False
     return lines_of(after.sig) >= LEAST_LINES
 
@@ -900,13 +899,20 @@ def draw_free(rng, st, cx, pending, wanted):
     return DRAW[name](rng, st, cx)
 
 
-def draw_chain(seed):
-    """the chain of a seed: a Chain with the interval text on stdin, the files it names, and its operators.  Deterministic."""
+def draw_chain(seed, genome=GENOME, inputs=None):
+    """the chain of a seed: a Chain with the interval text on stdin, the files it names, and its operators.  Deterministic.
+    genome: the (name, length) pairs of the chromosomes file; for another one than GENOME, inputs = (stdin, files) are that
+    genome's interval text and its TRACK, INTERVALS and ANCHORS files (depth and files_of are cut to GENOME's lengths).
+    The draws themselves do not look at the genome: every checker the model is made of is defined on a vector of any
+    length -- oracle.cpu's windowed loops clamp or zero-pad at both ends (tests/test_contig_cases.py holds smooth, the
+    extrema and the morphology to their documented meaning on vectors shorter than the half window), and the checkers of
+    the operators beyond the table define their truncation -- so no window is barred on a short contig."""
     rng = np.random.default_rng(SALT + seed)
-    stdin, files = depth(seed), files_of(seed)
-    cx = {"track": signal_of(files[TRACK]), "tag": "chain%d" % seed, "placed": 0, "pending": [],
+    assert inputs is not None or genome is GENOME
+    stdin, files = inputs if inputs is not None else (depth(seed), files_of(seed))
+    cx = {"track": signal_of(files[TRACK], genome=genome), "tag": "chain%d" % seed, "placed": 0, "pending": [],
           "force": [CASES[seed % len(CASES)], CASES[(seed + len(CASES) // 2) % len(CASES)]]}
-    st = State(signal_of(stdin))
+    st = State(signal_of(stdin, genome=genome))
     wanted = []
     own = [(EVERY[(seed + j) % len(EVERY)], None, None) for j in (0, 14, 28)]             # and every operator is three seeds' own
     cx["force"] = [own[0], own[1], cx["force"][0], own[2], cx["force"][1]]
@@ -957,13 +963,13 @@ def draw_chain(seed):
                 pending = []
         if k == len(plan) and k < 16 and (len(ops) < 3 or (wanted and cx["placed"] < 3) or cx["force"]):
             plan.append(None)                                          # at least three operators, three of them the seed's own
-    return Chain(seed, stdin, files, ops)
+    return Chain(seed, stdin, files, ops, genome)
 
 
 def run_model(chain, without=None):
     """the model's signal behind every operator: a list of len(ops) + 1 dicts {chromosome: vector}, the ingested signal
     first (the prefixes are kept).  without: the index of an operator to leave out"""
-    st = State(signal_of(chain.stdin))
+    st = State(signal_of(chain.stdin, genome=chain.genome))
     out = [st.sig]
     for k, op in enumerate(chain.ops):
         if k != without:
@@ -976,8 +982,8 @@ def run_model(chain, without=None):
 def report(sig, precision=17):
     """a signal as the driver reports it: one line per run of equal values that are not zero, zero-based half-open"""
     lines = []
-    for c, n in GENOME:
-        v = sig[c]
+    for c, v in sig.items():
+        n = v.size
         cuts = np.concatenate(([0], np.flatnonzero(v[1:] != v[:-1]) + 1, [n]))
         for s, e in zip(cuts[:-1].tolist(), cuts[1:].tolist()):
             if v[s] != 0:

@@ -4,6 +4,7 @@ neighbourhood the driver's bookkeeping is sensitive to is drawn at least three t
 prefix of any chain holds a non-finite value, and few chains are vacuous -- a short report, or a last rewriting operator
 that could be left out without the report noticing."""
 import collections
+import hashlib
 import time
 
 import numpy as np
@@ -38,6 +39,21 @@ def test_the_same_seed_gives_the_same_chain_and_files(chains):
         assert again.args() == chain.args() and again.stdin == chain.stdin and again.files == chain.files
         assert cm.report(cm.run_model(again)[-1]) == cm.report(chains[seed][1][-1])
     assert len({repr(c) for c, _, _ in chains.values()}) == len(chains)             # (and another seed another chain)
+
+
+def test_the_default_genome_draws_what_it_drew_before_the_genome_was_a_parameter(chains):
+    """one sha256 over repr(chain), chain.stdin and the files of every seed of SEEDS, taken while GENOME was still a module
+    constant read by every operator's model: draw_chain(seed) with the default genome draws exactly that"""
+    h = hashlib.sha256()
+    for seed in cm.SEEDS:
+        chain = chains[seed][0]
+        assert chain.genome is cm.GENOME
+        h.update(repr(chain).encode())
+        h.update(chain.stdin.encode())
+        for name in sorted(chain.files):
+            h.update(name.encode())
+            h.update(chain.files[name].encode())
+    assert h.hexdigest() == "82e3815e2fead5406291a5d63ec6faa8fbb17d2b09cee346c260bd59d2c0c1f5"
 
 
 def test_chains_are_three_to_eight_operators_with_their_files(chains):
