@@ -1114,6 +1114,111 @@ def genome_matrix_last():
     return dict(zip(("rows", "cells", "host cells", "launches"), [int(x) for x in out]))
 
 
+# ------------------------------------------------------ regionsover (not in the reference) ----
+
+REGIONS_MAX_COLUMNS = 16384
+
+
+class RegionSource(C.Structure):
+    """gdsp_region_source of include/genodsp_hip.h"""
+    _fields_ = [("d_v", C.c_void_p), ("n", C.c_uint32), ("device", C.c_int), ("stream", C.c_void_p),
+                ("h_start", C.c_void_p), ("h_end", C.c_void_p), ("h_minus", C.c_void_p), ("nregions", C.c_uint32)]
+
+
+def _regions_array(regions, nvecs):
+    """regions: rows (vector index, start, end, strand +1 / -1), zero-based half-open -> int64[count, 4]"""
+    a = np.asarray(regions, dtype=np.int64).reshape(-1, 4)
+    assert np.all((a[:, 0] >= 0) & (a[:, 0] <= 0x7FFFFFFF)) and np.all((a[:, 1:3] >= 0) & (a[:, 1:3] <= 0xFFFFFFFF))
+    assert np.all(np.abs(a[:, 3]) == 1)
+    return a
+
+
+def _regions_columns(body, upstream, downstream, bin):
+    ok = bin >= 1 and body >= 1 and upstream >= 0 and downstream >= 0 and upstream % bin == 0 and downstream % bin == 0
+    return upstream // bin + body + downstream // bin if ok else 0
+
+
+def region_cell_bounds(n, start, end, strand, body, upstream=0, downstream=0, bin=1, column=0):
+    """Host, no GPU: (lo, hi), the bases [lo, hi) of one column of the row of region [start, end) on a chromosome of n
+    bases, cut to [0, n) (lo >= hi: an empty cell) -- gdsp_region_cell_bounds, the function the kernel itself uses."""
+    lo, hi = C.c_int64(), C.c_int64()
+    call("gdsp_region_cell_bounds", int(n), int(start), int(end), 1 if strand < 0 else 0, int(body), int(upstream),
+         int(downstream), int(bin), int(column), C.byref(lo), C.byref(hi))
+    return lo.value, hi.value
+
+
+def regions_set_launch_rows(rows):
+    """Rows per launch of genome_regions (0: the library's own number).  For tests that force several launches."""
+    call("gdsp_regions_set_launch_rows", int(rows))
+
+
+def regions_rows(vecs, regions, body, upstream=0, downstream=0, bin=1, what="mean", lo=-DBL_MAX, hi=DBL_MAX, stream=None):
+    """One gdsp_region_rows_batch: (rows, todo).  rows is np.float64[len(regions), ncols] as the device left it, todo the
+    np.uint32 indices row * ncols + column of the cells it could not finish exactly (in no particular order), whose
+    entries of rows mean nothing.  vecs: as xsum_sources, whole chromosomes; regions: rows (vector index, start, end,
+    strand +1 / -1)."""
+    body, upstream, downstream, bin = int(body), int(upstream), int(downstream), int(bin)
+    _, items = _anchor_items(vecs, stream)
+    a = _regions_array(regions, len(vecs))
+    na = len(a)
+    reg = DeviceBuffer(max(1, 3 * na) * 4)                              # the starts, the ends, the code words
+    if na:
+        reg.upload(np.concatenate([a[:, 1].astype(np.uint32), a[:, 2].astype(np.uint32),
+                                   (a[:, 0] * 2 + (a[:, 3] < 0)).astype(np.uint32)]), stream=stream)
+    ncols = _regions_columns(body, upstream, downstream, bin)
+    cells = na * ncols
+    out = DeviceBuffer(max(1, cells) * 8)
+    todo = DeviceBuffer((max(1, cells) + 1) * 4)                        # the counter, then the list
+    todo.upload(np.zeros(1, np.uint32), stream=stream)
+    call("gdsp_region_rows_batch", items, len(vecs), C.c_void_p(reg.ptr), C.c_void_p(reg.ptr + 4 * na),
+         C.c_void_p(reg.ptr + 8 * na), na, body, upstream, downstream, bin, _matrix_figure(what), float(lo), float(hi),
+         C.c_void_p(out.ptr), C.c_void_p(todo.ptr + 4), C.c_void_p(todo.ptr), _sp(stream))
+    ntodo = int(todo.download(np.uint32, 1, stream=stream)[0])
+    assert ntodo <= cells
+    rows = out.download(np.float64, cells, stream=stream).reshape(na, ncols) if cells else np.zeros((na, ncols))
+    left = todo.download(np.uint32, 1 + ntodo, stream=stream)[1:].copy()
+    return rows, left
+
+
+def genome_regions(vecs, regions, body, upstream=0, downstream=0, bin=1, what="mean", lo=-DBL_MAX, hi=DBL_MAX, stream=None):
+    """Every region scaled to the same columns (gdsp_genome_regions): np.float64[len(regions), upstream // bin + body +
+    downstream // bin], row i the figure `what` ("mean", "sum", "count", "min" or "max") of region i over its upstream
+    flank in columns of `bin` bases, its own bases in `body` columns, and its downstream flank, in the region's own
+    direction; every value exact and rounded once, NaN where a mean, min or max has nothing to look at.  vecs: as
+    xsum_sources, whole chromosomes; regions: rows (vector index, start, end, strand +1 / -1), zero-based half-open, and
+    the rows come back in their order."""
+    body, upstream, downstream, bin = int(body), int(upstream), int(downstream), int(bin)
+    a = _regions_array(regions, len(vecs))
+    ncols = _regions_columns(body, upstream, downstream, bin)
+    src = xsum_sources(vecs, stream)
+    tab = (RegionSource * max(1, len(vecs)))()
+    keep = []
+    for i in range(len(vecs)):
+        where = np.flatnonzero(a[:, 0] == i)
+        start = np.ascontiguousarray(a[where, 1], dtype=np.uint32)
+        end = np.ascontiguousarray(a[where, 2], dtype=np.uint32)
+        minus = np.ascontiguousarray(a[where, 3] < 0, dtype=np.uint32)
+        mine = np.zeros((max(1, where.size), max(1, ncols)), np.float64)
+        keep.append((where, start, end, minus, mine))
+        tab[i].d_v, tab[i].n, tab[i].device, tab[i].stream = src[i].d_v, src[i].n, src[i].device, stream
+        tab[i].h_start, tab[i].h_end, tab[i].h_minus, tab[i].nregions = start.ctypes.data, end.ctypes.data, minus.ctypes.data, where.size
+    if len(a) and not np.all(a[:, 0] < len(vecs)):
+        raise GdspError("genome_regions: a region names a vector the call does not have")
+    rows = (C.c_void_p * max(1, len(keep)))(*[k[4].ctypes.data for k in keep])
+    call("gdsp_genome_regions", tab, len(vecs), body, upstream, downstream, bin, _matrix_figure(what), float(lo), float(hi), rows)
+    out = np.zeros((a.shape[0], ncols), np.float64)
+    for where, _, _, _, mine in keep:
+        out[where] = mine[:where.size, :ncols]
+    return out
+
+
+def genome_regions_last():
+    """What the last genome_regions did: its rows, its cells, the cells the host finished, and the launches."""
+    out = (C.c_uint64 * 4)()
+    lib().gdsp_genome_regions_last(out)
+    return dict(zip(("rows", "cells", "host cells", "launches"), [int(x) for x in out]))
+
+
 # ------------------------------------------------------ histogram (not in the reference) ----
 
 HISTOGRAM_MAX_BINS = 65536

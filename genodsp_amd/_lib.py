@@ -204,6 +204,12 @@ SIGNATURES = {
     "gdsp_genome_matrix": (_int, [_vp, _int, C.c_int32, _u32, _u32, _int, _f64, _f64, _vp]),
     "gdsp_matrix_set_launch_rows": (_int, [_u32]),
     "gdsp_genome_matrix_last": (None, [_vp]),
+    # regionsover (not in the reference)
+    "gdsp_region_cell_bounds": (_int, [_u32, _u32, _u32, _int, _u32, _u32, _u32, _u32, _u32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gdsp_region_rows_batch": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _int, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "gdsp_genome_regions": (_int, [_vp, _int, _u32, _u32, _u32, _u32, _int, _f64, _f64, _vp]),
+    "gdsp_regions_set_launch_rows": (_int, [_u32]),
+    "gdsp_genome_regions_last": (None, [_vp]),
     # statsover (not in the reference)
     "gdsp_interval_stats_tile": (_u32, []),
     "gdsp_interval_stats": (_int, [_vp, _u32, _vp, _vp, _u32, _f64, _f64, _vp, _vp]),

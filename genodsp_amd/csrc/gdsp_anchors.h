@@ -3,6 +3,8 @@
 // fills it, the checks of the arguments both take, the check on the device that every anchor lies inside its vector, the
 // gather of a device's sources into items and anchors, and the holder of what a call allocates.  The kernels, the figures
 // and the two end-to-end drivers stay in their files; gdsp_anchors.hip has the check on the device, compiled once.
+// gdsp_regionsover.hip (regionsover) takes the code word, the launch table, the argument checks and the holder from here;
+// a region has a start and an end where an anchor has a position, so its check on the device and its gather are its own.
 #pragma once
 #include <algorithm>
 #include <utility>

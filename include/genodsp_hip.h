@@ -821,6 +821,47 @@ int gdsp_matrix_set_launch_rows (uint32_t rows);
 /* what the last gdsp_genome_matrix did: [0] rows, [1] cells, [2] cells the host finished, [3] launches */
 void gdsp_genome_matrix_last (uint64_t out[4]);
 
+/* ---- regionsover (not in the reference): every region of a list scaled to the same columns, one row per region, exact --
+ * The other half of matrixover (deepTools' computeMatrix scale-regions).  A region is (vector, [s, e), strand) with
+ * 0 <= s < e <= n of its WHOLE chromosome vector and L = e - s.  A row has U / b + B + D / b columns in the region's own
+ * direction: the upstream flank of U bases in columns of b, the body in B columns, the downstream flank of D bases in
+ * columns of b.  1 <= B <= GDSP_REGIONS_MAX_COLUMNS; U, D <= GDSP_REGIONS_MAX_COLUMNS; b >= 1 divides both; at most
+ * GDSP_REGIONS_MAX_COLUMNS columns.  In integers, on the plus strand:
+ *   body column k        the bases [s + floor (k L / B), s + floor ((k+1) L / B)): the B cells partition [s, e), each of
+ *                        floor (L / B) or ceil (L / B) bases, and with L < B some are empty;
+ *   upstream column j    [s - U + j b, s - U + (j+1) b);     downstream column j    [e + j b, e + (j+1) b);
+ *   a flank cell is cut to [0, n) (a region itself is never cut: one that leaves its vector is refused).
+ * The minus strand is the mirror image about the region: body column k is [e - floor ((k+1) L / B), e - floor (k L / B)),
+ * upstream lies above e and downstream below s.  A CELL is thus one interval of the chromosome, possibly empty, and its
+ * figures are matrixover's, that is statsover's for that interval under the limits lo, hi; one call computes one figure
+ * GDSP_MATRIX_*; an empty cell has count 0, sum +0.0 and mean, min, max NaN.  Each value is a function of its cell's
+ * sample alone: nothing depends on the launch split, grid, dispatch order, devices or the order of the regions.
+ *
+ * gdsp_region_cell_bounds is that definition on the host, without a device: [*lo, *hi) of one column, cut to [0, n)
+ * (*lo >= *hi: empty) -- the same function the kernel and the host half use.
+ * gdsp_region_rows_batch writes the rows of `count` regions that are on the device already -- d_start, d_end and d_code
+ * (vector * 2 + minus, as an anchor's) DEVICE arrays, items as gdsp_matrix_rows_batch takes them -- into d_out, count x
+ * ncols doubles, row-major; d_todo and d_ntodo as there.  GDSP_EINVAL for a bad shape or a region that is not
+ * s < e <= n of one of the items (decided on the device: the call waits for the stream once; no kernel follows).
+ * gdsp_genome_regions is the host half: a source is a whole chromosome on `device` with its regions as HOST arrays; per
+ * device it uploads them, launches bounded pieces (at most 2^25 cells each; gdsp_regions_set_launch_rows lowers the rows
+ * of a piece for tests, 0 restores), reads the rows back into h_rows[i] (sources[i].nregions x ncols doubles) and
+ * computes the to-do cells with gdsp_interval_stats_batch. */
+#define GDSP_REGIONS_MAX_COLUMNS 16384
+typedef struct gdsp_region_source { const double* d_v; uint32_t n; int device; void* stream;
+                                    const uint32_t* h_start; const uint32_t* h_end; const uint32_t* h_minus;
+                                    uint32_t nregions; } gdsp_region_source;
+int gdsp_region_cell_bounds (uint32_t n, uint32_t start, uint32_t end, int minus, uint32_t B, uint32_t U, uint32_t D, uint32_t b,
+                             uint32_t column, int64_t* lo, int64_t* hi);
+int gdsp_region_rows_batch (const gdsp_batch_item* items, int nitems, const uint32_t* d_start, const uint32_t* d_end,
+                            const uint32_t* d_code, uint32_t count, uint32_t B, uint32_t U, uint32_t D, uint32_t b, int what,
+                            double lo, double hi, double* d_out, uint32_t* d_todo, uint32_t* d_ntodo, void* stream);
+int gdsp_genome_regions (const gdsp_region_source* sources, int nsources, uint32_t B, uint32_t U, uint32_t D, uint32_t b, int what,
+                         double lo, double hi, double* const* h_rows);
+int gdsp_regions_set_launch_rows (uint32_t rows);
+/* what the last gdsp_genome_regions did: [0] rows, [1] cells, [2] cells the host finished, [3] launches */
+void gdsp_genome_regions_last (uint64_t out[4]);
+
 /* ---- statsover (not in the reference): one signal quantified over many intervals, exact ---------------------------
  * For a vector v of n doubles, an interval [s, e) with 0 <= s < e <= n, and limits lo, hi:
  *   the sample of the interval is stats' sample restricted to it: the bases i in [s, e) with !(v[i] < lo) &&
