@@ -1,10 +1,11 @@
 // gdsp_anchors.h -- the anchor half the anchor operators share (gdsp_profileover.hip: profileover; gdsp_matrixover.hip:
-// matrixover): how an anchor is encoded for the device, the table of read-only vectors a launch takes and the walk that
-// fills it, the checks of the arguments both take, the check on the device that every anchor lies inside its vector, the
-// gather of a device's sources into items and anchors, and the holder of what a call allocates.  The kernels, the figures
-// and the two end-to-end drivers stay in their files; gdsp_anchors.hip has the check on the device, compiled once.
-// gdsp_regionsover.hip (regionsover) takes the code word, the launch table, the argument checks and the holder from here;
-// a region has a start and an end where an anchor has a position, so its check on the device and its gather are its own.
+// matrixover; gdsp_regionsover.hip: regionsover): how an anchor is encoded for the device, the table of read-only vectors a
+// launch takes and the walk that fills it, the checks of the arguments they take, the check on the device that every
+// anchor lies inside its vector, the gather of a device's sources into items and anchors, the walk over the devices of an
+// end-to-end call, and the holder of what a call allocates.  The kernels and the figures stay in their files;
+// gdsp_anchors.hip has the checks on the device, compiled once.  A region has a start and an end where an anchor has a
+// position: its check on the device is the anchors' host sequence around another kernel, and its gather stays with
+// regionsover.  What matrixover and regionsover share beyond this -- the rows of a device -- is gdsp_matrix_rows.h's.
 #pragma once
 #include <algorithm>
 #include <utility>
@@ -84,6 +85,9 @@ static inline int gdsp_anchor_check_sources (const gdsp_profile_source* sources,
 // the same of `count` anchors that are on the device already, decided there: each names one of the items and a position in it
 int gdsp_anchor_check (const gdsp_batch_item* items, int nitems, const uint32_t* d_pos, const uint32_t* d_code, uint32_t count,
                        hipStream_t s, const char* who);
+// and of `count` regions: each names one of the items and is start < end <= the item's length
+int gdsp_region_check (const gdsp_batch_item* items, int nitems, const uint32_t* d_start, const uint32_t* d_end, const uint32_t* d_code,
+                       uint32_t count, hipStream_t s, const char* who);
 
 // ---- the gather: the sources mine[0 .. nmine) (indices into `sources`) as the items of one device's calls.  Item k is
 // source mine[k]; pos / code get the sources' anchors, one source after the other in that order, source mine[k]'s being
@@ -105,6 +109,31 @@ static inline void gdsp_anchor_gather (const gdsp_profile_source* sources, const
 			}
 		if (first != NULL) first[k+1] = first[k] + S.nanchors;
 		}
+	}
+
+// ---- the devices of an end-to-end call, each once in ascending order: on_device (mine, nmine) -> GDSP_OK or an error, with
+// that device current and mine[0 .. nmine) its sources (indices into `sources`, the caller's order).  The caller's device
+// is current again afterwards.  who: the entry point, as the message names it ----
+template <typename Source, typename OnDevice>
+static inline int gdsp_anchor_per_device (const Source* sources, int nsources, const char* who, OnDevice on_device)
+	{
+	int rc = GDSP_OK, home = 0;
+	GDSP_HIP_TRY (hipGetDevice (&home));
+	std::vector<int> devices;
+	for (int i=0 ; i<nsources ; i++) devices.push_back (sources[i].device);
+	std::sort (devices.begin (), devices.end ());
+	devices.erase (std::unique (devices.begin (), devices.end ()), devices.end ());
+	std::vector<int> mine;
+	for (size_t d=0 ; (d<devices.size ()) && (rc == GDSP_OK) ; d++)
+		{
+		mine.clear ();
+		for (int i=0 ; i<nsources ; i++) { if (sources[i].device == devices[d]) mine.push_back (i); }
+		if (hipSetDevice (devices[d]) != hipSuccess)
+			{ gdsp_set_error ("%s: device %d cannot be selected", who, devices[d]);  rc = GDSP_EHIP;  break; }
+		rc = on_device (mine.data (), (int) mine.size ());
+		}
+	(void) hipSetDevice (home);
+	return rc;
 	}
 
 // ---- what a call allocates on its devices: freed when the call returns, whichever way, each on the device it came from ----

@@ -1,7 +1,8 @@
 // gdsp_matrix_cell.h -- the cell of the matrix operators (gdsp_matrixover.hip: matrixover, cells of one bin width around
 // anchors; gdsp_regionsover.hip: regionsover, cells whose width changes with the row): what a lane knows of its sample,
 // how lanes fold their shares, and how a cell's figure is finished exactly and rounded once -- or handed to the host, by
-// its index on the launch's to-do list.  The routes that feed a cell stay with the kernels.
+// its index on the launch's to-do list.  The routes that feed a cell stay with the kernels; what the host does with the
+// rows and the list is gdsp_matrix_rows.h's.
 #pragma once
 #include <math.h>
 #include "gdsp_common.h"
@@ -137,17 +138,4 @@ __device__ __forceinline__ void mx_later_wave (uint32_t* __restrict__ todo, uint
 	if (lane == leader) base = atomicAdd (ntodo, (uint32_t) __popcll (mask));
 	base = __shfl (base, (int) leader, 64);
 	if (later) todo[base + (uint32_t) __popcll (mask & ((1ull << lane) - 1))] = cell;
-	}
-
-// host: the figure of a cell the exact interval call computed
-static inline double mx_figure_of (const gdsp_interval_stat& st, int what)
-	{
-	switch (what)
-		{
-		case GDSP_MATRIX_MEAN:  return st.mean;
-		case GDSP_MATRIX_SUM:   return st.sum;
-		case GDSP_MATRIX_COUNT: return (double) st.count;
-		case GDSP_MATRIX_MIN:   return st.min;
-		default:                return st.max;
-		}
 	}

@@ -25,7 +25,9 @@
 // wave and stretch, and computed by the host half through gdsp_interval_stats_batch.  One double is written per cell, by one lane; no
 // atomics on cells, no wave or workgroup waits for another (the LDS piece is a wave's own), no scratch.
 // What concerns the anchors rather than the figures -- their code word, the table of vectors a launch takes, the checks, the
-// gather of a device's sources, the holder of its allocations -- is gdsp_anchors.h's, shared with profileover.
+// gather of a device's sources, the walk over the devices, the holder of its allocations -- is gdsp_anchors.h's, shared with
+// profileover; the host half of a device's rows -- launches, copies back, the to-do list -- is gdsp_matrix_rows.h's, shared
+// with regionsover.
 
 #include <float.h>
 #include <math.h>
@@ -36,6 +38,7 @@
 #include "gdsp_anchors.h"
 #include "gdsp_xsum_dev.h"
 #include "gdsp_matrix_cell.h"
+#include "gdsp_matrix_rows.h"
 
 enum { MX_ROUTE_COPY = 0, MX_ROUTE_NARROW = 1, MX_ROUTE_WIDE = 2 };
 
@@ -235,14 +238,8 @@ static int mx_launch (const gdsp_batch_item* items, int nitems, const uint32_t* 
 	const dim3 grid (std::min<uint32_t> ((count + MX_WAVES - 1) / MX_WAVES, MX_WG_TARGET));
 	return gdsp_anchor_tables (items, nitems, [&] (const GdspAnchorTable& B) -> int
 		{
-		switch (what)
-			{
-			case GDSP_MATRIX_MEAN:  mx_launch_route<GDSP_MATRIX_MEAN>  (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
-			case GDSP_MATRIX_SUM:   mx_launch_route<GDSP_MATRIX_SUM>   (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
-			case GDSP_MATRIX_COUNT: mx_launch_route<GDSP_MATRIX_COUNT> (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
-			case GDSP_MATRIX_MIN:   mx_launch_route<GDSP_MATRIX_MIN>   (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
-			default:                mx_launch_route<GDSP_MATRIX_MAX>   (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo);  break;
-			}
+		mx_with_figure (what, [&] (auto W)
+			{ mx_launch_route<decltype (W)::value> (B, grid, s, d_pos, d_code, count, offLo, noffsets, bin, lo, hi, d_out, d_todo, d_ntodo); });
 		GDSP_LAUNCH_CHECK ();
 		if (launches != NULL) (*launches)++;
 		return GDSP_OK;
@@ -286,86 +283,24 @@ namespace {
 int mx_on_device (const gdsp_profile_source* sources, const int* mine, int nmine, int32_t offLo, uint32_t noffsets, uint32_t bin,
                   int what, double lo, double hi, double* const* h_rows)
 	{
-	const uint32_t ncols = noffsets / bin;
 	std::vector<gdsp_batch_item> items;
 	std::vector<uint64_t> first (nmine + 1, 0);                   // the device's rows: source k owns first[k] .. first[k+1]
-	std::vector<uint32_t> pos, code;
-	gdsp_anchor_gather (sources, mine, nmine, items, pos, code, first.data ());
-	const uint64_t na = first[nmine];
-	if (na == 0) return GDSP_OK;
-	GDSP_REQUIRE (na <= UINT32_MAX, "more than 2^32 - 1 anchors on a device");
-	hipStream_t s = gdsp_stream (sources[mine[0]].stream);
-
-	uint64_t perLaunch = std::max<uint64_t> (1, MX_LAUNCH_CELLS / ncols);
-	if (mxLaunchRows != 0) perLaunch = std::min<uint64_t> (perLaunch, mxLaunchRows);
-	perLaunch = std::min (perLaunch, na);
-	const size_t cells = (size_t) perLaunch * ncols;
-
-	GdspAnchorHeld held;
-	const char* const who = "gdsp_genome_matrix";
-	uint32_t *d_anchors = NULL, *d_todo = NULL;
-	double*   d_out = NULL;
-	int rc = held.alloc ((void**) &d_anchors, 2 * na * sizeof(uint32_t), who, "anchors");
-	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_out, cells * sizeof(double), who, "rows");
-	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_todo, (cells + 1) * sizeof(uint32_t), who, "to-do list");     // the counter, then the list
-	if (rc != GDSP_OK) return rc;
-	GDSP_HIP_TRY (hipMemcpyAsync (d_anchors,      pos.data (),  na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (d_anchors + na, code.data (), na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-
-	std::vector<uint32_t> todo, tVec, tStart, tEnd;
-	std::vector<double*>  tWhere;
-	std::vector<gdsp_interval_stat> tStat;
-	for (uint64_t r0=0 ; r0<na ; r0+=perLaunch)
-		{
-		const uint32_t nr = (uint32_t) std::min<uint64_t> (perLaunch, na - r0);
-		uint32_t ntodo = 0;
-		GDSP_HIP_TRY (hipMemsetAsync (d_todo, 0, sizeof(uint32_t), s));
-		rc = mx_launch (items.data (), nmine, d_anchors + r0, d_anchors + na + r0, nr, offLo, noffsets, bin, what, lo, hi,
-		                d_out, d_todo + 1, d_todo, s, &mxLast[3]);
-		if (rc != GDSP_OK) return rc;
-		GDSP_HIP_TRY (hipMemcpyAsync (&ntodo, d_todo, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-		// the rows, to the sources that own them
-		int k = (int) (std::upper_bound (first.begin (), first.end (), r0) - first.begin ()) - 1;
-		for (uint64_t a=r0 ; a<r0+nr ; )
+	std::vector<uint32_t> cols[2];                                // the positions, the code words
+	const std::vector<uint32_t> &pos = cols[0], &code = cols[1];
+	gdsp_anchor_gather (sources, mine, nmine, items, cols[0], cols[1], first.data ());
+	if (first[nmine] == 0) return GDSP_OK;
+	GDSP_REQUIRE (first[nmine] <= UINT32_MAX, "more than 2^32 - 1 anchors on a device");
+	return mx_rows_on_device (items, first, mine, cols, noffsets / bin, what, lo, hi, h_rows, mxLaunchRows, mxLast,
+	                          sources[mine[0]].stream, "gdsp_genome_matrix", "anchors",
+		[&] (const uint32_t* d_rows, uint64_t na, uint32_t nr, double* d_out, uint32_t* d_todo, uint32_t* d_ntodo, hipStream_t s, uint64_t* launches) -> int
+			{ return mx_launch (items.data (), nmine, d_rows, d_rows + na, nr, offLo, noffsets, bin, what, lo, hi, d_out, d_todo, d_ntodo, s, launches); },
+		[&] (uint64_t a, uint32_t j, int64_t n, int64_t* gLo, int64_t* gHi)
 			{
-			while (first[k+1] <= a) k++;
-			const uint64_t b = std::min<uint64_t> (first[k+1], r0 + nr);
-			GDSP_HIP_TRY (hipMemcpyAsync (h_rows[mine[k]] + (size_t) (a - first[k]) * ncols, d_out + (size_t) (a - r0) * ncols,
-			                              (size_t) (b - a) * ncols * sizeof(double), hipMemcpyDeviceToHost, s));
-			a = b;
-			}
-		GDSP_HIP_TRY (hipStreamSynchronize (s));
-		if (ntodo == 0) continue;
-
-		// the cells the device left: each is one interval of its chromosome, computed by the exact interval call
-		GDSP_REQUIRE (ntodo <= (uint64_t) nr * ncols, "the to-do list is longer than the launch");
-		todo.resize (ntodo);
-		GDSP_HIP_TRY (hipMemcpyAsync (todo.data (), d_todo + 1, (size_t) ntodo * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-		GDSP_HIP_TRY (hipStreamSynchronize (s));
-		tVec.clear ();  tStart.clear ();  tEnd.clear ();  tWhere.clear ();
-		for (uint32_t t=0 ; t<ntodo ; t++)
-			{
-			const uint64_t a = r0 + todo[t] / ncols;
-			const uint32_t j = todo[t] % ncols;
-			const int kk = (int) (std::upper_bound (first.begin (), first.end (), a) - first.begin ()) - 1;
-			const int64_t n = items[kk].n, p = pos[a];
-			const int64_t kLo = (int64_t) offLo + (int64_t) j * bin, kHi = kLo + bin - 1;
-			int64_t gLo = gdsp_anchor_minus (code[a])? p - kHi : p + kLo;
-			int64_t gHi = gdsp_anchor_minus (code[a])? p - kLo : p + kHi;
-			gLo = std::max<int64_t> (gLo, 0);  gHi = std::min<int64_t> (gHi, n - 1);
-			double* where = h_rows[mine[kk]] + (size_t) (a - first[kk]) * ncols + j;
-			if (gLo > gHi) { *where = ((what == GDSP_MATRIX_COUNT) || (what == GDSP_MATRIX_SUM))? 0.0 : NAN;  continue; }
-			tVec.push_back ((uint32_t) kk);  tStart.push_back ((uint32_t) gLo);  tEnd.push_back ((uint32_t) (gHi + 1));
-			tWhere.push_back (where);
-			}
-		tStat.resize (tWhere.size ());
-		rc = gdsp_interval_stats_batch (items.data (), nmine, tVec.data (), tStart.data (), tEnd.data (), (uint32_t) tWhere.size (),
-		                                lo, hi, tStat.data (), (void*) s);
-		if (rc != GDSP_OK) return rc;
-		for (size_t t=0 ; t<tWhere.size () ; t++) *tWhere[t] = mx_figure_of (tStat[t], what);
-		mxLast[2] += ntodo;
-		}
-	return GDSP_OK;
+			// the offsets kLo .. kHi of column j, from the anchor in its own direction, cut to the chromosome
+			const int64_t p = pos[a], kLo = (int64_t) offLo + (int64_t) j * bin, kHi = kLo + bin - 1;
+			*gLo = std::max<int64_t> (gdsp_anchor_minus (code[a])? p - kHi : p + kLo, 0);
+			*gHi = std::min<int64_t> (gdsp_anchor_minus (code[a])? p - kLo : p + kHi, n - 1) + 1;
+			});
 	}
 
 } // namespace
@@ -389,24 +324,8 @@ int gdsp_genome_matrix (const gdsp_profile_source* sources, int nsources, int32_
 		}, &mxLast[0]);
 	if (rc != GDSP_OK) return rc;
 	mxLast[1] = mxLast[0] * ncols;
-
-	int home = 0;
-	GDSP_HIP_TRY (hipGetDevice (&home));
-	std::vector<int> devices;
-	for (int i=0 ; i<nsources ; i++) devices.push_back (sources[i].device);
-	std::sort (devices.begin (), devices.end ());
-	devices.erase (std::unique (devices.begin (), devices.end ()), devices.end ());
-	std::vector<int> mine;
-	for (size_t d=0 ; (d<devices.size ()) && (rc == GDSP_OK) ; d++)
-		{
-		mine.clear ();
-		for (int i=0 ; i<nsources ; i++) { if (sources[i].device == devices[d]) mine.push_back (i); }
-		if (hipSetDevice (devices[d]) != hipSuccess)
-			{ gdsp_set_error ("gdsp_genome_matrix: device %d cannot be selected", devices[d]);  rc = GDSP_EHIP;  break; }
-		rc = mx_on_device (sources, mine.data (), (int) mine.size (), offLo, noffsets, bin, what, lo, hi, h_rows);
-		}
-	(void) hipSetDevice (home);
-	return rc;
+	return gdsp_anchor_per_device (sources, nsources, __func__, [&] (const int* mine, int nmine) -> int
+		{ return mx_on_device (sources, mine, nmine, offLo, noffsets, bin, what, lo, hi, h_rows); });
 	}
 
 } // extern "C"

@@ -17,8 +17,10 @@
 //              else 16) owns a cell, whose [lo, hi) inside the stretch each group reads from rg_bound.
 //   otherwise  the wave strides over the cell and folds its 64 lanes with the shuffle tree.
 // The cell -- MxAcc, mx_take, mx_fold, mx_finish with its proof, the to-do list -- is gdsp_matrix_cell.h's, shared with
-// matrixover, as are the sizes of a stretch.  One double is written per cell, by one lane; no atomics on cells; one atomic
-// per wave and stretch for the to-do list; no wave or workgroup waits for another (the LDS piece is a wave's own); no scratch.
+// matrixover, as are the sizes of a stretch; the host half of a device's rows is gdsp_matrix_rows.h's and the check on the
+// device that every region lies inside its vector gdsp_anchors.hip's.  One double is written per cell, by one lane; no
+// atomics on cells; one atomic per wave and stretch for the to-do list; no wave or workgroup waits for another (the LDS
+// piece is a wave's own); no scratch.
 
 #include <float.h>
 #include <math.h>
@@ -29,6 +31,7 @@
 #include "gdsp_anchors.h"
 #include "gdsp_xsum_dev.h"
 #include "gdsp_matrix_cell.h"
+#include "gdsp_matrix_rows.h"
 
 // ---------------------------------------------------------------------------------- the geometry of a row ----
 struct RgShape { uint32_t B, b, nUp, nDown, ncols; };       // body columns, bases of a flank column, flank columns
@@ -275,21 +278,6 @@ void regions_kernel (GdspAnchorTable P, const uint32_t* __restrict__ d_start, co
 		}
 	}
 
-// *d_bad = 1 when some region names a vector the call does not have or is not s < e <= n of its vector: all that stands
-// between a bad position and a kernel that reads outside its vector
-__global__ void region_check_kernel (const uint32_t* __restrict__ d_start, const uint32_t* __restrict__ d_end,
-                                     const uint32_t* __restrict__ d_code, uint32_t count, const uint32_t* __restrict__ d_n,
-                                     uint32_t nvec, uint32_t* __restrict__ d_bad)
-	{
-	bool bad = false;
-	for (uint32_t i=blockIdx.x*blockDim.x+threadIdx.x ; i<count ; i+=gridDim.x*blockDim.x)
-		{
-		const uint32_t vec = gdsp_anchor_vec (d_code[i]);
-		bad |= (vec >= nvec) || (d_start[i] >= d_end[i]) || (d_end[i] > d_n[(vec < nvec)? vec : 0]);
-		}
-	if (bad) atomicOr (d_bad, 1u);
-	}
-
 // ---------------------------------------------------------------------------------------------- host ----
 static uint32_t rgLaunchRows = 0;                            // see gdsp_regions_set_launch_rows
 static uint64_t rgLast[4];                                   // see gdsp_genome_regions_last
@@ -304,32 +292,6 @@ static int rg_check_shape (uint32_t B, uint32_t U, uint32_t D, uint32_t b, int w
 	return GDSP_OK;
 	}
 
-static int rg_check_on_device (const gdsp_batch_item* items, int nitems, const uint32_t* d_start, const uint32_t* d_end,
-                               const uint32_t* d_code, uint32_t count, hipStream_t s, const char* who)
-	{
-	std::vector<uint32_t> h_n (nitems);
-	for (int i=0 ; i<nitems ; i++) h_n[i] = items[i].n;
-	uint32_t* d_work = NULL;                                    // the flag, then the lengths
-	if (hipMalloc ((void**) &d_work, (size_t) (nitems + 1) * sizeof(uint32_t)) != hipSuccess)
-		{ gdsp_set_error ("%s: no device memory for the region check", who);  return GDSP_ENOMEM; }
-	uint32_t bad = 0;
-	hipError_t e = hipMemsetAsync (d_work, 0, sizeof(uint32_t), s);
-	if (e == hipSuccess) e = hipMemcpyAsync (d_work + 1, h_n.data (), (size_t) nitems * sizeof(uint32_t), hipMemcpyHostToDevice, s);
-	if (e == hipSuccess) e = hipStreamSynchronize (s);           // (h_n is pageable: the copy has left it)
-	if (e == hipSuccess)
-		{
-		uint32_t g = (count + 255) / 256;
-		if (g > 1024) g = 1024;                                  // (a thread strides over the regions beyond 1024 x 256)
-		hipLaunchKernelGGL (region_check_kernel, dim3 (g), dim3 (256), 0, s, d_start, d_end, d_code, count, d_work + 1, (uint32_t) nitems, d_work);
-		e = hipGetLastError ();
-		}
-	if (e == hipSuccess) e = hipMemcpyAsync (&bad, d_work, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess) e = hipStreamSynchronize (s);
-	(void) hipFree (d_work);
-	GDSP_HIP_TRY (e);
-	return (bad == 0)? GDSP_OK : gdsp_anchor_refuse (who, "a region is empty or lies outside its vector");
-	}
-
 // the launch sequences of one call (arguments checked, every region inside its vector); *launches counts them
 static int rg_launch (const gdsp_batch_item* items, int nitems, const uint32_t* d_start, const uint32_t* d_end, const uint32_t* d_code,
                       uint32_t count, const RgShape& S, int what, double lo, double hi, double* d_out, uint32_t* d_todo,
@@ -338,14 +300,8 @@ static int rg_launch (const gdsp_batch_item* items, int nitems, const uint32_t* 
 	const dim3 grid (std::min<uint32_t> ((count + MX_WAVES - 1) / MX_WAVES, MX_WG_TARGET)), block (MX_THREADS);
 	return gdsp_anchor_tables (items, nitems, [&] (const GdspAnchorTable& T) -> int
 		{
-		switch (what)
-			{
-			case GDSP_MATRIX_MEAN:  hipLaunchKernelGGL (regions_kernel<GDSP_MATRIX_MEAN>,  grid, block, 0, s, T, d_start, d_end, d_code, count, S, lo, hi, d_out, d_todo, d_ntodo);  break;
-			case GDSP_MATRIX_SUM:   hipLaunchKernelGGL (regions_kernel<GDSP_MATRIX_SUM>,   grid, block, 0, s, T, d_start, d_end, d_code, count, S, lo, hi, d_out, d_todo, d_ntodo);  break;
-			case GDSP_MATRIX_COUNT: hipLaunchKernelGGL (regions_kernel<GDSP_MATRIX_COUNT>, grid, block, 0, s, T, d_start, d_end, d_code, count, S, lo, hi, d_out, d_todo, d_ntodo);  break;
-			case GDSP_MATRIX_MIN:   hipLaunchKernelGGL (regions_kernel<GDSP_MATRIX_MIN>,   grid, block, 0, s, T, d_start, d_end, d_code, count, S, lo, hi, d_out, d_todo, d_ntodo);  break;
-			default:                hipLaunchKernelGGL (regions_kernel<GDSP_MATRIX_MAX>,   grid, block, 0, s, T, d_start, d_end, d_code, count, S, lo, hi, d_out, d_todo, d_ntodo);  break;
-			}
+		mx_with_figure (what, [&] (auto W)
+			{ hipLaunchKernelGGL (regions_kernel<decltype (W)::value>, grid, block, 0, s, T, d_start, d_end, d_code, count, S, lo, hi, d_out, d_todo, d_ntodo); });
 		GDSP_LAUNCH_CHECK ();
 		if (launches != NULL) (*launches)++;
 		return GDSP_OK;
@@ -389,7 +345,7 @@ int gdsp_region_rows_batch (const gdsp_batch_item* items, int nitems, const uint
 	hipStream_t s = gdsp_stream (stream);
 	if (count == 0) return GDSP_OK;
 
-	rc = rg_check_on_device (items, nitems, d_start, d_end, d_code, count, s, __func__);     // on the device, where the regions are
+	rc = gdsp_region_check (items, nitems, d_start, d_end, d_code, count, s, __func__);     // on the device, where the regions are
 	if (rc != GDSP_OK) return rc;
 	return rg_launch (items, nitems, d_start, d_end, d_code, count, S, what, lo, hi, d_out, d_todo, d_ntodo, s, NULL);
 	}
@@ -403,10 +359,10 @@ namespace {
 int rg_on_device (const gdsp_region_source* sources, const int* mine, int nmine, const RgShape& S, int what, double lo, double hi,
                   double* const* h_rows)
 	{
-	const uint32_t ncols = S.ncols;
 	std::vector<gdsp_batch_item> items;
 	std::vector<uint64_t> first (nmine + 1, 0);                   // the device's rows: source k owns first[k] .. first[k+1]
-	std::vector<uint32_t> start, end, code;
+	std::vector<uint32_t> cols[3];                                // the starts, the ends, the code words
+	std::vector<uint32_t> &start = cols[0], &end = cols[1], &code = cols[2];
 	for (int k=0 ; k<nmine ; k++)
 		{
 		const gdsp_region_source& Q = sources[mine[k]];
@@ -419,80 +375,14 @@ int rg_on_device (const gdsp_region_source* sources, const int* mine, int nmine,
 			}
 		first[k+1] = first[k] + Q.nregions;
 		}
-	const uint64_t na = first[nmine];
-	if (na == 0) return GDSP_OK;
-	GDSP_REQUIRE (na <= UINT32_MAX, "more than 2^32 - 1 regions on a device");
-	hipStream_t s = gdsp_stream (sources[mine[0]].stream);
-
-	uint64_t perLaunch = std::max<uint64_t> (1, MX_LAUNCH_CELLS / ncols);
-	if (rgLaunchRows != 0) perLaunch = std::min<uint64_t> (perLaunch, rgLaunchRows);
-	perLaunch = std::min (perLaunch, na);
-	const size_t cells = (size_t) perLaunch * ncols;
-
-	GdspAnchorHeld held;
-	const char* const who = "gdsp_genome_regions";
-	uint32_t *d_regions = NULL, *d_todo = NULL;                   // the starts, the ends, the code words
-	double*   d_out = NULL;
-	int rc = held.alloc ((void**) &d_regions, 3 * na * sizeof(uint32_t), who, "regions");
-	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_out, cells * sizeof(double), who, "rows");
-	if (rc == GDSP_OK) rc = held.alloc ((void**) &d_todo, (cells + 1) * sizeof(uint32_t), who, "to-do list");     // the counter, then the list
-	if (rc != GDSP_OK) return rc;
-	GDSP_HIP_TRY (hipMemcpyAsync (d_regions,          start.data (), na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (d_regions + na,     end.data (),   na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (d_regions + 2 * na, code.data (),  na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-
-	std::vector<uint32_t> todo, tVec, tStart, tEnd;
-	std::vector<double*>  tWhere;
-	std::vector<gdsp_interval_stat> tStat;
-	for (uint64_t r0=0 ; r0<na ; r0+=perLaunch)
-		{
-		const uint32_t nr = (uint32_t) std::min<uint64_t> (perLaunch, na - r0);
-		uint32_t ntodo = 0;
-		GDSP_HIP_TRY (hipMemsetAsync (d_todo, 0, sizeof(uint32_t), s));
-		rc = rg_launch (items.data (), nmine, d_regions + r0, d_regions + na + r0, d_regions + 2 * na + r0, nr, S, what, lo, hi,
-		                d_out, d_todo + 1, d_todo, s, &rgLast[3]);
-		if (rc != GDSP_OK) return rc;
-		GDSP_HIP_TRY (hipMemcpyAsync (&ntodo, d_todo, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-		// the rows, to the sources that own them
-		int k = (int) (std::upper_bound (first.begin (), first.end (), r0) - first.begin ()) - 1;
-		for (uint64_t a=r0 ; a<r0+nr ; )
-			{
-			while (first[k+1] <= a) k++;
-			const uint64_t z = std::min<uint64_t> (first[k+1], r0 + nr);
-			GDSP_HIP_TRY (hipMemcpyAsync (h_rows[mine[k]] + (size_t) (a - first[k]) * ncols, d_out + (size_t) (a - r0) * ncols,
-			                              (size_t) (z - a) * ncols * sizeof(double), hipMemcpyDeviceToHost, s));
-			a = z;
-			}
-		GDSP_HIP_TRY (hipStreamSynchronize (s));
-		if (ntodo == 0) continue;
-
-		// the cells the device left: each is one interval of its chromosome -- by the kernel's own rg_bound -- computed by
-		// the exact interval call
-		GDSP_REQUIRE (ntodo <= (uint64_t) nr * ncols, "the to-do list is longer than the launch");
-		todo.resize (ntodo);
-		GDSP_HIP_TRY (hipMemcpyAsync (todo.data (), d_todo + 1, (size_t) ntodo * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-		GDSP_HIP_TRY (hipStreamSynchronize (s));
-		tVec.clear ();  tStart.clear ();  tEnd.clear ();  tWhere.clear ();
-		for (uint32_t t=0 ; t<ntodo ; t++)
-			{
-			const uint64_t a = r0 + todo[t] / ncols;
-			const uint32_t j = todo[t] % ncols;
-			const int kk = (int) (std::upper_bound (first.begin (), first.end (), a) - first.begin ()) - 1;
-			int64_t gLo, gHi;
-			rg_column (S, rg_row (S, start[a], end[a], gdsp_anchor_minus (code[a])), (int64_t) items[kk].n, j, &gLo, &gHi);
-			double* where = h_rows[mine[kk]] + (size_t) (a - first[kk]) * ncols + j;
-			if (gLo >= gHi) { *where = ((what == GDSP_MATRIX_COUNT) || (what == GDSP_MATRIX_SUM))? 0.0 : NAN;  continue; }
-			tVec.push_back ((uint32_t) kk);  tStart.push_back ((uint32_t) gLo);  tEnd.push_back ((uint32_t) gHi);
-			tWhere.push_back (where);
-			}
-		tStat.resize (tWhere.size ());
-		rc = gdsp_interval_stats_batch (items.data (), nmine, tVec.data (), tStart.data (), tEnd.data (), (uint32_t) tWhere.size (),
-		                                lo, hi, tStat.data (), (void*) s);
-		if (rc != GDSP_OK) return rc;
-		for (size_t t=0 ; t<tWhere.size () ; t++) *tWhere[t] = mx_figure_of (tStat[t], what);
-		rgLast[2] += ntodo;
-		}
-	return GDSP_OK;
+	if (first[nmine] == 0) return GDSP_OK;
+	GDSP_REQUIRE (first[nmine] <= UINT32_MAX, "more than 2^32 - 1 regions on a device");
+	return mx_rows_on_device (items, first, mine, cols, S.ncols, what, lo, hi, h_rows, rgLaunchRows, rgLast,
+	                          sources[mine[0]].stream, "gdsp_genome_regions", "regions",
+		[&] (const uint32_t* d_rows, uint64_t na, uint32_t nr, double* d_out, uint32_t* d_todo, uint32_t* d_ntodo, hipStream_t s, uint64_t* launches) -> int
+			{ return rg_launch (items.data (), nmine, d_rows, d_rows + na, d_rows + 2 * na, nr, S, what, lo, hi, d_out, d_todo, d_ntodo, s, launches); },
+		[&] (uint64_t a, uint32_t j, int64_t n, int64_t* gLo, int64_t* gHi)       // (by the kernel's own rg_bound)
+			{ rg_column (S, rg_row (S, start[a], end[a], gdsp_anchor_minus (code[a])), n, j, gLo, gHi); });
 	}
 
 } // namespace
@@ -518,24 +408,8 @@ int gdsp_genome_regions (const gdsp_region_source* sources, int nsources, uint32
 		rgLast[0] += Q.nregions;
 		}
 	rgLast[1] = rgLast[0] * S.ncols;
-
-	int home = 0;
-	GDSP_HIP_TRY (hipGetDevice (&home));
-	std::vector<int> devices;
-	for (int i=0 ; i<nsources ; i++) devices.push_back (sources[i].device);
-	std::sort (devices.begin (), devices.end ());
-	devices.erase (std::unique (devices.begin (), devices.end ()), devices.end ());
-	std::vector<int> mine;
-	for (size_t d=0 ; (d<devices.size ()) && (rc == GDSP_OK) ; d++)
-		{
-		mine.clear ();
-		for (int i=0 ; i<nsources ; i++) { if (sources[i].device == devices[d]) mine.push_back (i); }
-		if (hipSetDevice (devices[d]) != hipSuccess)
-			{ gdsp_set_error ("gdsp_genome_regions: device %d cannot be selected", devices[d]);  rc = GDSP_EHIP;  break; }
-		rc = rg_on_device (sources, mine.data (), (int) mine.size (), S, what, lo, hi, h_rows);
-		}
-	(void) hipSetDevice (home);
-	return rc;
+	return gdsp_anchor_per_device (sources, nsources, __func__, [&] (const int* mine, int nmine) -> int
+		{ return rg_on_device (sources, mine, nmine, S, what, lo, hi, h_rows); });
 	}
 
 } // extern "C"

@@ -96,6 +96,23 @@ int   read_anchor_line  (char* name, char* filename, FILE* f, char* line, int li
 long long anchor_of     (long long s, long long e, int minus, int anchor);
 void  read_anchor_file  (char* name, char* filename, const anchor_opts* o, const sigpart* parts, int nsrc, anchors* anc,
                          u64* numRead, u64* numUsed, u64* numSkipped, anchor_used_fn used, void* usedCtx);
+/* what matrixover and regionsover share (ops_common.c): a table with one line per used row of a file (an anchor, a
+ * region), in the file's order, held whole on the host.  --as= and the names of the figures (GDSP_MATRIX_*); the used
+ * rows as their lines name them (length: regionsover's); the refusal of more than ROW_TABLE_MAX_CELLS cells (complaint:
+ * the printf format of name, rows, columns, cells and the most cells); a part's vector, device, stream and the storage of
+ * its rows (selects the part's device); the lines -- chrom start end strand, the length when withLength, then ncols values,
+ * NA where there is none; and the variables and the report at the end */
+#define ROW_TABLE_MAX_CELLS (1ull << 30)
+extern const char* const figureNames[5];
+typedef struct rowrec { u32 part, index, start, end, length;  int minus; } rowrec;
+typedef struct rowlist { rowrec* rows;  u64 count, cap;  char* name; } rowlist;
+int   figure_opt_take   (char* name, char* arg, int* what);
+void  rowlist_add       (rowlist* l, int part, u32 index, u32 start, u32 end, u32 length, int minus);
+u64   row_table_cells   (char* name, u64 numUsed, u32 ncols, const char* complaint);
+double* row_table_part  (char* name, const sigpart* part, u32 count, u32 ncols, const valtype** d_v, u32* n, int* device, void** stream);
+void  row_table_print   (char* name, FILE* out, const rowlist* list, double* const* table, u32 ncols, const sigpart* parts,
+                         int strandColumn, int withLength, int precision);
+void  row_table_report  (char* rowsName, u64 numUsed, u64 cells, int quiet);
 
 /* ops_fused.c: run op (and the operators after it, up to stopOp) as one fused kernel when
  * the chain is one the device library fuses; returns how many operators were consumed (0 = none) */
@@ -175,11 +192,30 @@ int   segments_opts_take       (segments_opts* o, char* name, char* arg);
 void  segments_opts_take_other (segments_opts* o, char* name, char* arg);
 void  segments_opts_free       (segments_opts* o);
 void  segments_run             (dspop* op, segments_opts* o, int wantTable, const segments_paint* paint);
-/* what the driver lends statsover (ops_statsover.c): the pending intervals of chromsSorted[ci] as ib_add left them
+/* what the driver lends the interval tables (ops_common.c): the pending intervals of chromsSorted[ci] as ib_add left them
  * (ib_begin forgets them), and the report's "%.*f" (NULL: not a case for the hand-rolled form, print through printf) */
 int   ib_chromosomes      (void);
 u32   ib_pending_of       (int ci, spec** s, u32** start, u32** end, valtype** val);
 char* put_value_fixed     (char* p, valtype v, int precision);
+/* what statsover and percentilesover share (ops_common.c): a table with one line per interval of a file, in file order --
+ * chromosome, start and end as the file has them, then the operator's figures.  The file is read like mask's (read_interval
+ * without a value column, place_interval), the intervals may overlap and come in any order; they are buffered with ib_add
+ * and every ib_batch_limit() of them, and at the end of the file, each device answers those on its chromosomes in one call
+ * and their lines are written.  The operator says how: */
+typedef struct interval_table
+	{
+	size_t recSize;                               /* bytes of what is kept of an interval until its line is written */
+	/* one device's share, that device selected: record i of `out` for interval i, [start[i], end[i]) of items[vec[i]] */
+	void (*answer) (void* ctx, gdsp_batch_item* items, int m, u32* vec, u32* start, u32* end, u32 k, void* out);
+	/* a line behind its end column, from its record, newline included, at p; -> behind what was written */
+	char* (*put) (void* ctx, char* p, const void* rec, spec* s);
+	size_t lineMax;                               /* the most characters of a line, beyond its chromosome's name */
+	void (*header) (void* ctx, FILE* out);        /* writes the header lines; NULL: none */
+	void*  ctx;
+	u64    bases;                                 /* the run adds: the summed length of the intervals, */
+	double msAll, msDevice, msFormat;             /* the time of the run, of its device calls and of formatting and writing */
+	} interval_table;
+void  interval_table_run  (char* name, char* filename, char* outFilename, int originOne, interval_table* t);
 /* ops_correlate.c (correlate), shared with ops_lagcorr.c: the intervals of a file, read
  * by the rules of `add <file>`, into every chromosome's partner -- what `add <file>` would leave on an all-zero genome */
 void  load_track_into_partners (char* name, char* filename, int valColumn, int originOne);

@@ -422,3 +422,215 @@ void read_anchor_file (char* name, char* filename, const anchor_opts* o, const s
 	fclose (f);
 	*_numRead = numRead;  *_numUsed = numUsed;  *_numSkipped = numSkipped;
 	}
+
+/* ---------------------------------------------- a table with one line per used row (matrixover, regionsover) ---- */
+const char* const figureNames[5] = { "mean", "sum", "count", "min", "max" };       /* GDSP_MATRIX_* */
+
+int figure_opt_take (char* name, char* arg, int* what)
+	{
+	if (strcmp_prefix (arg, "--as=") != 0) return false;
+	*what = -1;
+	for (int k=0 ; k<5 ; k++) { if (strcmp (strchr (arg, '=') + 1, figureNames[k]) == 0) *what = k; }
+	if (*what < 0) chastise ("[%s] the figure is mean, sum, count, min or max (\"%s\")\n", name, arg);
+	return true;
+	}
+
+void rowlist_add (rowlist* l, int part, u32 index, u32 start, u32 end, u32 length, int minus)
+	{
+	if (l->count == l->cap)
+		{
+		l->cap  = (l->cap == 0)? 1024 : 2*l->cap;
+		l->rows = (rowrec*) must_alloc (realloc (l->rows, l->cap * sizeof(rowrec)), l->name);
+		}
+	rowrec* r = &l->rows[l->count++];
+	r->part = (u32) part;  r->index = index;  r->start = start;  r->end = end;  r->length = length;  r->minus = minus;
+	}
+
+/* the whole table lives on the host: refused before any device work when it is too large */
+u64 row_table_cells (char* name, u64 numUsed, u32 ncols, const char* complaint)
+	{
+	const u64 cells = numUsed * ncols;
+	if (cells > ROW_TABLE_MAX_CELLS)
+		{
+		fprintf (stderr, complaint, name, (unsigned long long) numUsed, ncols, (unsigned long long) cells, (unsigned long long) ROW_TABLE_MAX_CELLS);
+		exit (EXIT_FAILURE);
+		}
+	return cells;
+	}
+
+double* row_table_part (char* name, const sigpart* part, u32 count, u32 ncols, const valtype** d_v, u32* n, int* device, void** stream)
+	{
+	select_device_of (part->s);
+	*d_v = part->v;  *n = part->n;
+	*device = physical_device_of (part->s);  *stream = op_stream ();
+	return (count == 0)? NULL : (double*) must_alloc (malloc ((size_t) count * ncols * sizeof(double)), name);
+	}
+
+void row_table_print (char* name, FILE* out, const rowlist* list, double* const* table, u32 ncols, const sigpart* parts,
+                      int strandColumn, int withLength, int precision)
+	{
+	enum { textLen = 1 << 16 };
+	char* text = (char*) must_alloc (malloc (textLen), name);
+	for (u64 r=0 ; r<list->count ; r++)
+		{
+		const rowrec* rr = &list->rows[r];
+		const double* x  = table[rr->part] + (size_t) rr->index * ncols;
+		const char strand = (strandColumn < 0)? '.' : (rr->minus? '-' : '+');
+		fprintf (out, "%s\t%u\t%u\t%c", parts[rr->part].s->chrom, rr->start, rr->end, strand);
+		if (withLength) fprintf (out, "\t%u", rr->length);
+		char* p = text;
+		for (u32 j=0 ; j<ncols ; j++)
+			{
+			*(p++) = '\t';
+			if (isnan (x[j])) { memcpy (p, "NA", 2);  p += 2; }
+			else              p = put_value (p, x[j], precision);
+			if (p - text > textLen - 450) { fwrite (text, 1, (size_t) (p - text), out);  p = text; }
+			}
+		*(p++) = '\n';
+		fwrite (text, 1, (size_t) (p - text), out);
+		}
+	free (text);
+	}
+
+void row_table_report (char* rowsName, u64 numUsed, u64 cells, int quiet)
+	{
+	set_named_global (rowsName, (valtype) numUsed);
+	set_named_global ("cells",  (valtype) cells);
+	if (!quiet) fprintf (stderr, "%s is %llu, cells is %llu\n", rowsName, (unsigned long long) numUsed, (unsigned long long) cells);
+	}
+
+/* ------------------------------------ a table with one line per interval of a file (statsover, percentilesover) ---- */
+/* a kept interval as its line names it; its record arrives in rec under the same serial number */
+typedef struct itrow { spec* s;  u32 fileStart, fileEnd; } itrow;
+
+typedef struct itbatch
+	{
+	itrow* rows;   char* rec;   size_t cap;                     /* by serial number */
+	u32   *vec, *start, *end, *serial;  char* out;  size_t ivCap;      /* one device's share, as the library takes it */
+	char*  text;   size_t textCap;
+	} itbatch;
+
+/* the pending intervals' records, device by device (one call each), then their lines in file order */
+static void interval_table_flush (char* name, interval_table* t, itbatch* b, u64 pending, FILE* f)
+	{
+	const int numChroms = ib_chromosomes ();
+	if (pending == 0) return;
+	gdsp_batch_item* items = (gdsp_batch_item*) must_alloc (calloc (numChroms + 1, sizeof(gdsp_batch_item)), name);
+	sync_all_devices ();
+	const double t0 = now_ms ();
+	for (int d=0 ; d<device_count_in_use () ; d++)
+		{
+		int    m = 0;
+		size_t k = 0, want = 0;
+		spec*  first = NULL;
+		for (int ci=0 ; ci<numChroms ; ci++)
+			{
+			spec* s;  u32 *start, *end;  valtype* val;
+			u32 count = ib_pending_of (ci, &s, &start, &end, &val);
+			if ((count != 0) && (device_index_of (s) == d)) want += count;
+			}
+		if (want == 0) continue;
+		if (want > b->ivCap)
+			{
+			free (b->vec);  free (b->start);  free (b->end);  free (b->serial);  free (b->out);
+			b->vec    = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
+			b->start  = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
+			b->end    = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
+			b->serial = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
+			b->out    = (char*) must_alloc (malloc (want * t->recSize), name);
+			b->ivCap  = want;
+			}
+		for (int ci=0 ; ci<numChroms ; ci++)
+			{
+			spec* s;  u32 *start, *end;  valtype* val;
+			u32 count = ib_pending_of (ci, &s, &start, &end, &val);
+			if ((count == 0) || (device_index_of (s) != d)) continue;
+			if (first == NULL) first = s;
+			items[m].d_in = s->valVector;  items[m].d_out = NULL;  items[m].n = s->length;
+			for (u32 i=0 ; i<count ; i++, k++)
+				{ b->vec[k] = (u32) m;  b->start[k] = start[i];  b->end[k] = end[i];  b->serial[k] = (u32) val[i]; }
+			m++;
+			}
+		select_device_of (first);
+		t->answer (t->ctx, items, m, b->vec, b->start, b->end, (u32) k, b->out);
+		for (size_t i=0 ; i<k ; i++) memcpy (b->rec + b->serial[i] * t->recSize, b->out + i * t->recSize, t->recSize);
+		}
+	free (items);
+	select_device_of (chromsSorted[0]);
+	const double t1 = now_ms ();
+
+	size_t len = 0;
+	for (u64 r=0 ; r<pending ; r++)
+		{
+		const itrow* w = &b->rows[r];
+		const size_t chromLen = strlen (w->s->chrom);
+		if (len + chromLen + t->lineMax > b->textCap)
+			{
+			if (len != 0) { fwrite (b->text, 1, len, f);  len = 0; }
+			if (chromLen + t->lineMax > b->textCap)
+				{
+				b->textCap = (1u << 20) + chromLen + t->lineMax;
+				b->text = (char*) must_alloc (realloc (b->text, b->textCap), name);
+				}
+			}
+		char* p = b->text + len;
+		memcpy (p, w->s->chrom, chromLen);  p += chromLen;  *(p++) = '\t';
+		p = put_unsigned (p, w->fileStart);  *(p++) = '\t';
+		p = put_unsigned (p, w->fileEnd);
+		p = t->put (t->ctx, p, b->rec + r * t->recSize, w->s);
+		len = (size_t) (p - b->text);
+		}
+	if (len != 0) fwrite (b->text, 1, len, f);
+	t->msDevice += t1 - t0;  t->msFormat += now_ms () - t1;
+	ib_begin ();                                               /* forget them */
+	}
+
+void interval_table_run (char* name, char* filename, char* outFilename, int originOne, interval_table* t)
+	{
+	char    line[1001], prevChrom[1001];
+	char*   chrom;
+	spec*   s = NULL;
+	u32     start, end, o = originOne? 1 : 0;
+	valtype val;
+	itbatch b;
+	memset (&b, 0, sizeof(b));
+
+	const double tStart = now_ms ();
+	FILE* f = fopen (filename, "rt");
+	if (f == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for reading\n", name, filename);  exit (EXIT_FAILURE); }
+	FILE* out = open_table (name, outFilename);
+	for (int i=0 ; chromsSorted[i]!=NULL ; i++) chromsSorted[i]->flag = false;
+	if (t->header != NULL) t->header (t->ctx, out);
+
+	ib_begin ();
+	prevChrom[0] = 0;
+	while (read_interval (f, line, sizeof(line), /*valCol*/ -1, &chrom, &start, &end, &val))
+		{
+		if (strcmp (chrom, prevChrom) != 0)
+			{ s = find_chromosome_spec (chrom);  safe_strncpy (prevChrom, chrom, sizeof(prevChrom)-1); }
+		if (s == NULL) continue;
+		if (!s->flag) { if (trackOperations) fprintf (stderr, "%s(%s)\n", name, chrom);  s->flag = true; }
+
+		const u32 fileStart = start;
+		start -= o;
+		u32 adjStart, adjEnd;
+		if (!place_interval (name, filename, chrom, s, start, end, &adjStart, &adjEnd)) continue;
+		if (adjStart >= adjEnd) continue;                      /* (an empty interval has no sample and no line) */
+		const u64 serial = ib_pending ();
+		if (serial >= b.cap)
+			{
+			b.cap  = (b.cap == 0)? 4096 : 2*b.cap;
+			b.rows = (itrow*) must_alloc (realloc (b.rows, b.cap * sizeof(itrow)), name);
+			b.rec  = (char*) must_alloc (realloc (b.rec, b.cap * t->recSize), name);
+			}
+		b.rows[serial].s = s;  b.rows[serial].fileStart = fileStart;  b.rows[serial].fileEnd = end;
+		ib_add (s, adjStart, adjEnd, (valtype) serial);
+		t->bases += adjEnd - adjStart;
+		if (ib_pending () >= ib_batch_limit ()) interval_table_flush (name, t, &b, ib_pending (), out);
+		}
+	fclose (f);
+	interval_table_flush (name, t, &b, ib_pending (), out);
+	close_table (out);
+	t->msAll += now_ms () - tStart;
+	free (b.rows);  free (b.rec);  free (b.vec);  free (b.start);  free (b.end);  free (b.serial);  free (b.out);  free (b.text);
+	}

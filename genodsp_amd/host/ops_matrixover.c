@@ -5,7 +5,9 @@
  * in the anchor's own direction.  The signal is not modified.
  *
  * Options, refusals and the file's reader are profileover's (anchor_opts and read_anchor_file, ops_common.c).  The whole
- * matrix is held on the host, 8 bytes a cell, so a call of more than 2^30 cells is refused before any device work.
+ * matrix is held on the host, 8 bytes a cell, so a call of more than 2^30 cells is refused before any device work.  --as=,
+ * that refusal, the storage of the rows, the lines of the table and the report at the end are the row-table half shared
+ * with regionsover (host_services.h, ops_common.c).
  *
  * The figures are gdsp_genome_matrix's (include/genodsp_hip.h): each value is statsover's figure of the cell's interval,
  * exact and rounded once, a function of the cell's sample alone -- so what is printed does not depend on the number of
@@ -24,10 +26,6 @@
 #include "host_services.h"
 
 dspprototypes(op_matrixover)
-
-#define MATRIX_MAX_CELLS (1ull << 30)
-
-static const char* const figureNames[5] = { "mean", "sum", "count", "min", "max" };       /* GDSP_MATRIX_* */
 
 typedef struct dspop_matrixover
 	{
@@ -79,13 +77,7 @@ dspop* op_matrixover_parse (char* name, int argc, char** argv)
 		char* arg = argv[0];
 		char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
 		if (anchor_opts_take (&op->where, name, arg)) continue;
-		if (strcmp_prefix (arg, "--as=") == 0)
-			{
-			op->what = -1;
-			for (int k=0 ; k<5 ; k++) { if (strcmp (argVal, figureNames[k]) == 0) op->what = k; }
-			if (op->what < 0) chastise ("[%s] the figure is mean, sum, count, min or max (\"%s\")\n", name, arg);
-			continue;
-			}
+		if (figure_opt_take (name, arg, &op->what)) continue;
 		if (strcmp_prefix (arg, "--output=") == 0)
 			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
 		if (sample_opts_take (&op->sample, name, arg, SAMPLE_OPT_PRECISION | SAMPLE_OPT_QUIET)) continue;
@@ -109,20 +101,8 @@ void op_matrixover_free (dspop* _op)
 	}
 
 /* the used anchors in the file's order: whose row each is, and its interval as the file has it */
-typedef struct rowrec { u32 part, index, start, end;  int minus; } rowrec;
-typedef struct rowlist { rowrec* rows;  u64 count, cap;  char* name; } rowlist;
-
 static void remember_row (void* ctx, int part, u32 index, u32 start, u32 end, int minus)
-	{
-	rowlist* l = (rowlist*) ctx;
-	if (l->count == l->cap)
-		{
-		l->cap  = (l->cap == 0)? 1024 : 2*l->cap;
-		l->rows = (rowrec*) must_alloc (realloc (l->rows, l->cap * sizeof(rowrec)), l->name);
-		}
-	rowrec* r = &l->rows[l->count++];
-	r->part = (u32) part;  r->index = index;  r->start = start;  r->end = end;  r->minus = minus;
-	}
+	{ rowlist_add ((rowlist*) ctx, part, index, start, end, /*length*/ 0, minus); }
 
 void op_matrixover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
 	{
@@ -139,26 +119,16 @@ void op_matrixover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_c
 	rowlist list = { NULL, 0, 0, name };
 	u64 numRead, numUsed, numSkipped;
 	read_anchor_file (name, op->filename, &op->where, parts, nsrc, anc, &numRead, &numUsed, &numSkipped, remember_row, &list);
-
-	/* the whole matrix lives on the host: refused before any device work when it is too large */
-	const u64 cells = numUsed * ncols;
-	if (cells > MATRIX_MAX_CELLS)
-		{
-		fprintf (stderr, "[%s] %llu anchors times %u columns are %llu cells, more than the %llu a call can hold; use a wider --bin\n",
-		         name, (unsigned long long) numUsed, ncols, (unsigned long long) cells, (unsigned long long) MATRIX_MAX_CELLS);
-		exit (EXIT_FAILURE);
-		}
+	const u64 cells = row_table_cells (name, numUsed, ncols,
+	                                   "[%s] %llu anchors times %u columns are %llu cells, more than the %llu a call can hold; use a wider --bin\n");
 
 	gdsp_profile_source* src = (gdsp_profile_source*) must_alloc (calloc (nsrc? nsrc : 1, sizeof(gdsp_profile_source)), name);
 	double** rows = (double**) must_alloc (calloc (nsrc? nsrc : 1, sizeof(double*)), name);
 	sync_all_devices ();
 	for (int i=0 ; i<nsrc ; i++)
 		{
-		select_device_of (parts[i].s);
-		src[i].d_v = parts[i].v;  src[i].n = parts[i].n;
-		src[i].device = physical_device_of (parts[i].s);  src[i].stream = op_stream ();
+		rows[i] = row_table_part (name, &parts[i], anc[i].count, ncols, &src[i].d_v, &src[i].n, &src[i].device, &src[i].stream);
 		src[i].h_pos = anc[i].pos;  src[i].h_minus = anc[i].minus;  src[i].nanchors = anc[i].count;
-		if (anc[i].count != 0) rows[i] = (double*) must_alloc (malloc ((size_t) anc[i].count * ncols * sizeof(double)), name);
 		}
 	if (nsrc > 0) select_device_of (parts[0].s);
 	check_gdsp (gdsp_genome_matrix (src, nsrc, offLo, noffsets, bin, op->what, op->sample.minAllowed, op->sample.maxAllowed, rows), name);
@@ -175,35 +145,12 @@ void op_matrixover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_c
 	fprintf (out, "#chrom\tstart\tend\tstrand");
 	for (u32 j=0 ; j<ncols ; j++) fprintf (out, "\t%d", offLo + (int) (j * bin));
 	fprintf (out, "\n");
-	enum { textLen = 1 << 16 };
-	char* text = (char*) must_alloc (malloc (textLen), name);
-	for (u64 r=0 ; r<list.count ; r++)
-		{
-		const rowrec* rr = &list.rows[r];
-		const double* x  = rows[rr->part] + (size_t) rr->index * ncols;
-		const char strand = (op->where.strandColumn < 0)? '.' : (rr->minus? '-' : '+');
-		fprintf (out, "%s\t%u\t%u\t%c", parts[rr->part].s->chrom, rr->start, rr->end, strand);
-		char* p = text;
-		for (u32 j=0 ; j<ncols ; j++)
-			{
-			*(p++) = '\t';
-			if (isnan (x[j])) { memcpy (p, "NA", 2);  p += 2; }
-			else              p = put_value (p, x[j], op->sample.precision);
-			if (p - text > textLen - 450) { fwrite (text, 1, (size_t) (p - text), out);  p = text; }
-			}
-		*(p++) = '\n';
-		fwrite (text, 1, (size_t) (p - text), out);
-		}
+	row_table_print (name, out, &list, rows, ncols, parts, op->where.strandColumn, /*withLength*/ false, op->sample.precision);
 	close_table (out);
-	free (text);
 	for (int i=0 ; i<nsrc ; i++) free (rows[i]);
 	free (rows);
 	free (list.rows);
-
-	set_named_global ("anchors", (valtype) numUsed);
-	set_named_global ("cells",   (valtype) cells);
-	if (!op->sample.quiet)
-		fprintf (stderr, "anchors is %llu, cells is %llu\n", (unsigned long long) numUsed, (unsigned long long) cells);
+	row_table_report ("anchors", numUsed, cells, op->sample.quiet);
 	}
 
 /* the driver: the signal is only read, 8 B per anchor and offset, and 8 B are written per cell */

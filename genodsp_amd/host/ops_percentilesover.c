@@ -4,12 +4,12 @@
  * reads does not drag).  What statsover leaves out, since it takes more than one reduction per interval.  The signal is
  * not modified and no variable is set.  The two operators differ in name only: both default to --percentiles=50.
  *
- * The file is read like statsover's (ops_statsover.c: read_interval without a value column, the routing, origin and
- * clipping rules of fileop_apply; the intervals may overlap and come in any order), buffered with ib_add -- the value slot
- * carries the interval's serial number in its batch -- and every ib_batch_limit() of them, and at the end of the file,
- * each device answers the intervals on its chromosomes in one call (gdsp_interval_percentiles_batch,
- * include/genodsp_hip.h: every value an input value, a function of the interval's sample alone).  Batches are
- * consecutive stretches of the file, so printing them one after the other keeps file order.
+ * The file is read, the intervals are batched and the lines are written by the half shared with statsover
+ * (interval_table_run, ops_common.c; host_services.h says how): the intervals may overlap and come in any order, and every
+ * ib_batch_limit() of them, and at the end of the file, each device answers the intervals on its chromosomes in one call
+ * (gdsp_interval_percentiles_batch, include/genodsp_hip.h: every value an input value, a function of the interval's sample
+ * alone).  What is these operators' own is that call, the header with a column per percentile and the values of a line,
+ * NA where the sample is empty.
  *
  * The driver finds these operators through opgroup_percentilesover, at the end of this file (host_services.h); every call
  * into the device library for them stays here. */
@@ -106,125 +106,54 @@ static void percentilesover_free (dspop* _op)
 	free (op);
 	}
 
-/* ------------------------------------------------------------------------------------------ one batch ---- */
-/* a kept interval as its line names it; its figures arrive in count[] and values[] under the same serial number */
-typedef struct row { spec* s;  u32 fileStart, fileEnd; } row;
+/* ------------------------------------------------------------------------------------- the table's figures ---- */
+/* what is kept of an interval: the size of its sample and, in the order asked for, its numPcts percentiles */
+typedef struct pctrec { u32 count;  double values[]; } pctrec;
+#define pctrec_size(np) (sizeof(pctrec) + (size_t) (np) * sizeof(double))
 
-typedef struct batch
+/* one device's share in one call */
+static void answer_percentiles (void* ctx, gdsp_batch_item* items, int m, u32* vec, u32* start, u32* end, u32 k, void* out)
 	{
-	row*   rows;   u32* count;   double* values;   size_t cap;                /* by serial number */
-	u32   *vec, *start, *end, *serial, *outCount;  double* outValues;  size_t ivCap;   /* one device's share, as the library takes it */
-	char*  text;   size_t textCap;
-	} batch;
-
-/* the pending intervals' figures, device by device (one call each), then their lines in file order */
-static void flush_batch (dspop_percentilesover* op, batch* b, u64 pending, FILE* f)
-	{
-	const char*  name = op->common.name;
-	const int    numChroms = ib_chromosomes ();
+	dspop_percentilesover* op = (dspop_percentilesover*) ctx;
+	char*        name = op->common.name;
 	const size_t np = (size_t) op->numPcts;
-	if (pending == 0) return;
-	gdsp_batch_item* items = (gdsp_batch_item*) must_alloc (calloc (numChroms + 1, sizeof(gdsp_batch_item)), name);
-	sync_all_devices ();
-	for (int d=0 ; d<device_count_in_use () ; d++)
+	u32*    count  = (u32*) must_alloc (malloc (k * sizeof(u32)), name);
+	double* values = (double*) must_alloc (malloc (k * np * sizeof(double)), name);
+	check_gdsp (gdsp_interval_percentiles_batch (items, m, vec, start, end, k, op->pcts, op->numPcts, op->sample.minAllowed,
+	                                             op->sample.maxAllowed, count, values, op_stream ()), name);
+	for (size_t i=0 ; i<k ; i++)
 		{
-		int    m = 0;
-		size_t k = 0, want = 0;
-		spec*  first = NULL;
-		for (int ci=0 ; ci<numChroms ; ci++)
-			{
-			spec* s;  u32 *start, *end;  valtype* val;
-			u32 count = ib_pending_of (ci, &s, &start, &end, &val);
-			if ((count != 0) && (device_index_of (s) == d)) want += count;
-			}
-		if (want == 0) continue;
-		if (want > b->ivCap)
-			{
-			free (b->vec);  free (b->start);  free (b->end);  free (b->serial);  free (b->outCount);  free (b->outValues);
-			b->vec       = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
-			b->start     = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
-			b->end       = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
-			b->serial    = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
-			b->outCount  = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
-			b->outValues = (double*) must_alloc (malloc (want * GDSP_INTERVAL_PERCENTILES_MAX * sizeof(double)), name);
-			b->ivCap     = want;
-			}
-		for (int ci=0 ; ci<numChroms ; ci++)
-			{
-			spec* s;  u32 *start, *end;  valtype* val;
-			u32 count = ib_pending_of (ci, &s, &start, &end, &val);
-			if ((count == 0) || (device_index_of (s) != d)) continue;
-			if (first == NULL) first = s;
-			items[m].d_in = s->valVector;  items[m].d_out = NULL;  items[m].n = s->length;
-			for (u32 i=0 ; i<count ; i++, k++)
-				{ b->vec[k] = (u32) m;  b->start[k] = start[i];  b->end[k] = end[i];  b->serial[k] = (u32) val[i]; }
-			m++;
-			}
-		select_device_of (first);
-		check_gdsp (gdsp_interval_percentiles_batch (items, m, b->vec, b->start, b->end, (u32) k, op->pcts, op->numPcts,
-		                                             op->sample.minAllowed, op->sample.maxAllowed, b->outCount, b->outValues,
-		                                             op_stream ()), name);
-		for (size_t i=0 ; i<k ; i++)
-			{
-			b->count[b->serial[i]] = b->outCount[i];
-			memcpy (&b->values[b->serial[i] * np], &b->outValues[i * np], np * sizeof(double));
-			}
+		pctrec* r = (pctrec*) ((char*) out + i * pctrec_size (np));
+		r->count = count[i];
+		memcpy (r->values, &values[i * np], np * sizeof(double));
 		}
-	free (items);
-	select_device_of (chromsSorted[0]);
-
-	/* a line: the name, two coordinates and the count (at most 20 digits each), np values of at most 400 characters, tabs */
-	const size_t lineMax = 100 + 401 * np;
-	size_t len = 0;
-	for (u64 r=0 ; r<pending ; r++)
-		{
-		const row* w = &b->rows[r];
-		const size_t chromLen = strlen (w->s->chrom);
-		if (len + chromLen + lineMax > b->textCap)
-			{
-			if (len != 0) { fwrite (b->text, 1, len, f);  len = 0; }
-			if (chromLen + lineMax > b->textCap)
-				{
-				b->textCap = (1u << 20) + chromLen + lineMax;
-				b->text = (char*) must_alloc (realloc (b->text, b->textCap), name);
-				}
-			}
-		char* p = b->text + len;
-		memcpy (p, w->s->chrom, chromLen);  p += chromLen;  *(p++) = '\t';
-		p = put_unsigned (p, w->fileStart);  *(p++) = '\t';
-		p = put_unsigned (p, w->fileEnd);    *(p++) = '\t';
-		p = put_unsigned (p, b->count[r]);
-		for (size_t j=0 ; j<np ; j++)
-			{
-			const double x = b->values[r * np + j];
-			*(p++) = '\t';
-			if (isnan (x)) { *(p++) = 'N';  *(p++) = 'A'; }
-			else           p = put_value (p, x, op->sample.precision);
-			}
-		*(p++) = '\n';
-		len = (size_t) (p - b->text);
-		}
-	if (len != 0) fwrite (b->text, 1, len, f);
-	ib_begin ();                                               /* forget them */
+	free (count);  free (values);
 	}
 
-static void percentilesover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
+/* a line: the name, two coordinates and the count (at most 20 digits each), np values of at most 400 characters, tabs */
+#define pct_line_max(np) (100 + 401 * (size_t) (np))
+
+static char* put_percentiles (void* ctx, char* p, const void* rec, arg_dont_complain(spec* s))
 	{
-	dspop_percentilesover* op = (dspop_percentilesover*) _op;
-	char    line[1001], prevChrom[1001];
-	char*   chrom;
-	spec*   s = NULL;
-	u32     start, end, o = op->originOne? 1 : 0;
-	valtype val;
-	batch   b;
-	memset (&b, 0, sizeof(b));
+	dspop_percentilesover* op = (dspop_percentilesover*) ctx;
+	const pctrec* r = (const pctrec*) rec;
+	*(p++) = '\t';
+	p = put_unsigned (p, r->count);
+	for (int j=0 ; j<op->numPcts ; j++)
+		{
+		const double x = r->values[j];
+		*(p++) = '\t';
+		if (isnan (x)) { *(p++) = 'N';  *(p++) = 'A'; }
+		else           p = put_value (p, x, op->sample.precision);
+		}
+	*(p++) = '\n';
+	return p;
+	}
 
-	FILE* f = fopen (op->filename, "rt");
-	if (f == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for reading\n", _op->name, op->filename);  exit (EXIT_FAILURE); }
-	FILE* out = open_table (_op->name, op->outFilename);
-	for (int i=0 ; chromsSorted[i]!=NULL ; i++) chromsSorted[i]->flag = false;
-
-	/* the header: a column per percentile, named as percentile names its variable */
+/* the header: a column per percentile, named as percentile names its variable */
+static void put_header (void* ctx, FILE* out)
+	{
+	dspop_percentilesover* op = (dspop_percentilesover*) ctx;
 	fputs ("#chrom\tstart\tend\tcount", out);
 	for (int j=0 ; j<op->numPcts ; j++)
 		{
@@ -233,39 +162,14 @@ static void percentilesover_apply (dspop* _op, arg_dont_complain(char* vName), a
 		fprintf (out, "\tp%s", varName + strlen ("percentile"));
 		}
 	fputc ('\n', out);
+	}
 
-	ib_begin ();
-	prevChrom[0] = 0;
-	while (read_interval (f, line, sizeof(line), /*valCol*/ -1, &chrom, &start, &end, &val))
-		{
-		if (strcmp (chrom, prevChrom) != 0)
-			{ s = find_chromosome_spec (chrom);  safe_strncpy (prevChrom, chrom, sizeof(prevChrom)-1); }
-		if (s == NULL) continue;
-		if (!s->flag) { if (trackOperations) fprintf (stderr, "%s(%s)\n", _op->name, chrom);  s->flag = true; }
-
-		const u32 fileStart = start;
-		start -= o;
-		u32 adjStart, adjEnd;
-		if (!place_interval (_op->name, op->filename, chrom, s, start, end, &adjStart, &adjEnd)) continue;
-		if (adjStart >= adjEnd) continue;                      /* (an empty interval has no sample and no line) */
-		const u64 serial = ib_pending ();
-		if (serial >= b.cap)
-			{
-			b.cap    = (b.cap == 0)? 4096 : 2*b.cap;
-			b.rows   = (row*) must_alloc (realloc (b.rows, b.cap * sizeof(row)), _op->name);
-			b.count  = (u32*) must_alloc (realloc (b.count, b.cap * sizeof(u32)), _op->name);
-			b.values = (double*) must_alloc (realloc (b.values, b.cap * GDSP_INTERVAL_PERCENTILES_MAX * sizeof(double)), _op->name);
-			}
-		b.rows[serial].s = s;  b.rows[serial].fileStart = fileStart;  b.rows[serial].fileEnd = end;
-		ib_add (s, adjStart, adjEnd, (valtype) serial);
-		op->bases += adjEnd - adjStart;
-		if (ib_pending () >= ib_batch_limit ()) flush_batch (op, &b, ib_pending (), out);
-		}
-	fclose (f);
-	flush_batch (op, &b, ib_pending (), out);
-	close_table (out);
-	free (b.rows);  free (b.count);  free (b.values);  free (b.vec);  free (b.start);  free (b.end);  free (b.serial);
-	free (b.outCount);  free (b.outValues);  free (b.text);
+static void percentilesover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
+	{
+	dspop_percentilesover* op = (dspop_percentilesover*) _op;
+	interval_table t = { pctrec_size (op->numPcts), answer_percentiles, put_percentiles, pct_line_max (op->numPcts), put_header, op, 0, 0, 0, 0 };
+	interval_table_run (_op->name, op->filename, op->outFilename, op->originOne, &t);
+	op->bases += t.bases;
 	}
 
 /* the driver: the signal is only read, 8 B per base of the intervals' summed length since the last call (the long

@@ -6,8 +6,11 @@
  * The signal is not modified.
  *
  * The file's lines are read as profileover and matrixover read them (read_anchor_line, ops_common.c), and the options
- * that are theirs too are taken by anchor_opts_take; what a region is and which are used is decided here.  The whole
- * table is held on the host, 8 bytes a cell, so a call of more than 2^30 cells is refused before any device work.
+ * that are theirs too are taken by anchor_opts_take; what a region is and which are used is decided here -- the reader
+ * stays here because it counts a line on a chromosome the genome lacks as read and skipped, which read_anchor_file does
+ * not count at all.  The whole table is held on the host, 8 bytes a cell, so a call of more than 2^30 cells is refused
+ * before any device work.  --as=, that refusal, the storage of the rows, the lines of the table and the report at the end
+ * are the row-table half shared with matrixover (host_services.h, ops_common.c).
  *
  * The figures are gdsp_genome_regions' (include/genodsp_hip.h): each value is statsover's figure of the cell's interval,
  * exact and rounded once, a function of the cell's sample alone -- so what is printed does not depend on the number of
@@ -26,10 +29,6 @@
 #include "host_services.h"
 
 dspprototypes(op_regionsover)
-
-#define REGIONS_MAX_CELLS (1ull << 30)
-
-static const char* const figureNames[5] = { "mean", "sum", "count", "min", "max" };       /* GDSP_MATRIX_* */
 
 typedef struct dspop_regionsover
 	{
@@ -101,13 +100,7 @@ dspop* op_regionsover_parse (char* name, int argc, char** argv)
 		if (strcmp_prefix (arg, "--anchor=") == 0)
 			chastise ("[%s] a region is looked at from its start to its end: no anchor (\"%s\")\n", name, arg);
 		if (anchor_opts_take (&op->where, name, arg)) continue;        /* (flanks, --bin=, --strand=, --origin=; refuses a window) */
-		if (strcmp_prefix (arg, "--as=") == 0)
-			{
-			op->what = -1;
-			for (int k=0 ; k<5 ; k++) { if (strcmp (argVal, figureNames[k]) == 0) op->what = k; }
-			if (op->what < 0) chastise ("[%s] the figure is mean, sum, count, min or max (\"%s\")\n", name, arg);
-			continue;
-			}
+		if (figure_opt_take (name, arg, &op->what)) continue;
 		if (strcmp_prefix (arg, "--output=") == 0)
 			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
 		if (sample_opts_take (&op->sample, name, arg, SAMPLE_OPT_PRECISION | SAMPLE_OPT_QUIET)) continue;
@@ -142,9 +135,8 @@ void op_regionsover_free (dspop* _op)
 	free (op);
 	}
 
-/* the regions of one chromosome as the library takes them, and the used regions in the file's order */
+/* the regions of one chromosome as the library takes them */
 typedef struct regions { u32 *start, *end, *minus;  u32 count, cap; } regions;
-typedef struct rowrec { u32 part, index, start, end, length;  int minus; } rowrec;
 
 void op_regionsover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
 	{
@@ -158,8 +150,8 @@ void op_regionsover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_
 	sigpart* parts;
 	int nsrc = signal_parts (&parts);
 	regions* reg = (regions*) must_alloc (calloc (nsrc? nsrc : 1, sizeof(regions)), name);
-	rowrec*  rows = NULL;
-	u64 numRows = 0, capRows = 0, numRead = 0, numSkipped = 0, basesSeen = 0;
+	rowlist  list = { NULL, 0, 0, name };                     /* the used regions in the file's order */
+	u64 numRead = 0, numSkipped = 0, basesSeen = 0;
 
 	/* the file: a region is used when its chromosome is in the genome, it lies inside it and it is long enough */
 	FILE* f = fopen (op->filename, "rt");
@@ -195,38 +187,22 @@ void op_regionsover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_
 			a->end   = (u32*) must_alloc (realloc (a->end,   a->cap * sizeof(u32)), name);
 			a->minus = (u32*) must_alloc (realloc (a->minus, a->cap * sizeof(u32)), name);
 			}
-		if (numRows == capRows)
-			{
-			capRows = (capRows == 0)? 1024 : 2*capRows;
-			rows = (rowrec*) must_alloc (realloc (rows, capRows * sizeof(rowrec)), name);
-			}
-		rowrec* rr = &rows[numRows++];
-		rr->part = (u32) at;  rr->index = a->count;  rr->start = start;  rr->end = end;  rr->length = (u32) (ie - is);  rr->minus = minus;
+		rowlist_add (&list, at, a->count, start, end, (u32) (ie - is), minus);
 		a->start[a->count] = (u32) is;  a->end[a->count] = (u32) ie;  a->minus[a->count] = (u32) minus;  a->count++;
 		basesSeen += (u64) U + (u64) (ie - is) + (u64) D;
 		}
 	fclose (f);
-	const u64 numUsed = numRows;
-
-	/* the whole table lives on the host: refused before any device work when it is too large */
-	const u64 cells = numUsed * ncols;
-	if (cells > REGIONS_MAX_CELLS)
-		{
-		fprintf (stderr, "[%s] %llu regions times %u columns are %llu cells, more than the %llu a call can hold; use a smaller --body or a wider --bin\n",
-		         name, (unsigned long long) numUsed, ncols, (unsigned long long) cells, (unsigned long long) REGIONS_MAX_CELLS);
-		exit (EXIT_FAILURE);
-		}
+	const u64 numUsed = list.count;
+	const u64 cells = row_table_cells (name, numUsed, ncols,
+	                                   "[%s] %llu regions times %u columns are %llu cells, more than the %llu a call can hold; use a smaller --body or a wider --bin\n");
 
 	gdsp_region_source* src = (gdsp_region_source*) must_alloc (calloc (nsrc? nsrc : 1, sizeof(gdsp_region_source)), name);
 	double** table = (double**) must_alloc (calloc (nsrc? nsrc : 1, sizeof(double*)), name);
 	sync_all_devices ();
 	for (int i=0 ; i<nsrc ; i++)
 		{
-		select_device_of (parts[i].s);
-		src[i].d_v = parts[i].v;  src[i].n = parts[i].n;
-		src[i].device = physical_device_of (parts[i].s);  src[i].stream = op_stream ();
+		table[i] = row_table_part (name, &parts[i], reg[i].count, ncols, &src[i].d_v, &src[i].n, &src[i].device, &src[i].stream);
 		src[i].h_start = reg[i].start;  src[i].h_end = reg[i].end;  src[i].h_minus = reg[i].minus;  src[i].nregions = reg[i].count;
-		if (reg[i].count != 0) table[i] = (double*) must_alloc (malloc ((size_t) reg[i].count * ncols * sizeof(double)), name);
 		}
 	if (nsrc > 0) select_device_of (parts[0].s);
 	check_gdsp (gdsp_genome_regions (src, nsrc, B, U, D, bin, op->what, op->sample.minAllowed, op->sample.maxAllowed, table), name);
@@ -245,35 +221,12 @@ void op_regionsover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_
 	for (u32 j=0 ; j<B ; j++)     fprintf (out, "\tb%u", j);
 	for (u32 j=0 ; j<nDown ; j++) fprintf (out, "\t+%u", j * bin);
 	fprintf (out, "\n");
-	enum { textLen = 1 << 16 };
-	char* text = (char*) must_alloc (malloc (textLen), name);
-	for (u64 r=0 ; r<numRows ; r++)
-		{
-		const rowrec* rr = &rows[r];
-		const double* x  = table[rr->part] + (size_t) rr->index * ncols;
-		const char strand = (op->where.strandColumn < 0)? '.' : (rr->minus? '-' : '+');
-		fprintf (out, "%s\t%u\t%u\t%c\t%u", parts[rr->part].s->chrom, rr->start, rr->end, strand, rr->length);
-		char* p = text;
-		for (u32 j=0 ; j<ncols ; j++)
-			{
-			*(p++) = '\t';
-			if (isnan (x[j])) { memcpy (p, "NA", 2);  p += 2; }
-			else              p = put_value (p, x[j], op->sample.precision);
-			if (p - text > textLen - 450) { fwrite (text, 1, (size_t) (p - text), out);  p = text; }
-			}
-		*(p++) = '\n';
-		fwrite (text, 1, (size_t) (p - text), out);
-		}
+	row_table_print (name, out, &list, table, ncols, parts, op->where.strandColumn, /*withLength*/ true, op->sample.precision);
 	close_table (out);
-	free (text);
 	for (int i=0 ; i<nsrc ; i++) free (table[i]);
 	free (table);
-	free (rows);
-
-	set_named_global ("regions", (valtype) numUsed);
-	set_named_global ("cells",   (valtype) cells);
-	if (!op->sample.quiet)
-		fprintf (stderr, "regions is %llu, cells is %llu\n", (unsigned long long) numUsed, (unsigned long long) cells);
+	free (list.rows);
+	row_table_report ("regions", numUsed, cells, op->sample.quiet);
 	}
 
 /* the driver: the signal is only read, 8 B per base of a region and its flanks, and 8 B are written per cell */

@@ -2,12 +2,12 @@
  * file -- count, sum, mean, min, max and the position of the maximum of the signal inside it (mean depth per gene;
  * height, area and summit of every peak; signal per bin).  The signal is not modified and no variable is set.
  *
- * The file is read like mask's and maxover's (read_interval, no value column; the routing, origin and clipping rules of
- * fileop_apply, ops_intervals.c), but the intervals may overlap and come in any order.  They are buffered with ib_add --
- * the value slot carries the interval's serial number in its batch -- and every ib_batch_limit() of them, and at the end
- * of the file, each device computes the figures of the intervals on its chromosomes in one launch
- * (gdsp_interval_stats_batch, include/genodsp_hip.h: every figure exact and rounded once, a function of the interval's
- * sample alone).  Batches are consecutive stretches of the file, so printing them one after the other keeps file order.
+ * The file is read, the intervals are batched and the lines are written by the half shared with percentilesover
+ * (interval_table_run, ops_common.c; host_services.h says how): the intervals may overlap and come in any order, and every
+ * ib_batch_limit() of them, and at the end of the file, each device computes the figures of the intervals on its
+ * chromosomes in one launch (gdsp_interval_stats_batch, include/genodsp_hip.h: every figure exact and rounded once, a
+ * function of the interval's sample alone).  What is statsover's own is that call, the figures of a line
+ * (put_interval_figures) and, with GDSP_STATSOVER_TIMES=1, where a run's time went, on stderr.
  *
  * The driver finds this operator through opgroup_statsover, at the end of this file (host_services.h); every call into the
  * device library for it stays here. */
@@ -31,7 +31,6 @@ typedef struct dspop_statsover
 	sample_opts sample;                         /* (its limits and precision; no window) */
 	int         originOne;
 	u64         bases;                          /* summed length of the intervals (--report=gpu) */
-	double      msDevice, msFormat;             /* GDSP_STATSOVER_TIMES=1: where a run's time went, on stderr */
 	} dspop_statsover;
 
 OP_SHORT (op_statsover, "print count, sum, mean, min, max and summit of the signal over each interval of a file (not in genodsp)")
@@ -82,148 +81,30 @@ void op_statsover_free (dspop* _op)
 	free (op);
 	}
 
-/* ------------------------------------------------------------------------------------------ one batch ---- */
-/* a kept interval as its line names it; its figures arrive in rec[] under the same serial number */
-typedef struct row { spec* s;  u32 fileStart, fileEnd; } row;
-
-typedef struct batch
+/* ------------------------------------------------------------------------------------- the table's figures ---- */
+/* one device's share in one launch */
+static void answer_stats (void* ctx, gdsp_batch_item* items, int m, u32* vec, u32* start, u32* end, u32 k, void* out)
 	{
-	row*   rows;   gdsp_interval_stat* rec;   size_t cap;  /* by serial number */
-	u32   *vec, *start, *end, *serial;  gdsp_interval_stat* out;  size_t ivCap;     /* one device's share, as the library takes it */
-	char*  text;   size_t textCap;
-	} batch;
+	dspop_statsover* op = (dspop_statsover*) ctx;
+	check_gdsp (gdsp_interval_stats_batch (items, m, vec, start, end, k, op->sample.minAllowed, op->sample.maxAllowed,
+	                                       (gdsp_interval_stat*) out, op_stream ()), op->common.name);
+	}
 
-/* the pending intervals' figures, device by device (one launch each), then their lines in file order */
-static void flush_batch (dspop_statsover* op, batch* b, u64 pending, FILE* f)
+static char* put_stats (void* ctx, char* p, const void* rec, spec* s)
 	{
-	const char* name = op->common.name;
-	const int   numChroms = ib_chromosomes ();
-	gdsp_batch_item* items = (gdsp_batch_item*) must_alloc (calloc (numChroms + 1, sizeof(gdsp_batch_item)), name);
-	if (pending == 0) { free (items);  return; }
-	sync_all_devices ();
-	const double t0 = now_ms ();
-	for (int d=0 ; d<device_count_in_use () ; d++)
-		{
-		int    m = 0;
-		size_t k = 0, want = 0;
-		spec*  first = NULL;
-		for (int ci=0 ; ci<numChroms ; ci++)
-			{
-			spec* s;  u32 *start, *end;  valtype* val;
-			u32 count = ib_pending_of (ci, &s, &start, &end, &val);
-			if ((count != 0) && (device_index_of (s) == d)) want += count;
-			}
-		if (want == 0) continue;
-		if (want > b->ivCap)
-			{
-			free (b->vec);  free (b->start);  free (b->end);  free (b->serial);  free (b->out);
-			b->vec    = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
-			b->start  = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
-			b->end    = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
-			b->serial = (u32*) must_alloc (malloc (want * sizeof(u32)), name);
-			b->out    = (gdsp_interval_stat*) must_alloc (malloc (want * sizeof(gdsp_interval_stat)), name);
-			b->ivCap  = want;
-			}
-		for (int ci=0 ; ci<numChroms ; ci++)
-			{
-			spec* s;  u32 *start, *end;  valtype* val;
-			u32 count = ib_pending_of (ci, &s, &start, &end, &val);
-			if ((count == 0) || (device_index_of (s) != d)) continue;
-			if (first == NULL) first = s;
-			items[m].d_in = s->valVector;  items[m].d_out = NULL;  items[m].n = s->length;
-			for (u32 i=0 ; i<count ; i++, k++)
-				{ b->vec[k] = (u32) m;  b->start[k] = start[i];  b->end[k] = end[i];  b->serial[k] = (u32) val[i]; }
-			m++;
-			}
-		select_device_of (first);
-		check_gdsp (gdsp_interval_stats_batch (items, m, b->vec, b->start, b->end, (u32) k, op->sample.minAllowed, op->sample.maxAllowed,
-		                                       b->out, op_stream ()), name);
-		for (size_t i=0 ; i<k ; i++) b->rec[b->serial[i]] = b->out[i];
-		}
-	free (items);
-	select_device_of (chromsSorted[0]);
-	const double t1 = now_ms ();
-
-	size_t len = 0;
-	for (u64 r=0 ; r<pending ; r++)
-		{
-		const row* w = &b->rows[r];
-		const size_t chromLen = strlen (w->s->chrom);
-		if (len + chromLen + 2200 > b->textCap)
-			{
-			if (len != 0) { fwrite (b->text, 1, len, f);  len = 0; }
-			if (chromLen + 2200 > b->textCap)
-				{
-				b->textCap = (1u << 20) + chromLen + 2200;
-				b->text = (char*) must_alloc (realloc (b->text, b->textCap), name);
-				}
-			}
-		char* p = b->text + len;
-		memcpy (p, w->s->chrom, chromLen);  p += chromLen;  *(p++) = '\t';
-		p = put_unsigned (p, w->fileStart);  *(p++) = '\t';
-		p = put_unsigned (p, w->fileEnd);
-		p = put_interval_figures (p, &b->rec[r], w->s->start, op->originOne, op->sample.precision);
-		len = (size_t) (p - b->text);
-		}
-	if (len != 0) fwrite (b->text, 1, len, f);
-	op->msDevice += t1 - t0;  op->msFormat += now_ms () - t1;
-	ib_begin ();                                               /* forget them */
+	dspop_statsover* op = (dspop_statsover*) ctx;
+	return put_interval_figures (p, (const gdsp_interval_stat*) rec, s->start, op->originOne, op->sample.precision);
 	}
 
 void op_statsover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_complain(u32 vLen), arg_dont_complain(valtype* v))
 	{
 	dspop_statsover* op = (dspop_statsover*) _op;
-	char    line[1001], prevChrom[1001];
-	char*   chrom;
-	spec*   s = NULL;
-	u32     start, end, o = op->originOne? 1 : 0;
-	valtype val;
-	batch   b;
-	memset (&b, 0, sizeof(b));
-
-	const double tStart = now_ms ();
-	FILE* f = fopen (op->filename, "rt");
-	if (f == NULL) { fprintf (stderr, "[%s] can't open \"%s\" for reading\n", _op->name, op->filename);  exit (EXIT_FAILURE); }
-	FILE* out = open_table (_op->name, op->outFilename);
-	for (int i=0 ; chromsSorted[i]!=NULL ; i++) chromsSorted[i]->flag = false;
-
-	ib_begin ();
-	prevChrom[0] = 0;
-	while (read_interval (f, line, sizeof(line), /*valCol*/ -1, &chrom, &start, &end, &val))
-		{
-		if (strcmp (chrom, prevChrom) != 0)
-			{ s = find_chromosome_spec (chrom);  safe_strncpy (prevChrom, chrom, sizeof(prevChrom)-1); }
-		if (s == NULL) continue;
-		if (!s->flag) { if (trackOperations) fprintf (stderr, "%s(%s)\n", _op->name, chrom);  s->flag = true; }
-
-		const u32 fileStart = start;
-		start -= o;
-		u32 adjStart, adjEnd;
-		if (!place_interval (_op->name, op->filename, chrom, s, start, end, &adjStart, &adjEnd)) continue;
-		if (adjStart >= adjEnd) continue;                      /* (an empty interval has no sample and no line) */
-		const u64 serial = ib_pending ();
-		if (serial >= b.cap)
-			{
-			b.cap  = (b.cap == 0)? 4096 : 2*b.cap;
-			b.rows = (row*) must_alloc (realloc (b.rows, b.cap * sizeof(row)), _op->name);
-			b.rec  = (gdsp_interval_stat*) must_alloc (realloc (b.rec, b.cap * sizeof(gdsp_interval_stat)), _op->name);
-			}
-		b.rows[serial].s = s;  b.rows[serial].fileStart = fileStart;  b.rows[serial].fileEnd = end;
-		ib_add (s, adjStart, adjEnd, (valtype) serial);
-		op->bases += adjEnd - adjStart;
-		if (ib_pending () >= ib_batch_limit ()) flush_batch (op, &b, ib_pending (), out);
-		}
-	fclose (f);
-	flush_batch (op, &b, ib_pending (), out);
-	close_table (out);
+	interval_table t = { sizeof(gdsp_interval_stat), answer_stats, put_stats, 2200, NULL, op, 0, 0, 0, 0 };
+	interval_table_run (_op->name, op->filename, op->outFilename, op->originOne, &t);
+	op->bases += t.bases;
 	if (getenv ("GDSP_STATSOVER_TIMES") != NULL)
-		{
-		const double all = now_ms () - tStart;
-		fprintf (stderr, "[%s] times: %.1f ms = read and route %.1f + device calls %.1f + format and write %.1f\n", _op->name, all,
-		         all - op->msDevice - op->msFormat, op->msDevice, op->msFormat);
-		op->msDevice = op->msFormat = 0;
-		}
-	free (b.rows);  free (b.rec);  free (b.vec);  free (b.start);  free (b.end);  free (b.serial);  free (b.out);  free (b.text);
+		fprintf (stderr, "[%s] times: %.1f ms = read and route %.1f + device calls %.1f + format and write %.1f\n", _op->name, t.msAll,
+		         t.msAll - t.msDevice - t.msFormat, t.msDevice, t.msFormat);
 	}
 
 /* the driver: the signal is only read, 8 B per base of the intervals' summed length since the last call */

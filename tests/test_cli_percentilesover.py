@@ -215,6 +215,26 @@ def test_beyond_the_end_clipping_and_many_batches(driver, tmp_path):
 
 
 @pytest.mark.gpu
+def test_a_table_longer_than_the_text_buffer(driver, tmp_path):
+    """the lines of one batch are collected in a buffer of 1 MiB and written when the next line might not fit: a table of
+    several buffers is complete, in file order and the checker's byte for byte, to a file and to stdout"""
+    iv = coverage(51, True)
+    sig = signal(iv, tmp_path)
+    regs = so.short_regions(52)
+    ps = [0, 10000, 25000, 50000, 75000, 90000, 99999, 100000]
+    want = table(sig, regs, ps=ps)
+    assert len(want) > 3 << 19 and len(want.splitlines()) == 1 + len(regs) - 30
+    files = {"regions.bed": bed(regs)}
+    args = ["--nooutput", "=", "percentilesover", "regions.bed", "--percentiles=0,10,25,50,75,90,99.999,100"]
+    rc, out, err = cli(args + ["--output=table.tsv"], iv, tmp_path, files=files)
+    assert rc == 0 and out == "", err
+    got = read(tmp_path, "table.tsv")
+    assert got == want, [(g, w) for g, w in zip(got.splitlines(), want.splitlines()) if g != w][:3]
+    rc, out, err = cli(args, iv, tmp_path, files=files)
+    assert rc == 0 and out == want, err
+
+
+@pytest.mark.gpu
 def test_report_gpu_credits_the_bases(driver, tmp_path):
     iv = coverage(41)
     regs = [r for r in regions(42, 50) if r[0] != "chrZ"]

@@ -244,6 +244,48 @@ def test_beyond_the_end_and_many_batches(driver, tmp_path):
     assert [l.split("\t")[:3] for l in got] == [["chrA", "1500", "2600"], ["chrA", "2999", "5000"]]
 
 
+def eighths(seed):
+    """coverage's intervals with values that are eighths: every sum of them is exact, and the 17 decimals `signal` reads the
+    ingested signal back with name each base's double exactly, however small"""
+    rng = np.random.default_rng(seed)
+    lines = []
+    for c, n in CHROMS:
+        for _ in range(n // 25):
+            a = int(rng.integers(1000, n - 300))
+            lines.append("%s %d %d %.3f" % (c, a, a + int(rng.integers(1, 300)), round((rng.standard_normal() * 10 + 2) * 8) / 8))
+    return "\n".join(lines) + "\n"
+
+
+def short_regions(seed, count=30000):
+    """`count` intervals of 1 .. 20 bases anywhere on the genome, unsorted, a few on a chromosome the genome does not have"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k, ci in enumerate(rng.integers(0, 3, count).tolist()):
+        c, n = CHROMS[ci]
+        s = int(rng.integers(0, n - 1))
+        out.append(("chrZ" if k % 1000 == 999 else c, s, min(n, s + 1 + int(rng.integers(0, 20)))))
+    return out
+
+
+@pytest.mark.gpu
+def test_a_table_longer_than_the_text_buffer(driver, tmp_path):
+    """the lines of one batch are collected in a buffer of 1 MiB and written when the next line might not fit: a table of
+    several buffers is complete, in file order and the checker's byte for byte, to a file and to stdout"""
+    iv = eighths(51)
+    sig = signal(iv, tmp_path)
+    regs = short_regions(52)
+    want = table(sig, regs, precision=12)
+    assert len(want) > 2 << 20 and len(want.splitlines()) == len(regs) - 30
+    files = {"regions.bed": bed(regs)}
+    rc, out, err = cli(["--nooutput", "=", "statsover", "regions.bed", "--precision=12", "--output=table.tsv"], iv, tmp_path, files=files)
+    assert rc == 0 and out == "", err
+    with open(os.path.join(str(tmp_path), "table.tsv")) as f:
+        got = f.read()
+    assert got == want, [(g, w) for g, w in zip(got.splitlines(), want.splitlines()) if g != w][:3]
+    rc, out, err = cli(["--nooutput", "=", "statsover", "regions.bed", "--precision=12"], iv, tmp_path, files=files)
+    assert rc == 0 and out == want, err
+
+
 @pytest.mark.gpu
 def test_report_gpu_credits_the_bases(driver, tmp_path):
     iv = coverage(41)

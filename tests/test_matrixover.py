@@ -225,6 +225,33 @@ def test_a_cell_two_terms_cannot_hold_goes_to_the_host():
 
 
 @pytest.mark.gpu
+def test_host_cells_of_later_vectors_and_later_launches():
+    """the cells the host finishes lie on the second and the third of three vectors and, two rows a launch, in the third
+    launch and after it: each has to find its own vector, its own row there and its own interval"""
+    g = dev()
+    v = [depth(50, np.random.default_rng(3)), np.zeros(600), np.zeros(600)]
+    for x in v[1:]:
+        x[20:23] = [1e300, 1.0, 1e-300]
+        x[200:203] = [1e300, 1.0, 1e-300]
+    d = up(g, v)
+    for anchors, off_lo, noffsets, bin in (([(0, 3, 1), (1, 8, 1), (0, 40, -1), (2, 25, -1), (0, 0, 1), (1, 25, -1), (0, 49, -1), (2, 8, 1), (0, 20, 1), (1, 300, 1)], 0, 18, 3),
+                                           ([(0, 10, 1), (0, 30, -1), (2, 200, 1), (0, 45, 1), (1, 263, -1), (0, 5, -1), (1, 290, 1), (2, 263, -1), (0, 25, 1)], -64, 192, 64)):
+        whole = {name: g.genome_matrix(d, anchors, off_lo, noffsets, bin=bin, what=name) for name in ("sum", "mean")}
+        g.matrix_set_launch_rows(2)
+        try:
+            want = check(g, d, v, anchors, off_lo, noffsets, bin, what=("later", bin), host="some", figures=("sum", "mean"))
+            assert g.genome_matrix_last()["launches"] == (len(anchors) + 1) // 2
+            for name in ("sum", "mean"):
+                got = g.genome_matrix(d, anchors, off_lo, noffsets, bin=bin, what=name)
+                assert mref.same_bits(got, whole[name]), (bin, name)
+        finally:
+            g.matrix_set_launch_rows(0)
+        # the cells the host finished are on the vectors behind the first, whose five rows fill the first two launches
+        on = sorted({anchors[i][0] for i in np.argwhere(want["sum"] == 1e300)[:, 0]})
+        assert on == [1, 2], on
+
+
+@pytest.mark.gpu
 def test_depth_needs_no_host():
     """an integer sum below 2^53 is one double: nothing may be left to the host, whatever the figure and the route"""
     g = dev()

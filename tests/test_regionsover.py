@@ -247,6 +247,33 @@ def test_a_cell_two_terms_cannot_hold_goes_to_the_host():
 
 
 @pytest.mark.gpu
+def test_host_cells_of_later_vectors_and_later_launches():
+    """the cells the host finishes lie on the second and the third of three vectors and, two rows a launch, in the third
+    launch and after it: each has to find its own vector, its own row there and its own interval"""
+    g = dev()
+    v = [depth(50, np.random.default_rng(3)), np.zeros(600), np.zeros(600)]
+    for x in v[1:]:
+        x[20:23] = [1e300, 1.0, 1e-300]
+        x[200:203] = [1e300, 1.0, 1e-300]
+    d = up(g, v)
+    for regions, B, U, D, bin in (([(0, 3, 9, 1), (1, 14, 32, 1), (0, 30, 50, -1), (2, 11, 29, -1), (0, 0, 1, 1), (1, 11, 29, -1), (0, 40, 47, -1), (2, 14, 32, 1), (0, 20, 21, 1), (1, 300, 330, 1)], 6, 6, 6, 3),
+                                  ([(0, 10, 40, 1), (0, 0, 50, -1), (2, 180, 280, 1), (0, 45, 50, 1), (1, 150, 250, -1), (0, 5, 9, -1), (1, 290, 340, 1), (2, 150, 250, -1), (0, 25, 26, 1)], 2, 40, 40, 20)):
+        whole = {name: g.genome_regions(d, regions, B, U, D, bin, what=name) for name in ("sum", "mean")}
+        g.regions_set_launch_rows(2)
+        try:
+            want = check(g, d, v, regions, B, U, D, bin, what=("later", B, bin), host="some", figures=("sum", "mean"))
+            assert g.genome_regions_last()["launches"] == (len(regions) + 1) // 2
+            for name in ("sum", "mean"):
+                got = g.genome_regions(d, regions, B, U, D, bin, what=name)
+                assert rref.same_bits(got, whole[name]), (B, name)
+        finally:
+            g.regions_set_launch_rows(0)
+        # the cells the host finished are on the vectors behind the first, whose five rows fill the first two launches
+        on = sorted({regions[i][0] for i in np.argwhere(want["sum"] == 1e300)[:, 0]})
+        assert on == [1, 2], on
+
+
+@pytest.mark.gpu
 def test_depth_needs_no_host():
     """an integer sum below 2^53 is one double: nothing may be left to the host, whatever the figure and the route"""
     g = dev()
