@@ -1399,6 +1399,54 @@ def interval_percentiles_last():
     return dict(zip(("intervals", "short", "long", "passes", "batches", "ended_early"), [int(x) for x in out]))
 
 
+# ------------------------------------------------------ breadthover (not in the reference) ----
+
+def interval_breadth_tile():
+    """The tile the kernel cuts intervals at (values of the 16-byte aligned frame a vector lies in)."""
+    return int(lib().gdsp_interval_breadth_tile())
+
+
+def interval_breadth_set_launch_pieces(pieces=0):
+    """The most pieces of one launch; 0: the default.  For tests."""
+    call("gdsp_interval_breadth_set_launch_pieces", int(pieces))
+
+
+def interval_breadth(v, start, end, thresholds, strict=False, lo=-DBL_MAX, hi=DBL_MAX, stream=None, vec=None):
+    """The sample's size and, for every threshold T, the number of sampled bases with v >= T (v > T when strict) over the
+    intervals [start[i], end[i]) (gdsp_interval_breadth: statsover's sample, IEEE comparisons, integers throughout).
+    -> {"count": uint32[n], "atleast": uint32[n, len(thresholds)]} in the caller's order.  v: a DeviceVector or a
+    (vector, first, count) stretch of one; or a LIST of them with vec[i] naming interval i's vector
+    (gdsp_interval_breadth_batch).  Waits."""
+    vecs = v if isinstance(v, list) else [v]
+    items = _read_only_items(vecs)
+    start = np.ascontiguousarray(start, dtype=np.uint32)
+    end = np.ascontiguousarray(end, dtype=np.uint32)
+    assert start.shape == end.shape and start.ndim == 1
+    which = None if vec is None else np.ascontiguousarray(vec, dtype=np.uint32)
+    assert which is None or which.shape == start.shape
+    ts = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
+    count = np.zeros(start.size, np.uint32)
+    atleast = np.zeros((start.size, max(1, ts.size)), np.uint32)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    call("gdsp_interval_breadth_batch", items, len(vecs), vp(which), vp(start), vp(end), start.size, vp(ts), ts.size,
+         1 if strict else 0, float(lo), float(hi), vp(count), vp(atleast), _sp(stream))
+    return {"count": count, "atleast": atleast[:, :ts.size]}
+
+
+def interval_breadth_last():
+    """What the last interval_breadth did: intervals, pieces, launches, workgroups."""
+    out = (C.c_uint64 * 4)()
+    lib().gdsp_interval_breadth_last(out)
+    return dict(zip(("intervals", "pieces", "launches", "workgroups"), [int(x) for x in out]))
+
+
+def interval_breadth_times():
+    """Where the last interval_breadth's time went, in ms: cutting, the kernel (HIP events), copies and waiting, combining."""
+    ms = (C.c_double * 4)()
+    lib().gdsp_interval_breadth_times(ms)
+    return dict(zip(("ms_cut", "ms_kernel", "ms_copy", "ms_combine"), [float(x) for x in ms]))
+
+
 # ------------------------------------------------------- segments (not in the reference) ----
 
 RUN_PIECE = np.dtype([("vec", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32),

@@ -3,7 +3,7 @@
 //
 // Work is cut into PIECES: an interval intersected with a tile of IS_TILE values of the 16-byte aligned frame its vector
 // lies in.  The host sorts the pieces of a call by tile (a counting sort, the caller's order kept inside a tile) and cuts
-// every tile's list into ITEMS of at most IS_ITEM_PIECES pieces; a workgroup takes one item, so one 249 Mbp interval and
+// every tile's list into ITEMS of at most IC_ITEM_PIECES pieces; a workgroup takes one item, so one 249 Mbp interval and
 // a million intervals inside one tile both fill the device, and a tile no interval touches is never read.  The workgroup
 // brings the part of the tile its pieces cover into LDS with 16-byte loads, and its four waves take the pieces in turn:
 // a lane walks its piece with stride 64, keeps two 2-term TwoSum expansions (gdsp_xsum_dev.h: unchecked, a residual or
@@ -20,7 +20,8 @@
 // as its one source: adversarial data stays exact and gets slower.
 //
 // The staging buffers, the timing events, that second sum and the arithmetic on pieces are gdsp_pieces.h's, shared with
-// segments and keepsegments.
+// segments and keepsegments; the cut into pieces and items, their upload and the staging of an item's hull are
+// gdsp_interval_cut.h's, shared with breadthover.
 
 #include <float.h>
 #include <math.h>
@@ -30,61 +31,22 @@
 #include "gdsp_common.h"
 #include "gdsp_xsum_dev.h"
 #include "gdsp_pieces.h"
+#include "gdsp_interval_cut.h"
 
-#define IS_THREADS      256
-#define IS_WAVES        (IS_THREADS / 64)
-#define IS_TILE         4096                          // values: 32 KiB of LDS, five workgroups on a CU
-#define IS_ITEM_PIECES  64                            // pieces of one tile a workgroup takes
+#define IS_THREADS      IC_THREADS
+#define IS_WAVES        IC_WAVES
+#define IS_TILE         IC_TILE
 #define IS_CHUNK_PIECES (1u << 22)                    // pieces of one launch (records: 192 MiB); one interval has at most 2^20 + 1
 
 static_assert (sizeof(gdsp_interval_piece) == 48 && sizeof(gdsp_interval_stat) == 48, "the records of the header");
-static_assert (IS_TILE <= 65536 && IS_ITEM_PIECES <= 65535 && GDSP_BATCH_MAX <= 65535, "16-bit fields below");
-
-// one launch's table (the batch convention of gdsp_common.h): vector s is base[s][lead[s] .. lead[s]+n), base 16-byte aligned
-struct IsBatch
-	{
-	const double* base[GDSP_BATCH_MAX];
-	uint32_t      lead[GDSP_BATCH_MAX];
-	};
-
-// a workgroup's work: pieces [first, first+count) of the launch, all in tile `tile` of vector `vec`; together they cover
-// values [h0, h1) of the tile.  A piece is lo | (hi-1) << 16, values [lo, hi) of the tile.
-struct IsItem { uint32_t first, tile;  uint16_t count, vec, h0, h1m1; };
-static_assert (sizeof(IsItem) == 16, "loaded as one 16-byte word");
 
 __global__ __launch_bounds__(IS_THREADS)
-void interval_stats_kernel (IsBatch B, const uint4* __restrict__ items, const uint32_t* __restrict__ pieces, double lo, double hi,
+void interval_stats_kernel (IcBatch B, const uint4* __restrict__ items, const uint32_t* __restrict__ pieces, double lo, double hi,
                             gdsp_interval_piece* __restrict__ out)
 	{
 	__shared__ double tile[IS_TILE];
-	const uint4    raw   = items[blockIdx.x];
-	const uint32_t first = __builtin_amdgcn_readfirstlane (raw.x);
-	const uint32_t t     = __builtin_amdgcn_readfirstlane (raw.y);
-	const uint32_t cv    = __builtin_amdgcn_readfirstlane (raw.z);
-	const uint32_t hh    = __builtin_amdgcn_readfirstlane (raw.w);
-	const uint32_t count = cv & 0xFFFF, vec = cv >> 16;
-	const uint32_t h0    = hh & 0xFFFF, h1 = (hh >> 16) + 1;
-	const double*  base  = B.base[vec] + (uint64_t) t * IS_TILE;
-	const uint32_t pos0  = t * IS_TILE - B.lead[vec];          // the vector position of tile[0] (tile 0 behind a lead: tile[0] is in no piece)
-
-	// values [h0, h1) of the tile, whole 16-byte words first; the hull ends inside the vector, so an odd last value is
-	// loaded on its own (its word's other half may lie beyond the vector)
-	const uint32_t e0 = h0 & ~1u;
-	const uint32_t np = (h1 - e0) >> 1;
-	const double2* src = reinterpret_cast<const double2*> (base + e0);
-	double2*       dst = reinterpret_cast<double2*> (tile + e0);
-	for (uint32_t b0=0 ; b0<np ; b0+=GDSP_STAGE_DEPTH*IS_THREADS)
-		{
-		double2 r[GDSP_STAGE_DEPTH];
-#pragma unroll
-		for (int u=0 ; u<GDSP_STAGE_DEPTH ; u++)                // (every lane loads, index clamped: see gdsp_stage_f64)
-			{ const uint32_t p = b0 + u*IS_THREADS + threadIdx.x;  r[u] = src[(p < np)? p : np-1]; }
-#pragma unroll
-		for (int u=0 ; u<GDSP_STAGE_DEPTH ; u++)
-			{ const uint32_t p = b0 + u*IS_THREADS + threadIdx.x;  if (p < np) dst[p] = r[u]; }
-		}
-	if ((((h1 - e0) & 1) != 0) && (threadIdx.x == 0)) tile[h1-1] = base[h1-1];
-	__syncthreads ();
+	uint32_t first, count, pos0;
+	ic_stage_item (B, items, tile, first, count, pos0);
 
 	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	for (uint32_t k=wave ; k<count ; k+=IS_WAVES)
@@ -144,7 +106,7 @@ void interval_stats_kernel (IsBatch B, const uint4* __restrict__ items, const ui
 struct IsBuffers
 	{
 	GdspStaged<uint32_t> pieces;
-	GdspStaged<IsItem>   items;
+	GdspStaged<IcItem>   items;
 	GdspStaged<gdsp_interval_piece> out;
 	GdspStaged<uint64_t> img;
 	};
@@ -152,93 +114,24 @@ static IsBuffers isBuffers[64];
 static uint64_t  isLast[4];
 static double    isTimes[4];
 
-struct IsVector { const double* v;  uint32_t n, lead, tile0; };      // tile0: its first tile in the launch's numbering
-
-// the intervals sel[0 .. nsel) (indices into the caller's arrays; all on the vectors vecs[0 .. nvec) of this launch,
-// vector `vecBase + k` of the caller being vecs[k]), at most IS_CHUNK_PIECES pieces or one interval
-static int is_launch (IsBuffers& W, const IsVector* vecs, int nvec, int vecBase, uint32_t tiles, const uint32_t* sel, uint32_t nsel,
+// the intervals sel[0 .. nsel) of one launch (gdsp_interval_cut.h), at most IS_CHUNK_PIECES pieces or one interval
+static int is_launch (IsBuffers& W, const IcVector* vecs, int nvec, int vecBase, uint32_t tiles, const uint32_t* sel, uint32_t nsel,
                       const uint32_t* h_vec, const uint32_t* h_start, const uint32_t* h_end, double lo, double hi,
                       gdsp_interval_stat* h_out, int dev, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 	{
 	const GdspTimer tBin;
-
-	// pieces per tile and per interval
-	std::vector<uint32_t> tileFirst ((size_t) tiles + 1, 0), ivFirst ((size_t) nsel + 1, 0);
-	auto span = [&] (uint32_t i, const IsVector*& V, uint64_t& fs, uint64_t& fe)
-		{
-		V  = &vecs[((h_vec != NULL)? (int) h_vec[i] : 0) - vecBase];
-		fs = (uint64_t) h_start[i] + V->lead;  fe = (uint64_t) h_end[i] + V->lead;       // in the frame
-		};
-	for (uint32_t j=0 ; j<nsel ; j++)
-		{
-		const IsVector* V;  uint64_t fs, fe;
-		span (sel[j], V, fs, fe);
-		const uint32_t ts = (uint32_t) (fs / IS_TILE), te = (uint32_t) ((fe - 1) / IS_TILE);
-		for (uint32_t t=ts ; t<=te ; t++) tileFirst[V->tile0 + t + 1]++;
-		ivFirst[j+1] = ivFirst[j] + (te - ts + 1);
-		}
-	const uint32_t P = ivFirst[nsel];
-	uint32_t nitems = 0;
-	std::vector<uint32_t> itemBase (tiles, 0);
-	for (uint32_t g=0 ; g<tiles ; g++)
-		{
-		itemBase[g] = nitems;
-		nitems += (tileFirst[g+1] + IS_ITEM_PIECES - 1) / IS_ITEM_PIECES;
-		tileFirst[g+1] += tileFirst[g];
-		}
-	int rc = W.pieces.grow (P, "gdsp_interval_stats");
-	if (rc == GDSP_OK) rc = W.items.grow (nitems, "gdsp_interval_stats");
-	if (rc == GDSP_OK) rc = W.out.grow (P, "gdsp_interval_stats");
+	IcCut cut;
+	int rc = ic_cut ("gdsp_interval_stats", W.pieces, W.items, vecs, nvec, vecBase, tiles, sel, nsel, h_vec, h_start, h_end, cut);
+	if (rc == GDSP_OK) rc = W.out.grow (cut.P, "gdsp_interval_stats");
 	if (rc != GDSP_OK) return rc;
-
-	// the items of every tile that has pieces, their hulls still empty
-		{
-		int v = 0;
-		for (uint32_t g=0 ; g<tiles ; g++)
-			{
-			const uint32_t c = tileFirst[g+1] - tileFirst[g];
-			if (c == 0) continue;
-			while ((v+1 < nvec) && (vecs[v+1].tile0 <= g)) v++;
-			for (uint32_t k=0 ; k<c ; k+=IS_ITEM_PIECES)
-				{
-				IsItem& it = W.items.h[itemBase[g] + k / IS_ITEM_PIECES];
-				it.first = tileFirst[g] + k;  it.tile = g - vecs[v].tile0;
-				it.count = (uint16_t) std::min<uint32_t> (c - k, IS_ITEM_PIECES);  it.vec = (uint16_t) v;
-				it.h0 = 0xFFFF;  it.h1m1 = 0;
-				}
-			}
-		}
-	// the pieces, sorted by tile (the caller's order inside a tile); where each interval's pieces went
-	std::vector<uint32_t> cursor (tileFirst.begin (), tileFirst.end () - 1), ivPiece (P);
-	for (uint32_t j=0 ; j<nsel ; j++)
-		{
-		const IsVector* V;  uint64_t fs, fe;
-		span (sel[j], V, fs, fe);
-		const uint32_t ts = (uint32_t) (fs / IS_TILE), te = (uint32_t) ((fe - 1) / IS_TILE);
-		for (uint32_t t=ts ; t<=te ; t++)
-			{
-			const uint32_t g = V->tile0 + t;
-			const uint64_t t0 = (uint64_t) t * IS_TILE;
-			const uint32_t a = (uint32_t) (std::max (fs, t0) - t0), b = (uint32_t) (std::min (fe, t0 + IS_TILE) - t0);
-			const uint32_t pos = cursor[g]++;
-			W.pieces.h[pos] = a | ((b - 1) << 16);
-			ivPiece[ivFirst[j] + (t - ts)] = pos;
-			IsItem& it = W.items.h[itemBase[g] + (pos - tileFirst[g]) / IS_ITEM_PIECES];
-			it.h0   = (uint16_t) std::min<uint32_t> (it.h0, a);
-			it.h1m1 = (uint16_t) std::max<uint32_t> (it.h1m1, b - 1);
-			}
-		}
+	const std::vector<uint32_t> &tileFirst = cut.tileFirst, &ivFirst = cut.ivFirst, &ivPiece = cut.ivPiece;
+	const uint32_t P = cut.P, nitems = cut.nitems;
 	isTimes[0] += tBin.ms ();
 
 	const GdspTimer tDev;
-	IsBatch B;
-	for (int k=0 ; k<GDSP_BATCH_MAX ; k++)
-		{
-		B.base[k] = (k < nvec)? vecs[k].v - vecs[k].lead : NULL;
-		B.lead[k] = (k < nvec)? vecs[k].lead : 0;
-		}
-	GDSP_HIP_TRY (hipMemcpyAsync (W.pieces.d, W.pieces.h, (size_t) P * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (W.items.d, W.items.h, (size_t) nitems * sizeof(IsItem), hipMemcpyHostToDevice, s));
+	IcBatch B;
+	rc = ic_upload (B, vecs, nvec, W.pieces, W.items, cut, s);
+	if (rc != GDSP_OK) return rc;
 	GDSP_HIP_TRY (hipEventRecord (ev0, s));
 	hipLaunchKernelGGL (interval_stats_kernel, dim3(nitems), dim3(IS_THREADS), 0, s, B, reinterpret_cast<const uint4*> (W.items.d),
 	                    W.pieces.d, lo, hi, W.out.d);
@@ -379,59 +272,19 @@ int gdsp_interval_stats_batch (const gdsp_batch_item* items, int nitems, const u
 	memset (isLast, 0, sizeof(isLast));
 	for (int k=0 ; k<4 ; k++) isTimes[k] = 0;
 	if (count == 0) return GDSP_OK;
-	GDSP_REQUIRE ((h_start != NULL) && (h_end != NULL), "NULL interval arrays");
+	int rc = ic_check (__func__, items, nitems, h_vec, h_start, h_end, count);
+	if (rc != GDSP_OK) return rc;
 	GDSP_REQUIRE (h_out != NULL, "NULL result array");
-	GDSP_REQUIRE ((items != NULL) && (nitems > 0), "no vectors");
-	for (int k=0 ; k<nitems ; k++)
-		GDSP_REQUIRE ((items[k].n == 0) || ((items[k].d_in != NULL) && ((((uintptr_t) items[k].d_in) & 7) == 0)), "a vector must be 8-byte aligned");
-	for (uint32_t i=0 ; i<count ; i++)
-		{
-		const uint32_t v = (h_vec != NULL)? h_vec[i] : 0;
-		GDSP_REQUIRE (v < (uint32_t) nitems, "an interval names a vector beyond the table");
-		GDSP_REQUIRE (h_start[i] < h_end[i], "an interval must have start < end");
-		GDSP_REQUIRE (h_end[i] <= items[v].n, "an interval ends beyond its vector");
-		}
 	hipStream_t s = gdsp_stream (stream);
-	int dev = 0, rc = gdsp_device_slot (&dev);
+	int dev = 0;
+	rc = gdsp_device_slot (&dev);
 	if (rc != GDSP_OK) return rc;
 	GdspEventPair ev;
 	rc = ev.create ("gdsp_interval_stats");
-	std::vector<uint32_t> sel;
-	for (int v0=0 ; (v0<nitems) && (rc == GDSP_OK) ; v0+=GDSP_BATCH_MAX)         // a table of vectors at a time
-		{
-		const int nvec = std::min (GDSP_BATCH_MAX, nitems - v0);
-		IsVector vecs[GDSP_BATCH_MAX];
-		uint32_t tiles = 0;
-		for (int k=0 ; k<nvec ; k++)
-			{
-			vecs[k].v = items[v0+k].d_in;  vecs[k].n = items[v0+k].n;
-			vecs[k].lead  = (items[v0+k].n != 0)? gdsp_frame_lead (items[v0+k].d_in) : 0;
-			vecs[k].tile0 = tiles;
-			tiles += (uint32_t) gdsp_frame_tiles (vecs[k].n, vecs[k].lead, IS_TILE);
-			}
-		// the caller's order, cut where a launch is full
-		uint64_t pieces = 0;
-		sel.clear ();
-		for (uint32_t i=0 ; (i<=count) && (rc == GDSP_OK) ; i++)
-			{
-			uint64_t mine = 0;
-			if (i < count)
-				{
-				const int v = (h_vec != NULL)? (int) h_vec[i] : 0;
-				if ((v < v0) || (v >= v0 + nvec)) continue;
-				const uint64_t fs = (uint64_t) h_start[i] + vecs[v-v0].lead, fe = (uint64_t) h_end[i] + vecs[v-v0].lead;
-				mine = (fe - 1) / IS_TILE - fs / IS_TILE + 1;
-				}
-			if (!sel.empty () && ((i == count) || (pieces + mine > IS_CHUNK_PIECES)))
-				{
-				rc = is_launch (isBuffers[dev], vecs, nvec, v0, tiles, sel.data (), (uint32_t) sel.size (), h_vec, h_start, h_end, lo, hi,
-				                h_out, dev, s, ev.ev0, ev.ev1);
-				sel.clear ();  pieces = 0;
-				}
-			if (i < count) { sel.push_back (i);  pieces += mine; }
-			}
-		}
-	return rc;
+	if (rc != GDSP_OK) return rc;
+	return ic_for_each_launch (items, nitems, h_vec, h_start, h_end, count, IS_CHUNK_PIECES,
+		[&] (const IcVector* vecs, int nvec, int v0, uint32_t tiles, const uint32_t* sel, uint32_t nsel)
+			{ return is_launch (isBuffers[dev], vecs, nvec, v0, tiles, sel, nsel, h_vec, h_start, h_end, lo, hi, h_out, dev, s, ev.ev0, ev.ev1); });
 	}
 
 int gdsp_interval_stats (const double* d_v, uint32_t n, const uint32_t* h_start, const uint32_t* h_end, uint32_t count,

@@ -939,6 +939,41 @@ int  gdsp_interval_percentiles_set_batch (uint32_t longQueries);
  * before the last digit */
 void gdsp_interval_percentiles_last (uint64_t out[6]);
 
+/* ---- breadthover (not in the reference): bases at or above each depth threshold, per interval -----------------------
+ * The inverse of percentilesover's question: rank from value.  For a vector v of n doubles, an interval [s, e) with
+ * 0 <= s < e <= n, limits lo, hi, thresholds T_0 .. T_{q-1} (1 <= q <= GDSP_INTERVAL_THRESHOLDS_MAX) and a flag `strict`:
+ *   the sample is statsover's: the bases i in [s, e) with !(v[i] < lo) && !(v[i] > hi) and v[i] finite;
+ *   count      m, the number of sampled bases;
+ *   atleast_j  the number of sampled bases with v[i] >= T_j as IEEE compares them, or with v[i] > T_j when strict != 0;
+ *              -0.0 and +0.0 are equal.
+ * A threshold is any double that is not NaN, infinities included (T = -inf counts the whole sample, T = +inf nothing).
+ * Duplicate T_j are allowed, in any order, and answered in the order given.  Intervals may overlap, repeat and come in
+ * any order.  Every figure is an integer and a function of the interval's sample alone: nothing depends on tiles, grid,
+ * the split into launches, dispatch order, the order of the intervals or how they overlap, or devices.
+ *
+ * The conventions are gdsp_interval_percentiles[_batch]'s: HOST arrays in (GDSP_EINVAL, before the device is touched, for
+ * nt outside 1..16, a NaN threshold, start >= end, end > n, a vector index beyond the table, a misaligned vector and NULL
+ * arrays; count == 0 is a no-op), HOST arrays out in the caller's order -- h_count[i], and h_atleast[i*nt + j] for T_j --,
+ * vectors 8-byte aligned, the signal read on the current device and never written, and the call waits for the device.
+ * The device reduces statsover's pieces -- an interval cut at multiples of gdsp_interval_breadth_tile() values of the
+ * 16-byte aligned frame its vector lies in -- to integer records and the host adds an interval's records in 64 bits
+ * (gdsp_intervalbreadth.hip).  gdsp_interval_breadth_set_launch_pieces sets the most pieces of one launch (0: the
+ * default) so that a test can force several launches. */
+#define GDSP_INTERVAL_THRESHOLDS_MAX 16
+uint32_t gdsp_interval_breadth_tile (void);
+int gdsp_interval_breadth       (const double* d_v, uint32_t n, const uint32_t* h_start, const uint32_t* h_end, uint32_t count,
+                                 const double* thresholds, int nt, int strict, double lo, double hi,
+                                 uint32_t* h_count, uint32_t* h_atleast, void* stream);
+int gdsp_interval_breadth_batch (const gdsp_batch_item* items, int nitems, const uint32_t* h_vec, const uint32_t* h_start,
+                                 const uint32_t* h_end, uint32_t count, const double* thresholds, int nt, int strict,
+                                 double lo, double hi, uint32_t* h_count, uint32_t* h_atleast, void* stream);
+int  gdsp_interval_breadth_set_launch_pieces (uint32_t pieces);
+/* what the last gdsp_interval_breadth[_batch] did: [0] intervals, [1] pieces, [2] launches, [3] workgroups; and where its
+ * time went, in ms: [0] cutting the intervals into pieces (host), [1] the kernel (HIP events), [2] copies and waiting,
+ * [3] combining the pieces (host) */
+void gdsp_interval_breadth_last  (uint64_t out[4]);
+void gdsp_interval_breadth_times (double ms[4]);
+
 /* ---- segments (not in the reference): the signal's own thresholded regions, each with statsover's figures, exact ------
  * For a vector v of n doubles, a threshold T and tiesAbove:
  *   member   base i is a member iff v[i] > T, or v[i] >= T with ties above: binarize's test.  A NaN is never a member
