@@ -1309,11 +1309,12 @@ def _interval_figures(rec):
             "max": rec["max"].copy(), "maxpos": maxpos}
 
 
-def interval_stats(v, start, end, lo=-DBL_MAX, hi=DBL_MAX, stream=None, vec=None):
-    """count, sum, mean, min, max and maxpos of v over the intervals [start[i], end[i]) (gdsp_interval_stats: stats'
-    sample inside each interval, every figure exact and rounded once; NaN / -1 where the sample is empty).  -> dict of
-    numpy arrays in the caller's order.  v: a DeviceVector or a (vector, first, count) stretch of one; or a LIST of
-    them with vec[i] naming interval i's vector (gdsp_interval_stats_batch: one launch for all of them).  Waits."""
+def _vp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _interval_call(v, start, end, vec):
+    """interval_stats, interval_percentiles and interval_breadth open with it -> items, vectors, vec or None, start, end"""
     vecs = v if isinstance(v, list) else [v]
     items = _read_only_items(vecs)
     start = np.ascontiguousarray(start, dtype=np.uint32)
@@ -1321,10 +1322,23 @@ def interval_stats(v, start, end, lo=-DBL_MAX, hi=DBL_MAX, stream=None, vec=None
     assert start.shape == end.shape and start.ndim == 1
     which = None if vec is None else np.ascontiguousarray(vec, dtype=np.uint32)
     assert which is None or which.shape == start.shape
+    return items, len(vecs), which, start, end
+
+
+def interval_stats_set_launch_pieces(pieces=0):
+    """The most pieces of one launch; 0: the default.  For tests."""
+    call("gdsp_interval_stats_set_launch_pieces", int(pieces))
+
+
+def interval_stats(v, start, end, lo=-DBL_MAX, hi=DBL_MAX, stream=None, vec=None):
+    """count, sum, mean, min, max and maxpos of v over the intervals [start[i], end[i]) (gdsp_interval_stats: stats'
+    sample inside each interval, every figure exact and rounded once; NaN / -1 where the sample is empty).  -> dict of
+    numpy arrays in the caller's order.  v: a DeviceVector or a (vector, first, count) stretch of one; or a LIST of
+    them with vec[i] naming interval i's vector (gdsp_interval_stats_batch: one launch for all of them).  Waits."""
+    items, nvec, which, start, end = _interval_call(v, start, end, vec)
     rec = np.zeros(start.size, INTERVAL_STAT)
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    call("gdsp_interval_stats_batch", items, len(vecs), vp(which), vp(start), vp(end), start.size, float(lo), float(hi),
-         vp(rec), _sp(stream))
+    call("gdsp_interval_stats_batch", items, nvec, _vp(which), _vp(start), _vp(end), start.size, float(lo), float(hi),
+         _vp(rec), _sp(stream))
     return _interval_figures(rec)
 
 
@@ -1375,19 +1389,12 @@ def interval_percentiles(v, start, end, p_thousandths, lo=-DBL_MAX, hi=DBL_MAX, 
     sample is empty).  -> {"count": uint32[n], "values": float64[n, len(p_thousandths)]} in the caller's order.
     v: a DeviceVector or a (vector, first, count) stretch of one; or a LIST of them with vec[i] naming interval i's
     vector (gdsp_interval_percentiles_batch).  Waits."""
-    vecs = v if isinstance(v, list) else [v]
-    items = _read_only_items(vecs)
-    start = np.ascontiguousarray(start, dtype=np.uint32)
-    end = np.ascontiguousarray(end, dtype=np.uint32)
-    assert start.shape == end.shape and start.ndim == 1
-    which = None if vec is None else np.ascontiguousarray(vec, dtype=np.uint32)
-    assert which is None or which.shape == start.shape
+    items, nvec, which, start, end = _interval_call(v, start, end, vec)
     pcts = np.ascontiguousarray(np.atleast_1d(p_thousandths), dtype=np.uint32)
     count = np.zeros(start.size, np.uint32)
     values = np.zeros((start.size, max(1, pcts.size)), np.float64)
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    call("gdsp_interval_percentiles_batch", items, len(vecs), vp(which), vp(start), vp(end), start.size, vp(pcts), pcts.size,
-         float(lo), float(hi), vp(count), vp(values), _sp(stream))
+    call("gdsp_interval_percentiles_batch", items, nvec, _vp(which), _vp(start), _vp(end), start.size, _vp(pcts), pcts.size,
+         float(lo), float(hi), _vp(count), _vp(values), _sp(stream))
     return {"count": count, "values": values[:, :pcts.size]}
 
 
@@ -1417,19 +1424,12 @@ def interval_breadth(v, start, end, thresholds, strict=False, lo=-DBL_MAX, hi=DB
     -> {"count": uint32[n], "atleast": uint32[n, len(thresholds)]} in the caller's order.  v: a DeviceVector or a
     (vector, first, count) stretch of one; or a LIST of them with vec[i] naming interval i's vector
     (gdsp_interval_breadth_batch).  Waits."""
-    vecs = v if isinstance(v, list) else [v]
-    items = _read_only_items(vecs)
-    start = np.ascontiguousarray(start, dtype=np.uint32)
-    end = np.ascontiguousarray(end, dtype=np.uint32)
-    assert start.shape == end.shape and start.ndim == 1
-    which = None if vec is None else np.ascontiguousarray(vec, dtype=np.uint32)
-    assert which is None or which.shape == start.shape
+    items, nvec, which, start, end = _interval_call(v, start, end, vec)
     ts = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
     count = np.zeros(start.size, np.uint32)
     atleast = np.zeros((start.size, max(1, ts.size)), np.uint32)
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    call("gdsp_interval_breadth_batch", items, len(vecs), vp(which), vp(start), vp(end), start.size, vp(ts), ts.size,
-         1 if strict else 0, float(lo), float(hi), vp(count), vp(atleast), _sp(stream))
+    call("gdsp_interval_breadth_batch", items, nvec, _vp(which), _vp(start), _vp(end), start.size, _vp(ts), ts.size,
+         1 if strict else 0, float(lo), float(hi), _vp(count), _vp(atleast), _sp(stream))
     return {"count": count, "atleast": atleast[:, :ts.size]}
 
 

@@ -212,6 +212,7 @@ SIGNATURES = {
     "gdsp_genome_regions_last": (None, [_vp]),
     # statsover (not in the reference)
     "gdsp_interval_stats_tile": (_u32, []),
+    "gdsp_interval_stats_set_launch_pieces": (_int, [_u32]),
     "gdsp_interval_stats": (_int, [_vp, _u32, _vp, _vp, _u32, _f64, _f64, _vp, _vp]),
     "gdsp_interval_stats_batch": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _f64, _f64, _vp, _vp]),
     "gdsp_interval_stats_combine": (_int, [_vp, _u32, _vp, _vp]),

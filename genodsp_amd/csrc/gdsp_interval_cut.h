@@ -1,13 +1,15 @@
 // gdsp_interval_cut.h -- what the operators that reduce arbitrary intervals of a file piece by piece share
-// (gdsp_intervalstats.hip: statsover; gdsp_intervalbreadth.hip: breadthover): the refusals of a call, the walk over a
-// call's vectors a launch table at a time and over its intervals a launch at a time, the cut of a launch's intervals
-// into PIECES -- an interval intersected with a tile of IC_TILE values of the 16-byte aligned frame its vector lies in --,
-// their counting sort by tile (the caller's order kept inside a tile), the ITEMS of at most IC_ITEM_PIECES pieces of one
-// tile a workgroup takes, their upload, and on the device the decoding of an item and the staging of the part of the tile
-// its pieces cover.  What a wave does with a staged piece, the record it writes and how the host combines an interval's
-// records stay in the operators' files.
+// (gdsp_intervalstats.hip: statsover; gdsp_intervalbreadth.hip: breadthover): the refusals of a call (ic_check, which
+// percentilesover takes too), the walk over a call's vectors a launch table at a time and over its intervals a launch at
+// a time, the cut of a launch's intervals into PIECES -- an interval intersected with a tile of IC_TILE values of the
+// 16-byte aligned frame its vector lies in --, their counting sort by tile (the caller's order kept inside a tile), the
+// ITEMS of at most IC_ITEM_PIECES pieces of one tile a workgroup takes, their upload, on the device the decoding of an item
+// and the staging of the part of the tile its pieces cover, and (ic_run) everything a call and a launch do around the
+// kernel: buffers, report, events, copies, the wait, the timers.  What a wave does with a staged piece, the record it
+// writes, the start of its kernel and how the host combines an interval's records stay in the operators' files.
 #pragma once
 
+#include <string.h>
 #include <algorithm>
 #include <vector>
 #include "gdsp_common.h"
@@ -17,6 +19,7 @@
 #define IC_WAVES        (IC_THREADS / 64)
 #define IC_TILE         4096                          // values: 32 KiB of LDS, five workgroups on a CU
 #define IC_ITEM_PIECES  64                            // pieces of one tile a workgroup takes
+#define IC_LAUNCH_PIECES (1u << 22)                   // pieces of one launch by default; one interval has at most 2^20 + 1
 
 static_assert (IC_TILE <= 65536 && IC_ITEM_PIECES <= 65535 && GDSP_BATCH_MAX <= 65535, "16-bit fields below");
 
@@ -239,4 +242,82 @@ static inline int ic_for_each_launch (const gdsp_batch_item* items, int nitems, 
 			}
 		}
 	return rc;
+	}
+
+// ---------------------------------------------------------------------------------------------- launch ----
+// per device: staging and result buffers, grown on demand and kept; an operator derives from it what it adds
+template <typename Record>
+struct IcBuffers
+	{
+	GdspStaged<uint32_t> pieces;
+	GdspStaged<IcItem>   items;
+	GdspStaged<Record>   out;
+	};
+
+// what an operator's last call did: intervals, pieces and two counters of its own; ms spent cutting, in the kernel (HIP
+// events), copying and waiting, combining; and the most pieces of a launch (set by tests; 0: IC_LAUNCH_PIECES)
+struct IcReport { uint64_t last[4];  double ms[4];  uint32_t launchPieces; };
+
+// a launch as the operator's hooks see it: its vectors and their table, its intervals sel[0 .. nsel), its cut
+struct IcLaunch
+	{
+	const IcVector* vecs;  int nvec;  const uint32_t* sel;  uint32_t nsel;
+	IcBatch B;  IcCut cut;  int dev;  hipStream_t s;
+	};
+
+// a call, in the name of the entry point `entry` (buffers and events in the operator's name `who`): the refusals, then
+// launch by launch the cut, `recs` records of W.out per piece, the upload, the kernel between two events, the records'
+// way back and the wait.  The operator's hooks, each (W, launch) with W its buffers of this device:
+//   start   -> starts the kernel on launch.s (grid launch.cut.nitems);
+//   device  -> device work behind the records that counts as copy time, if any; GDSP_OK or what ends the call;
+//   combine -> the caller's results of the launch's intervals from the records in W.out.h (the combine timer); likewise
+template <typename Buffers, typename Start, typename Device, typename Combine>
+static inline int ic_run (const char* entry, const char* who, IcReport& rep, Buffers* perDevice, const gdsp_batch_item* items, int nitems,
+                          const uint32_t* h_vec, const uint32_t* h_start, const uint32_t* h_end, uint32_t count, size_t recs,
+                          void* stream, Start start, Device device, Combine combine)
+	{
+	memset (rep.last, 0, sizeof(rep.last));
+	for (int k=0 ; k<4 ; k++) rep.ms[k] = 0;
+	if (count == 0) return GDSP_OK;
+	int rc = ic_check (entry, items, nitems, h_vec, h_start, h_end, count);
+	if (rc != GDSP_OK) return rc;
+	IcLaunch L;
+	L.s = gdsp_stream (stream);
+	rc = gdsp_device_slot (&L.dev, entry);
+	if (rc != GDSP_OK) return rc;
+	GdspEventPair ev;
+	rc = ev.create (who);
+	if (rc != GDSP_OK) return rc;
+	Buffers& W = perDevice[L.dev];
+	return ic_for_each_launch (items, nitems, h_vec, h_start, h_end, count, (rep.launchPieces != 0)? rep.launchPieces : IC_LAUNCH_PIECES,
+		[&] (const IcVector* vecs, int nvec, int v0, uint32_t tiles, const uint32_t* sel, uint32_t nsel)
+			{
+			const GdspTimer tCut;
+			L.vecs = vecs;  L.nvec = nvec;  L.sel = sel;  L.nsel = nsel;
+			rc = ic_cut (who, W.pieces, W.items, vecs, nvec, v0, tiles, sel, nsel, h_vec, h_start, h_end, L.cut);
+			if (rc == GDSP_OK) rc = W.out.grow ((size_t) L.cut.P * recs, who);
+			if (rc != GDSP_OK) return rc;
+			rep.ms[0] += tCut.ms ();
+			const GdspTimer tDev;
+			rc = ic_upload (L.B, vecs, nvec, W.pieces, W.items, L.cut, L.s);
+			if (rc != GDSP_OK) return rc;
+			GDSP_HIP_TRY (hipEventRecord (ev.ev0, L.s));
+			start (W, L);
+			GDSP_LAUNCH_CHECK ();
+			GDSP_HIP_TRY (hipEventRecord (ev.ev1, L.s));
+			GDSP_HIP_TRY (hipMemcpyAsync (W.out.h, W.out.d, (size_t) L.cut.P * recs * sizeof(*W.out.h), hipMemcpyDeviceToHost, L.s));
+			GDSP_HIP_TRY (hipStreamSynchronize (L.s));
+			float kernelMs = 0;
+			GDSP_HIP_TRY (hipEventElapsedTime (&kernelMs, ev.ev0, ev.ev1));
+			rc = device (W, L);
+			if (rc != GDSP_OK) return rc;
+			rep.ms[1] += kernelMs;
+			rep.ms[2] += tDev.ms () - kernelMs;
+			const GdspTimer tCombine;
+			rc = combine (W, L);
+			if (rc != GDSP_OK) return rc;
+			rep.ms[3] += tCombine.ms ();
+			rep.last[0] += nsel;  rep.last[1] += L.cut.P;
+			return GDSP_OK;
+			});
 	}

@@ -19,6 +19,7 @@
 // integer: nothing depends on the cut, the grid or the dispatch order.
 //
 // The host adds an interval's pieces in 64-bit integers and gives the columns back in the caller's order of thresholds.
+// Everything a call and a launch do around the kernel is gdsp_interval_cut.h's (ic_run), shared with statsover.
 
 #include <float.h>
 #include <math.h>
@@ -29,8 +30,6 @@
 #include "gdsp_xsum_dev.h"
 #include "gdsp_pieces.h"
 #include "gdsp_interval_cut.h"
-
-#define IB_CHUNK_PIECES (1u << 22)                    // pieces of one launch (records: at most 272 MiB); one interval has at most 2^20 + 1
 
 struct IbThresholds { double t[GDSP_INTERVAL_THRESHOLDS_MAX]; };
 
@@ -87,17 +86,9 @@ void interval_breadth_kernel (IcBatch B, const uint4* __restrict__ items, const 
 	}
 
 // ---------------------------------------------------------------------------------------------- host ----
-// per device: staging and result buffers, grown on demand and kept
-struct IbBuffers
-	{
-	GdspStaged<uint32_t> pieces;
-	GdspStaged<IcItem>   items;
-	GdspStaged<uint32_t> out;
-	};
+typedef IcBuffers<uint32_t> IbBuffers;                // a piece's record: Q + 1 words (a launch's IC_LAUNCH_PIECES: at most 272 MiB)
 static IbBuffers ibBuffers[64];
-static uint64_t  ibLast[4];
-static double    ibTimes[4];
-static uint32_t  ibLaunchPieces = 0;                  // 0: IB_CHUNK_PIECES
+static IcReport  ibReport;                            // last: intervals, pieces, launches, workgroups
 
 // what a call asks of every launch: the thresholds as the kernel takes them and where each goes in the caller's order
 struct IbQuery
@@ -115,58 +106,36 @@ static void ib_start (const IbQuery& q, uint32_t nitems, hipStream_t s, const Ic
 	else               hipLaunchKernelGGL ((interval_breadth_kernel<Q, false>), dim3(nitems), dim3(IC_THREADS), 0, s, B, items, pieces, q.lo, q.hi, q.T, out);
 	}
 
-// the intervals sel[0 .. nsel) of one launch (gdsp_interval_cut.h)
-static int ib_launch (IbBuffers& W, const IcVector* vecs, int nvec, int vecBase, uint32_t tiles, const uint32_t* sel, uint32_t nsel,
-                      const uint32_t* h_vec, const uint32_t* h_start, const uint32_t* h_end, const IbQuery& q,
-                      uint32_t* h_count, uint32_t* h_atleast, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+static void ib_start_launch (const IbQuery& q, IbBuffers& W, const IcLaunch& L)
 	{
-	const GdspTimer tBin;
-	const size_t rec = (size_t) q.Q + 1;
-	IcCut cut;
-	int rc = ic_cut ("gdsp_interval_breadth", W.pieces, W.items, vecs, nvec, vecBase, tiles, sel, nsel, h_vec, h_start, h_end, cut);
-	if (rc == GDSP_OK) rc = W.out.grow ((size_t) cut.P * rec, "gdsp_interval_breadth");
-	if (rc != GDSP_OK) return rc;
-	ibTimes[0] += tBin.ms ();
-
-	const GdspTimer tDev;
-	IcBatch B;
-	rc = ic_upload (B, vecs, nvec, W.pieces, W.items, cut, s);
-	if (rc != GDSP_OK) return rc;
 	const uint4* items = reinterpret_cast<const uint4*> (W.items.d);
-	GDSP_HIP_TRY (hipEventRecord (ev0, s));
 	switch (q.Q)
 		{
-		case 1:  ib_start<1>  (q, cut.nitems, s, B, items, W.pieces.d, W.out.d);  break;
-		case 2:  ib_start<2>  (q, cut.nitems, s, B, items, W.pieces.d, W.out.d);  break;
-		case 4:  ib_start<4>  (q, cut.nitems, s, B, items, W.pieces.d, W.out.d);  break;
-		case 8:  ib_start<8>  (q, cut.nitems, s, B, items, W.pieces.d, W.out.d);  break;
-		default: ib_start<16> (q, cut.nitems, s, B, items, W.pieces.d, W.out.d);  break;
+		case 1:  ib_start<1>  (q, L.cut.nitems, L.s, L.B, items, W.pieces.d, W.out.d);  break;
+		case 2:  ib_start<2>  (q, L.cut.nitems, L.s, L.B, items, W.pieces.d, W.out.d);  break;
+		case 4:  ib_start<4>  (q, L.cut.nitems, L.s, L.B, items, W.pieces.d, W.out.d);  break;
+		case 8:  ib_start<8>  (q, L.cut.nitems, L.s, L.B, items, W.pieces.d, W.out.d);  break;
+		default: ib_start<16> (q, L.cut.nitems, L.s, L.B, items, W.pieces.d, W.out.d);  break;
 		}
-	GDSP_LAUNCH_CHECK ();
-	GDSP_HIP_TRY (hipEventRecord (ev1, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (W.out.h, W.out.d, (size_t) cut.P * rec * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-	GDSP_HIP_TRY (hipStreamSynchronize (s));
-	float kernelMs = 0;
-	GDSP_HIP_TRY (hipEventElapsedTime (&kernelMs, ev0, ev1));
-	ibTimes[1] += kernelMs;
-	ibTimes[2] += tDev.ms () - kernelMs;
+	}
 
-	// an interval's pieces, added in 64 bits (e - s <= 2^32 - 1 bounds every sum), into the caller's columns
-	const GdspTimer tCombine;
-	for (uint32_t j=0 ; j<nsel ; j++)
+// an interval's pieces, added in 64 bits (e - s <= 2^32 - 1 bounds every sum), into the caller's columns
+static int ib_combine (const IbQuery& q, IbBuffers& W, const IcLaunch& L, uint32_t* h_count, uint32_t* h_atleast)
+	{
+	const size_t rec = (size_t) q.Q + 1;
+	for (uint32_t j=0 ; j<L.nsel ; j++)
 		{
 		uint64_t sum[GDSP_INTERVAL_THRESHOLDS_MAX + 1] = { 0 };
-		for (uint32_t k=cut.ivFirst[j] ; k<cut.ivFirst[j+1] ; k++)
+		for (uint32_t k=L.cut.ivFirst[j] ; k<L.cut.ivFirst[j+1] ; k++)
 			{
-			const uint32_t* r = &W.out.h[(size_t) cut.ivPiece[k] * rec];
+			const uint32_t* r = &W.out.h[(size_t) L.cut.ivPiece[k] * rec];
 			for (int c=0 ; c<=q.nt ; c++) sum[c] += r[c];
 			}
-		const uint32_t i = sel[j];
+		const uint32_t i = L.sel[j];
 		h_count[i] = (uint32_t) sum[0];
 		for (int c=0 ; c<q.nt ; c++) h_atleast[(size_t) i * q.nt + q.column[c]] = (uint32_t) sum[1+c];
 		}
-	ibTimes[3] += tCombine.ms ();
-	ibLast[0] += nsel;  ibLast[1] += cut.P;  ibLast[2] += 1;  ibLast[3] += cut.nitems;
+	ibReport.last[2] += 1;  ibReport.last[3] += L.cut.nitems;
 	return GDSP_OK;
 	}
 
@@ -175,25 +144,16 @@ extern "C" {
 uint32_t gdsp_interval_breadth_tile (void) { return IC_TILE; }
 
 int gdsp_interval_breadth_set_launch_pieces (uint32_t pieces)
-	{
-	GDSP_REQUIRE (pieces <= IB_CHUNK_PIECES, "more pieces than a launch takes");
-	ibLaunchPieces = pieces;
-	return GDSP_OK;
-	}
+	{ GDSP_REQUIRE (pieces <= IC_LAUNCH_PIECES, "more pieces than a launch takes");  ibReport.launchPieces = pieces;  return GDSP_OK; }
 
 int gdsp_interval_breadth_batch (const gdsp_batch_item* items, int nitems, const uint32_t* h_vec, const uint32_t* h_start,
                                  const uint32_t* h_end, uint32_t count, const double* thresholds, int nt, int strict,
                                  double lo, double hi, uint32_t* h_count, uint32_t* h_atleast, void* stream)
 	{
-	memset (ibLast, 0, sizeof(ibLast));
-	for (int k=0 ; k<4 ; k++) ibTimes[k] = 0;
 	GDSP_REQUIRE ((nt >= 1) && (nt <= GDSP_INTERVAL_THRESHOLDS_MAX), "the number of thresholds must be in 1..16");
 	GDSP_REQUIRE (thresholds != NULL, "NULL thresholds");
 	for (int j=0 ; j<nt ; j++) GDSP_REQUIRE (thresholds[j] == thresholds[j], "a threshold is NaN");
-	if (count == 0) return GDSP_OK;
-	int rc = ic_check (__func__, items, nitems, h_vec, h_start, h_end, count);
-	if (rc != GDSP_OK) return rc;
-	GDSP_REQUIRE ((h_count != NULL) && (h_atleast != NULL), "NULL result arrays");
+	GDSP_REQUIRE ((count == 0) || ((h_count != NULL) && (h_atleast != NULL)), "NULL result arrays");
 
 	// ascending for the kernel (equal thresholds in the order given), padded with +inf; the caller's order kept
 	IbQuery q;
@@ -204,16 +164,10 @@ int gdsp_interval_breadth_batch (const gdsp_batch_item* items, int nitems, const
 	std::stable_sort (q.column, q.column + nt, [&] (int x, int y) { return thresholds[x] < thresholds[y]; });
 	for (int j=0 ; j<GDSP_INTERVAL_THRESHOLDS_MAX ; j++) q.T.t[j] = (j < nt)? thresholds[q.column[j]] : HUGE_VAL;
 
-	hipStream_t s = gdsp_stream (stream);
-	int dev = 0;
-	rc = gdsp_device_slot (&dev);
-	if (rc != GDSP_OK) return rc;
-	GdspEventPair ev;
-	rc = ev.create ("gdsp_interval_breadth");
-	if (rc != GDSP_OK) return rc;
-	return ic_for_each_launch (items, nitems, h_vec, h_start, h_end, count, (ibLaunchPieces != 0)? ibLaunchPieces : IB_CHUNK_PIECES,
-		[&] (const IcVector* vecs, int nvec, int v0, uint32_t tiles, const uint32_t* sel, uint32_t nsel)
-			{ return ib_launch (ibBuffers[dev], vecs, nvec, v0, tiles, sel, nsel, h_vec, h_start, h_end, q, h_count, h_atleast, s, ev.ev0, ev.ev1); });
+	return ic_run (__func__, "gdsp_interval_breadth", ibReport, ibBuffers, items, nitems, h_vec, h_start, h_end, count, (size_t) q.Q + 1, stream,
+		[&] (IbBuffers& W, const IcLaunch& L) { ib_start_launch (q, W, L); },
+		[] (IbBuffers&, const IcLaunch&) { return GDSP_OK; },
+		[&] (IbBuffers& W, const IcLaunch& L) { return ib_combine (q, W, L, h_count, h_atleast); });
 	}
 
 int gdsp_interval_breadth (const double* d_v, uint32_t n, const uint32_t* h_start, const uint32_t* h_end, uint32_t count,
@@ -225,7 +179,7 @@ int gdsp_interval_breadth (const double* d_v, uint32_t n, const uint32_t* h_star
 	return gdsp_interval_breadth_batch (&item, 1, NULL, h_start, h_end, count, thresholds, nt, strict, lo, hi, h_count, h_atleast, stream);
 	}
 
-void gdsp_interval_breadth_last  (uint64_t out[4]) { memcpy (out, ibLast, sizeof(ibLast)); }
-void gdsp_interval_breadth_times (double ms[4])    { memcpy (ms, ibTimes, sizeof(ibTimes)); }
+void gdsp_interval_breadth_last  (uint64_t out[4]) { memcpy (out, ibReport.last, sizeof(ibReport.last)); }
+void gdsp_interval_breadth_times (double ms[4])    { memcpy (ms, ibReport.ms, sizeof(ibReport.ms)); }
 
 } // extern "C"

@@ -27,6 +27,8 @@
 // leave at once in later passes (integer depth: three of six passes).  No workgroup waits for another.  The histograms
 // are IP_BINS 32-bit counts per query (an interval has at most 2^32 - 1 bases); a call with more long queries than the
 // workspace holds runs them in batches of whole intervals.
+// The refusals of a call's vectors and intervals are gdsp_interval_cut.h's (ic_check), shared with statsover and
+// breadthover; nothing else of that header is used here: these routes do not cut at frame tiles.
 
 #include <math.h>
 #include <string.h>
@@ -34,6 +36,7 @@
 #include <algorithm>
 #include "gdsp_common.h"
 #include "gdsp_pieces.h"
+#include "gdsp_interval_cut.h"
 #include "gdsp_rank_tile.h"
 
 #define IP_WAVE_MAX     512                           // bases one wave sorts
@@ -555,20 +558,12 @@ int gdsp_interval_percentiles_batch (const gdsp_batch_item* items, int nitems, c
 	GDSP_REQUIRE (pThousandths != NULL, "NULL percentiles");
 	for (int j=0 ; j<np ; j++) GDSP_REQUIRE (pThousandths[j] <= 100000, "a percentile is above 100000 thousandths");
 	if (count == 0) return GDSP_OK;
-	GDSP_REQUIRE ((h_start != NULL) && (h_end != NULL), "NULL interval arrays");
+	int rc = ic_check (__func__, items, nitems, h_vec, h_start, h_end, count);
+	if (rc != GDSP_OK) return rc;
 	GDSP_REQUIRE ((h_count != NULL) && (h_values != NULL), "NULL result array");
-	GDSP_REQUIRE ((items != NULL) && (nitems > 0), "no vectors");
-	for (int k=0 ; k<nitems ; k++)
-		GDSP_REQUIRE ((items[k].n == 0) || ((items[k].d_in != NULL) && ((((uintptr_t) items[k].d_in) & 7) == 0)), "a vector must be 8-byte aligned");
-	for (uint32_t i=0 ; i<count ; i++)
-		{
-		const uint32_t v = (h_vec != NULL)? h_vec[i] : 0;
-		GDSP_REQUIRE (v < (uint32_t) nitems, "an interval names a vector beyond the table");
-		GDSP_REQUIRE (h_start[i] < h_end[i], "an interval must have start < end");
-		GDSP_REQUIRE (h_end[i] <= items[v].n, "an interval ends beyond its vector");
-		}
 	hipStream_t s = gdsp_stream (stream);
-	int dev = 0, rc = gdsp_device_slot (&dev);
+	int dev = 0;
+	rc = gdsp_device_slot (&dev);
 	if (rc != GDSP_OK) return rc;
 	IpPcts P;
 	for (int j=0 ; j<GDSP_INTERVAL_PERCENTILES_MAX ; j++) P.p[j] = (j < np)? pThousandths[j] : 0;

@@ -20,8 +20,9 @@
 // as its one source: adversarial data stays exact and gets slower.
 //
 // The staging buffers, the timing events, that second sum and the arithmetic on pieces are gdsp_pieces.h's, shared with
-// segments and keepsegments; the cut into pieces and items, their upload and the staging of an item's hull are
-// gdsp_interval_cut.h's, shared with breadthover.
+// segments and keepsegments; the cut into pieces and items, the staging of an item's hull and everything a call and a
+// launch do around the kernel (ic_run) are gdsp_interval_cut.h's, shared with breadthover: this file keeps the kernel, its
+// start, the flagged pieces' second sum and the combine.
 
 #include <float.h>
 #include <math.h>
@@ -35,8 +36,7 @@
 
 #define IS_THREADS      IC_THREADS
 #define IS_WAVES        IC_WAVES
-#define IS_TILE         IC_TILE
-#define IS_CHUNK_PIECES (1u << 22)                    // pieces of one launch (records: 192 MiB); one interval has at most 2^20 + 1
+#define IS_TILE         IC_TILE                       // (a launch's IC_LAUNCH_PIECES records: 192 MiB)
 
 static_assert (sizeof(gdsp_interval_piece) == 48 && sizeof(gdsp_interval_stat) == 48, "the records of the header");
 
@@ -102,67 +102,34 @@ void interval_stats_kernel (IcBatch B, const uint4* __restrict__ items, const ui
 	}
 
 // ---------------------------------------------------------------------------------------------- host ----
-// per device: staging and result buffers, grown on demand and kept
-struct IsBuffers
-	{
-	GdspStaged<uint32_t> pieces;
-	GdspStaged<IcItem>   items;
-	GdspStaged<gdsp_interval_piece> out;
-	GdspStaged<uint64_t> img;
-	};
+// per device: the launch's buffers (gdsp_interval_cut.h) and the staging of the flagged pieces' second sum
+struct IsBuffers : IcBuffers<gdsp_interval_piece> { GdspStaged<uint64_t> img; };
 static IsBuffers isBuffers[64];
-static uint64_t  isLast[4];
-static double    isTimes[4];
+static IcReport  isReport;                            // last: intervals, pieces, flagged pieces, intervals rounded from the image
 
-// the intervals sel[0 .. nsel) of one launch (gdsp_interval_cut.h), at most IS_CHUNK_PIECES pieces or one interval
-static int is_launch (IsBuffers& W, const IcVector* vecs, int nvec, int vecBase, uint32_t tiles, const uint32_t* sel, uint32_t nsel,
-                      const uint32_t* h_vec, const uint32_t* h_start, const uint32_t* h_end, double lo, double hi,
-                      gdsp_interval_stat* h_out, int dev, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+// behind the records: each flagged piece is summed again as the one source of an exact pass
+static int is_flagged (IsBuffers& W, const IcLaunch& L, double lo, double hi, std::vector<uint32_t>& flagged, std::vector<uint64_t>& images)
 	{
-	const GdspTimer tBin;
-	IcCut cut;
-	int rc = ic_cut ("gdsp_interval_stats", W.pieces, W.items, vecs, nvec, vecBase, tiles, sel, nsel, h_vec, h_start, h_end, cut);
-	if (rc == GDSP_OK) rc = W.out.grow (cut.P, "gdsp_interval_stats");
-	if (rc != GDSP_OK) return rc;
-	const std::vector<uint32_t> &tileFirst = cut.tileFirst, &ivFirst = cut.ivFirst, &ivPiece = cut.ivPiece;
-	const uint32_t P = cut.P, nitems = cut.nitems;
-	isTimes[0] += tBin.ms ();
-
-	const GdspTimer tDev;
-	IcBatch B;
-	rc = ic_upload (B, vecs, nvec, W.pieces, W.items, cut, s);
-	if (rc != GDSP_OK) return rc;
-	GDSP_HIP_TRY (hipEventRecord (ev0, s));
-	hipLaunchKernelGGL (interval_stats_kernel, dim3(nitems), dim3(IS_THREADS), 0, s, B, reinterpret_cast<const uint4*> (W.items.d),
-	                    W.pieces.d, lo, hi, W.out.d);
-	GDSP_LAUNCH_CHECK ();
-	GDSP_HIP_TRY (hipEventRecord (ev1, s));
-	GDSP_HIP_TRY (hipMemcpyAsync (W.out.h, W.out.d, (size_t) P * sizeof(gdsp_interval_piece), hipMemcpyDeviceToHost, s));
-	GDSP_HIP_TRY (hipStreamSynchronize (s));
-	float kernelMs = 0;
-	GDSP_HIP_TRY (hipEventElapsedTime (&kernelMs, ev0, ev1));
-
-	// flagged pieces: each is summed again as the one source of an exact pass
-	std::vector<uint32_t> flagged;
-	std::vector<uint64_t> images;
 	auto stretchOf = [&] (uint32_t p)
 		{
-		const uint32_t g = (uint32_t) (std::upper_bound (tileFirst.begin (), tileFirst.end (), p) - tileFirst.begin ()) - 1;
+		const uint32_t g = (uint32_t) (std::upper_bound (L.cut.tileFirst.begin (), L.cut.tileFirst.end (), p) - L.cut.tileFirst.begin ()) - 1;
 		int v = 0;
-		while ((v+1 < nvec) && (vecs[v+1].tile0 <= g)) v++;
+		while ((v+1 < L.nvec) && (L.vecs[v+1].tile0 <= g)) v++;
 		const uint32_t a = W.pieces.h[p] & 0xFFFF, b = (W.pieces.h[p] >> 16) + 1;
-		return std::make_pair (B.base[v] + (uint64_t) (g - vecs[v].tile0) * IS_TILE + a, b - a);
+		return std::make_pair (L.B.base[v] + (uint64_t) (g - L.vecs[v].tile0) * IS_TILE + a, b - a);
 		};
-	rc = gdsp_flagged_images ("gdsp_interval_stats", P, [&] (uint32_t p) { return W.out.h[p].flag != 0; }, stretchOf, lo, hi,
-	                          W.img, dev, s, flagged, images);
-	if (rc != GDSP_OK) return rc;
-	isTimes[1] += kernelMs;
-	isTimes[2] += tDev.ms () - kernelMs;
+	return gdsp_flagged_images ("gdsp_interval_stats", L.cut.P, [&] (uint32_t p) { return W.out.h[p].flag != 0; }, stretchOf, lo, hi,
+	                            W.img, L.dev, L.s, flagged, images);
+	}
 
-	const GdspTimer tCombine;
+// the figures of the launch's intervals from their pieces' records
+static int is_combine (IsBuffers& W, const IcLaunch& L, const std::vector<uint32_t>& flagged, const std::vector<uint64_t>& images,
+                       gdsp_interval_stat* h_out)
+	{
+	const std::vector<uint32_t> &ivFirst = L.cut.ivFirst, &ivPiece = L.cut.ivPiece;
 	std::vector<gdsp_interval_piece> mine;
 	std::vector<uint64_t> mineImages;
-	for (uint32_t j=0 ; j<nsel ; j++)
+	for (uint32_t j=0 ; j<L.nsel ; j++)
 		{
 		const uint32_t np = ivFirst[j+1] - ivFirst[j];
 		const gdsp_interval_piece* pc = &W.out.h[ivPiece[ivFirst[j]]];
@@ -181,12 +148,11 @@ static int is_launch (IsBuffers& W, const IcVector* vecs, int nvec, int vecBase,
 			pc = mine.data ();
 			im = mineImages.empty ()? NULL : mineImages.data ();
 			}
-		rc = gdsp_interval_stats_combine (pc, np, im, &h_out[sel[j]]);
+		const int rc = gdsp_interval_stats_combine (pc, np, im, &h_out[L.sel[j]]);
 		if (rc != GDSP_OK) return rc;
-		isLast[3] += h_out[sel[j]].image;
+		isReport.last[3] += h_out[L.sel[j]].image;
 		}
-	isTimes[3] += tCombine.ms ();
-	isLast[0] += nsel;  isLast[1] += P;  isLast[2] += flagged.size ();
+	isReport.last[2] += flagged.size ();
 	return GDSP_OK;
 	}
 
@@ -269,23 +235,21 @@ int gdsp_interval_stats_combine (const gdsp_interval_piece* pieces, uint32_t npi
 int gdsp_interval_stats_batch (const gdsp_batch_item* items, int nitems, const uint32_t* h_vec, const uint32_t* h_start,
                                const uint32_t* h_end, uint32_t count, double lo, double hi, gdsp_interval_stat* h_out, void* stream)
 	{
-	memset (isLast, 0, sizeof(isLast));
-	for (int k=0 ; k<4 ; k++) isTimes[k] = 0;
-	if (count == 0) return GDSP_OK;
-	int rc = ic_check (__func__, items, nitems, h_vec, h_start, h_end, count);
-	if (rc != GDSP_OK) return rc;
-	GDSP_REQUIRE (h_out != NULL, "NULL result array");
-	hipStream_t s = gdsp_stream (stream);
-	int dev = 0;
-	rc = gdsp_device_slot (&dev);
-	if (rc != GDSP_OK) return rc;
-	GdspEventPair ev;
-	rc = ev.create ("gdsp_interval_stats");
-	if (rc != GDSP_OK) return rc;
-	return ic_for_each_launch (items, nitems, h_vec, h_start, h_end, count, IS_CHUNK_PIECES,
-		[&] (const IcVector* vecs, int nvec, int v0, uint32_t tiles, const uint32_t* sel, uint32_t nsel)
-			{ return is_launch (isBuffers[dev], vecs, nvec, v0, tiles, sel, nsel, h_vec, h_start, h_end, lo, hi, h_out, dev, s, ev.ev0, ev.ev1); });
+	GDSP_REQUIRE ((count == 0) || (h_out != NULL), "NULL result array");
+	std::vector<uint32_t> flagged;                    // the running launch's flagged pieces, and their images
+	std::vector<uint64_t> images;
+	return ic_run (__func__, "gdsp_interval_stats", isReport, isBuffers, items, nitems, h_vec, h_start, h_end, count, 1, stream,
+		[&] (IsBuffers& W, const IcLaunch& L)
+			{
+			hipLaunchKernelGGL (interval_stats_kernel, dim3(L.cut.nitems), dim3(IS_THREADS), 0, L.s, L.B, reinterpret_cast<const uint4*> (W.items.d),
+			                    W.pieces.d, lo, hi, W.out.d);
+			},
+		[&] (IsBuffers& W, const IcLaunch& L) { return is_flagged (W, L, lo, hi, flagged, images); },
+		[&] (IsBuffers& W, const IcLaunch& L) { return is_combine (W, L, flagged, images, h_out); });
 	}
+
+int gdsp_interval_stats_set_launch_pieces (uint32_t pieces)
+	{ GDSP_REQUIRE (pieces <= IC_LAUNCH_PIECES, "more pieces than a launch takes");  isReport.launchPieces = pieces;  return GDSP_OK; }
 
 int gdsp_interval_stats (const double* d_v, uint32_t n, const uint32_t* h_start, const uint32_t* h_end, uint32_t count,
                          double lo, double hi, gdsp_interval_stat* h_out, void* stream)
@@ -295,7 +259,7 @@ int gdsp_interval_stats (const double* d_v, uint32_t n, const uint32_t* h_start,
 	return gdsp_interval_stats_batch (&item, 1, NULL, h_start, h_end, count, lo, hi, h_out, stream);
 	}
 
-void gdsp_interval_stats_last  (uint64_t out[4]) { memcpy (out, isLast, sizeof(isLast)); }
-void gdsp_interval_stats_times (double ms[4])    { memcpy (ms, isTimes, sizeof(isTimes)); }
+void gdsp_interval_stats_last  (uint64_t out[4]) { memcpy (out, isReport.last, sizeof(isReport.last)); }
+void gdsp_interval_stats_times (double ms[4])    { memcpy (ms, isReport.ms, sizeof(isReport.ms)); }
 
 } // extern "C"

@@ -197,7 +197,7 @@ void  segments_run             (dspop* op, segments_opts* o, int wantTable, cons
 int   ib_chromosomes      (void);
 u32   ib_pending_of       (int ci, spec** s, u32** start, u32** end, valtype** val);
 char* put_value_fixed     (char* p, valtype v, int precision);
-/* what statsover and percentilesover share (ops_common.c): a table with one line per interval of a file, in file order --
+/* what statsover, percentilesover and breadthover share (ops_common.c): a table with one line per interval of a file, in file order --
  * chromosome, start and end as the file has them, then the operator's figures.  The file is read like mask's (read_interval
  * without a value column, place_interval), the intervals may overlap and come in any order; they are buffered with ib_add
  * and every ib_batch_limit() of them, and at the end of the file, each device answers those on its chromosomes in one call
@@ -216,6 +216,33 @@ typedef struct interval_table
 	double msAll, msDevice, msFormat;             /* the time of the run, of its device calls and of formatting and writing */
 	} interval_table;
 void  interval_table_run  (char* name, char* filename, char* outFilename, int originOne, interval_table* t);
+/* the head of those operators' control records, and what goes with it: the defaults; the options all of them take
+ * (--output=, --min= --max= --precision=, --origin=, --debug, the file's name, the complaint about anything else), asked
+ * after the operator has looked for its own; the complaints of the finished command line; the release of its strings;
+ * interval_table_run with the head's file names, the intervals' bases added to the head; and the work trait (the signal
+ * is only read, 8 B per base of the intervals' summed length since the last call) */
+typedef struct interval_op
+	{
+	dspop       common;
+	char*       filename;
+	char*       outFilename;
+	sample_opts sample;                           /* (its limits and precision; no window) */
+	int         originOne;
+	u64         bases;                            /* summed length of the intervals (--report=gpu) */
+	} interval_op;
+void  interval_op_init    (interval_op* h);
+void  interval_op_take    (interval_op* h, char* name, char* arg);
+void  interval_op_check   (interval_op* h, char* name);
+void  interval_op_free    (interval_op* h);
+void  interval_op_run     (interval_op* h, interval_table* t);
+void  interval_op_work    (dspop* op, u64* bases, double* bytesPerBase);
+/* the record percentilesover and breadthover keep of an interval: the size of its sample, a u32, and behind it n figures
+ * of elemSize bytes (4 or 8) each, the first elemSize bytes into the record.  new: room for k intervals' counts and
+ * figures as the library gives them; into: the k records at `out`, and the room is released */
+typedef struct counted_figures { u32* count;  void* figures;  size_t k, n, elemSize; } counted_figures;
+#define counted_figures_size(n, elemSize) (((size_t) (n) + 1) * (elemSize))
+counted_figures counted_figures_new  (char* name, size_t k, size_t n, size_t elemSize);
+void            counted_figures_into (counted_figures* f, void* out);
 /* ops_correlate.c (correlate), shared with ops_lagcorr.c: the intervals of a file, read
  * by the rules of `add <file>`, into every chromosome's partner -- what `add <file>` would leave on an all-zero genome */
 void  load_track_into_partners (char* name, char* filename, int valColumn, int originOne);

@@ -5,11 +5,12 @@
  * a pass per threshold; percentilesover answers the inverse question.  The signal is not modified and no variable is set.
  *
  * The file is read, the intervals are batched and the lines are written by the half shared with statsover and
- * percentilesover (interval_table_run, ops_common.c; host_services.h says how): the intervals may overlap and come in any
- * order, and every ib_batch_limit() of them, and at the end of the file, each device answers the intervals on its
- * chromosomes in one call (gdsp_interval_breadth_batch, include/genodsp_hip.h: every figure an integer, a function of the
- * interval's sample alone).  What is this operator's own is that call, the thresholds -- numbers, or variables fetched
- * when the operator runs --, the header with a column per threshold and the figures of a line.
+ * percentilesover, which also takes the options the three have in common (interval_table_run, interval_op: ops_common.c;
+ * host_services.h says how): the intervals may overlap and come in any order, and every ib_batch_limit() of them, and at
+ * the end of the file, each device answers the intervals on its chromosomes in one call (gdsp_interval_breadth_batch,
+ * include/genodsp_hip.h: every figure an integer, a function of the interval's sample alone).  What is this operator's
+ * own is that call, the thresholds -- numbers, or variables fetched when the operator runs --, the header with a column
+ * per threshold and the figures of a line.
  *
  * The driver finds this operator through opgroup_breadthover, at the end of this file (host_services.h); every call into
  * the device library for it stays here. */
@@ -27,18 +28,13 @@ dspprototypes(op_breadthover)
 
 typedef struct dspop_breadthover
 	{
-	dspop       common;
-	char*       filename;
-	char*       outFilename;
-	sample_opts sample;                         /* (its limits and precision; no window) */
-	int         originOne;
+	interval_op head;
 	int         tiesAbove;                      /* a base equal to the threshold counts ("at least"): the default */
 	int         asFraction;
 	valtype     thresholds[GDSP_INTERVAL_THRESHOLDS_MAX];   /* in the order given */
 	char*       varNames[GDSP_INTERVAL_THRESHOLDS_MAX];     /* those still to be fetched (resolve_variable) */
 	char*       labels[GDSP_INTERVAL_THRESHOLDS_MAX];       /* as the user spelled them */
 	int         numThresholds;
-	u64         bases;                          /* summed length of the intervals (--report=gpu) */
 	} dspop_breadthover;
 
 static void op_breadthover_usage_text (char* name, FILE* f, char* indent)
@@ -92,16 +88,13 @@ static void take_thresholds (dspop_breadthover* op, char* name, char* arg, char*
 dspop* op_breadthover_parse (char* name, int argc, char** argv)
 	{
 	dspop_breadthover* op = (dspop_breadthover*) new_op (name, sizeof(dspop_breadthover), true);
-	sample_opts_init (&op->sample);
-	op->originOne = (int) get_named_global ("originOne", false);
+	interval_op_init (&op->head);
 	op->tiesAbove = true;
 	take_thresholds (op, name, (char*) "--thresholds=1", (char*) "1");
 	for ( ; argc > 0 ; argv++, argc--)
 		{
 		char* arg = argv[0];
 		char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
-		if (strcmp_prefix (arg, "--output=") == 0)
-			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
 		if ((strcmp_prefix (arg, "--thresholds=") == 0) || (strcmp_prefix (arg, "--threshold=") == 0))
 			{ take_thresholds (op, name, arg, argVal);  continue; }
 		if ((strcmp (arg, "--ties:above") == 0) || (strcmp (arg, "--ties=above") == 0)) { op->tiesAbove = true;   continue; }
@@ -113,49 +106,34 @@ dspop* op_breadthover_parse (char* name, int argc, char** argv)
 			else chastise ("[%s] --as= takes count or fraction (\"%s\")\n", name, arg);
 			continue;
 			}
-		if (sample_opts_take (&op->sample, name, arg, SAMPLE_OPT_PRECISION)) continue;
-		if (origin_opt_take (arg, &op->originOne)) continue;
-		if (strcmp (arg, "--debug") == 0) continue;
-		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
-		if (op->filename == NULL) { op->filename = copy_string (arg);  continue; }
-		chastise ("[%s] Can't understand \"%s\"\n", name, arg);
+		interval_op_take (&op->head, name, arg);
 		}
-	if (op->filename == NULL) { fprintf (stderr, "[%s] no filename was provided\n", name);  exit (EXIT_FAILURE); }
-	if (op->sample.minAllowed > op->sample.maxAllowed) chastise ("[%s] --min can't be above --max\n", name);
+	interval_op_check (&op->head, name);
 	return (dspop*) op;
 	}
 
-void op_breadthover_free (dspop* _op)
+void op_breadthover_free (dspop* op)
 	{
-	dspop_breadthover* op = (dspop_breadthover*) _op;
-	forget_thresholds (op);
-	if (op->filename    != NULL) free (op->filename);
-	if (op->outFilename != NULL) free (op->outFilename);
+	forget_thresholds ((dspop_breadthover*) op);
+	interval_op_free ((interval_op*) op);
 	free (op);
 	}
 
 /* ------------------------------------------------------------------------------------- the table's figures ---- */
 /* what is kept of an interval: the size of its sample and, in the order asked for, its numThresholds counts */
 typedef struct breadthrec { u32 count;  u32 atleast[]; } breadthrec;
-#define breadthrec_size(nt) (sizeof(breadthrec) + (size_t) (nt) * sizeof(u32))
+#define breadthrec_size(nt) counted_figures_size (nt, sizeof(u32))
+_Static_assert (__builtin_offsetof (breadthrec, count) == 0 && __builtin_offsetof (breadthrec, atleast) == sizeof(u32), "counted_figures' record");
 
 /* one device's share in one call */
 static void answer_breadth (void* ctx, gdsp_batch_item* items, int m, u32* vec, u32* start, u32* end, u32 k, void* out)
 	{
 	dspop_breadthover* op = (dspop_breadthover*) ctx;
-	char*        name = op->common.name;
-	const size_t nt = (size_t) op->numThresholds;
-	u32* count   = (u32*) must_alloc (malloc (k * sizeof(u32)), name);
-	u32* atleast = (u32*) must_alloc (malloc (k * nt * sizeof(u32)), name);
+	char* name = op->head.common.name;
+	counted_figures f = counted_figures_new (name, k, (size_t) op->numThresholds, sizeof(u32));
 	check_gdsp (gdsp_interval_breadth_batch (items, m, vec, start, end, k, op->thresholds, op->numThresholds, !op->tiesAbove,
-	                                         op->sample.minAllowed, op->sample.maxAllowed, count, atleast, op_stream ()), name);
-	for (size_t i=0 ; i<k ; i++)
-		{
-		breadthrec* r = (breadthrec*) ((char*) out + i * breadthrec_size (nt));
-		r->count = count[i];
-		memcpy (r->atleast, &atleast[i * nt], nt * sizeof(u32));
-		}
-	free (count);  free (atleast);
+	                                         op->head.sample.minAllowed, op->head.sample.maxAllowed, f.count, (u32*) f.figures, op_stream ()), name);
+	counted_figures_into (&f, out);
 	}
 
 /* a line: the name, two coordinates and the count (at most 20 digits each), nt figures of at most 400 characters, tabs */
@@ -172,7 +150,7 @@ static char* put_breadth (void* ctx, char* p, const void* rec, arg_dont_complain
 		*(p++) = '\t';
 		if      (!op->asFraction) p = put_unsigned (p, r->atleast[j]);
 		else if (r->count == 0)   { *(p++) = 'N';  *(p++) = 'A'; }
-		else                      p = put_value (p, (double) r->atleast[j] / (double) r->count, op->sample.precision);   /* one IEEE division */
+		else                      p = put_value (p, (double) r->atleast[j] / (double) r->count, op->head.sample.precision);   /* one IEEE division */
 		}
 	*(p++) = '\n';
 	return p;
@@ -196,13 +174,8 @@ void op_breadthover_apply (dspop* _op, arg_dont_complain(char* vName), arg_dont_
 		if (op->thresholds[j] != op->thresholds[j]) chastise ("[%s] threshold %s is not a number\n", _op->name, op->labels[j]);
 		}
 	interval_table t = { breadthrec_size (op->numThresholds), answer_breadth, put_breadth, breadth_line_max (op->numThresholds), put_header, op, 0, 0, 0, 0 };
-	interval_table_run (_op->name, op->filename, op->outFilename, op->originOne, &t);
-	op->bases += t.bases;
+	interval_op_run (&op->head, &t);
 	}
-
-/* the driver: the signal is only read, 8 B per base of the intervals' summed length since the last call */
-static void breadthover_work (dspop* op, u64* bases, double* bytesPerBase)
-	{ *bases = ((dspop_breadthover*) op)->bases;  ((dspop_breadthover*) op)->bases = 0;  *bytesPerBase = 8; }
 
 OP_SHORT (op_breadthover, "print the bases at or above each threshold over each interval of a file (not in genodsp)")
 void op_breadthover_usage (char* name, FILE* f, char* indent) { op_breadthover_usage_text (name, f, indent); }
@@ -210,5 +183,5 @@ void op_breadthover_usage (char* name, FILE* f, char* indent) { op_breadthover_u
 static const dspinfo breadthoverRows[] =
 	{ dspinforecord("breadthover", op_breadthover), dspinfoalias ("breadth_over"), dspinfoalias ("coverageover"),
 	  dspinfoalias ("coverage_over"), dspinfoalias ("thresholdsover") };
-static const optraits breadthoverTraits[] = { { op_breadthover_apply, true, false, NULL, NULL, breadthover_work } };
+static const optraits breadthoverTraits[] = { { op_breadthover_apply, true, false, NULL, NULL, interval_op_work } };
 const opgroup opgroup_breadthover = OPGROUP (breadthoverRows, breadthoverTraits, NULL);

@@ -499,7 +499,7 @@ void row_table_report (char* rowsName, u64 numUsed, u64 cells, int quiet)
 	if (!quiet) fprintf (stderr, "%s is %llu, cells is %llu\n", rowsName, (unsigned long long) numUsed, (unsigned long long) cells);
 	}
 
-/* ------------------------------------ a table with one line per interval of a file (statsover, percentilesover) ---- */
+/* ----------------------- a table with one line per interval of a file (statsover, percentilesover, breadthover) ---- */
 /* a kept interval as its line names it; its record arrives in rec under the same serial number */
 typedef struct itrow { spec* s;  u32 fileStart, fileEnd; } itrow;
 
@@ -633,4 +633,62 @@ void interval_table_run (char* name, char* filename, char* outFilename, int orig
 	close_table (out);
 	t->msAll += now_ms () - tStart;
 	free (b.rows);  free (b.rec);  free (b.vec);  free (b.start);  free (b.end);  free (b.serial);  free (b.out);  free (b.text);
+	}
+
+/* the head the operators of such a table embed (host_services.h) */
+void interval_op_init (interval_op* h)
+	{
+	sample_opts_init (&h->sample);
+	h->originOne = (int) get_named_global ("originOne", false);
+	}
+
+void interval_op_take (interval_op* h, char* name, char* arg)
+	{
+	if (strcmp_prefix (arg, "--output=") == 0)
+		{ if (h->outFilename != NULL) free (h->outFilename);  h->outFilename = copy_string (strchr (arg, '=') + 1);  return; }
+	if (sample_opts_take (&h->sample, name, arg, SAMPLE_OPT_PRECISION)) return;
+	if (origin_opt_take (arg, &h->originOne)) return;
+	if (strcmp (arg, "--debug") == 0) return;
+	if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
+	if (h->filename == NULL) { h->filename = copy_string (arg);  return; }
+	chastise ("[%s] Can't understand \"%s\"\n", name, arg);
+	}
+
+void interval_op_check (interval_op* h, char* name)
+	{
+	if (h->filename == NULL) { fprintf (stderr, "[%s] no filename was provided\n", name);  exit (EXIT_FAILURE); }
+	if (h->sample.minAllowed > h->sample.maxAllowed) chastise ("[%s] --min can't be above --max\n", name);
+	}
+
+void interval_op_free (interval_op* h)
+	{
+	if (h->filename    != NULL) free (h->filename);
+	if (h->outFilename != NULL) free (h->outFilename);
+	}
+
+void interval_op_run (interval_op* h, interval_table* t)
+	{
+	interval_table_run (h->common.name, h->filename, h->outFilename, h->originOne, t);
+	h->bases += t->bases;
+	}
+
+void interval_op_work (dspop* op, u64* bases, double* bytesPerBase)
+	{ *bases = ((interval_op*) op)->bases;  ((interval_op*) op)->bases = 0;  *bytesPerBase = 8; }
+
+counted_figures counted_figures_new (char* name, size_t k, size_t n, size_t elemSize)
+	{
+	counted_figures f = { (u32*) must_alloc (malloc (k * sizeof(u32)), name), must_alloc (malloc (k * n * elemSize), name), k, n, elemSize };
+	return f;
+	}
+
+void counted_figures_into (counted_figures* f, void* out)
+	{
+	const size_t bytes = f->n * f->elemSize;
+	for (size_t i=0 ; i<f->k ; i++)
+		{
+		char* r = (char*) out + i * counted_figures_size (f->n, f->elemSize);
+		*(u32*) r = f->count[i];
+		memcpy (r + f->elemSize, (char*) f->figures + i * bytes, bytes);
+		}
+	free (f->count);  free (f->figures);
 	}

@@ -4,12 +4,13 @@
  * reads does not drag).  What statsover leaves out, since it takes more than one reduction per interval.  The signal is
  * not modified and no variable is set.  The two operators differ in name only: both default to --percentiles=50.
  *
- * The file is read, the intervals are batched and the lines are written by the half shared with statsover
- * (interval_table_run, ops_common.c; host_services.h says how): the intervals may overlap and come in any order, and every
- * ib_batch_limit() of them, and at the end of the file, each device answers the intervals on its chromosomes in one call
- * (gdsp_interval_percentiles_batch, include/genodsp_hip.h: every value an input value, a function of the interval's sample
- * alone).  What is these operators' own is that call, the header with a column per percentile and the values of a line,
- * NA where the sample is empty.
+ * The file is read, the intervals are batched and the lines are written by the half shared with statsover and
+ * breadthover, which also takes the options the three have in common (interval_table_run, interval_op: ops_common.c;
+ * host_services.h says how): the intervals may overlap and come in any order, and every ib_batch_limit() of them, and at
+ * the end of the file, each device answers the intervals on its chromosomes in one call (gdsp_interval_percentiles_batch,
+ * include/genodsp_hip.h: every value an input value, a function of the interval's sample alone).  What is these
+ * operators' own is that call, the header with a column per percentile and the values of a line, NA where the sample is
+ * empty.
  *
  * The driver finds these operators through opgroup_percentilesover, at the end of this file (host_services.h); every call
  * into the device library for them stays here. */
@@ -27,14 +28,9 @@ dspprototypes(op_percentilesover)  dspprototypes(op_medianover)
 
 typedef struct dspop_percentilesover
 	{
-	dspop       common;
-	char*       filename;
-	char*       outFilename;
-	sample_opts sample;                         /* (its limits and precision; no window) */
-	int         originOne;
+	interval_op head;
 	u32         pcts[GDSP_INTERVAL_PERCENTILES_MAX];   /* thousandths of a percent, in the order given */
 	int         numPcts;
-	u64         bases;                          /* summed length of the intervals (--report=gpu) */
 	} dspop_percentilesover;
 
 static void percentilesover_usage (char* name, FILE* f, char* indent)
@@ -75,59 +71,41 @@ static void take_percentiles (dspop_percentilesover* op, char* name, char* arg, 
 static dspop* percentilesover_parse (char* name, int argc, char** argv)
 	{
 	dspop_percentilesover* op = (dspop_percentilesover*) new_op (name, sizeof(dspop_percentilesover), true);
-	sample_opts_init (&op->sample);
-	op->originOne = (int) get_named_global ("originOne", false);
+	interval_op_init (&op->head);
 	op->pcts[0] = 50000;  op->numPcts = 1;
 	for ( ; argc > 0 ; argv++, argc--)
 		{
 		char* arg = argv[0];
-		char* argVal = strchr (arg, '=');  if (argVal != NULL) argVal++;
-		if (strcmp_prefix (arg, "--output=") == 0)
-			{ if (op->outFilename != NULL) free (op->outFilename);  op->outFilename = copy_string (argVal);  continue; }
 		if ((strcmp_prefix (arg, "--percentiles=") == 0) || (strcmp_prefix (arg, "--percentile=") == 0))
-			{ take_percentiles (op, name, arg, argVal);  continue; }
-		if (sample_opts_take (&op->sample, name, arg, SAMPLE_OPT_PRECISION)) continue;
-		if (origin_opt_take (arg, &op->originOne)) continue;
-		if (strcmp (arg, "--debug") == 0) continue;
-		if (strcmp_prefix (arg, "--") == 0) chastise ("[%s] Can't understand \"%s\"\n", name, arg);
-		if (op->filename == NULL) { op->filename = copy_string (arg);  continue; }
-		chastise ("[%s] Can't understand \"%s\"\n", name, arg);
+			take_percentiles (op, name, arg, strchr (arg, '=') + 1);
+		else
+			interval_op_take (&op->head, name, arg);
 		}
-	if (op->filename == NULL) { fprintf (stderr, "[%s] no filename was provided\n", name);  exit (EXIT_FAILURE); }
-	if (op->sample.minAllowed > op->sample.maxAllowed) chastise ("[%s] --min can't be above --max\n", name);
+	interval_op_check (&op->head, name);
 	return (dspop*) op;
 	}
 
-static void percentilesover_free (dspop* _op)
+static void percentilesover_free (dspop* op)
 	{
-	dspop_percentilesover* op = (dspop_percentilesover*) _op;
-	if (op->filename    != NULL) free (op->filename);
-	if (op->outFilename != NULL) free (op->outFilename);
+	interval_op_free ((interval_op*) op);
 	free (op);
 	}
 
 /* ------------------------------------------------------------------------------------- the table's figures ---- */
 /* what is kept of an interval: the size of its sample and, in the order asked for, its numPcts percentiles */
 typedef struct pctrec { u32 count;  double values[]; } pctrec;
-#define pctrec_size(np) (sizeof(pctrec) + (size_t) (np) * sizeof(double))
+#define pctrec_size(np) counted_figures_size (np, sizeof(double))
+_Static_assert (__builtin_offsetof (pctrec, count) == 0 && __builtin_offsetof (pctrec, values) == sizeof(double), "counted_figures' record");
 
 /* one device's share in one call */
 static void answer_percentiles (void* ctx, gdsp_batch_item* items, int m, u32* vec, u32* start, u32* end, u32 k, void* out)
 	{
 	dspop_percentilesover* op = (dspop_percentilesover*) ctx;
-	char*        name = op->common.name;
-	const size_t np = (size_t) op->numPcts;
-	u32*    count  = (u32*) must_alloc (malloc (k * sizeof(u32)), name);
-	double* values = (double*) must_alloc (malloc (k * np * sizeof(double)), name);
-	check_gdsp (gdsp_interval_percentiles_batch (items, m, vec, start, end, k, op->pcts, op->numPcts, op->sample.minAllowed,
-	                                             op->sample.maxAllowed, count, values, op_stream ()), name);
-	for (size_t i=0 ; i<k ; i++)
-		{
-		pctrec* r = (pctrec*) ((char*) out + i * pctrec_size (np));
-		r->count = count[i];
-		memcpy (r->values, &values[i * np], np * sizeof(double));
-		}
-	free (count);  free (values);
+	char* name = op->head.common.name;
+	counted_figures f = counted_figures_new (name, k, (size_t) op->numPcts, sizeof(double));
+	check_gdsp (gdsp_interval_percentiles_batch (items, m, vec, start, end, k, op->pcts, op->numPcts, op->head.sample.minAllowed,
+	                                             op->head.sample.maxAllowed, f.count, (double*) f.figures, op_stream ()), name);
+	counted_figures_into (&f, out);
 	}
 
 /* a line: the name, two coordinates and the count (at most 20 digits each), np values of at most 400 characters, tabs */
@@ -144,7 +122,7 @@ static char* put_percentiles (void* ctx, char* p, const void* rec, arg_dont_comp
 		const double x = r->values[j];
 		*(p++) = '\t';
 		if (isnan (x)) { *(p++) = 'N';  *(p++) = 'A'; }
-		else           p = put_value (p, x, op->sample.precision);
+		else           p = put_value (p, x, op->head.sample.precision);
 		}
 	*(p++) = '\n';
 	return p;
@@ -168,15 +146,10 @@ static void percentilesover_apply (dspop* _op, arg_dont_complain(char* vName), a
 	{
 	dspop_percentilesover* op = (dspop_percentilesover*) _op;
 	interval_table t = { pctrec_size (op->numPcts), answer_percentiles, put_percentiles, pct_line_max (op->numPcts), put_header, op, 0, 0, 0, 0 };
-	interval_table_run (_op->name, op->filename, op->outFilename, op->originOne, &t);
-	op->bases += t.bases;
+	interval_op_run (&op->head, &t);
 	}
 
-/* the driver: the signal is only read, 8 B per base of the intervals' summed length since the last call (the long
- * route reads an interval once per digit it needs: a lower bound there) */
-static void percentilesover_work (dspop* op, u64* bases, double* bytesPerBase)
-	{ *bases = ((dspop_percentilesover*) op)->bases;  ((dspop_percentilesover*) op)->bases = 0;  *bytesPerBase = 8; }
-
+/* (the work trait's 8 B per base: the long route reads an interval once per digit it needs, so a lower bound there) */
 OP_SHORT (op_percentilesover, "print the exact percentiles of the signal over each interval of a file (not in genodsp)")
 void   op_percentilesover_usage (char* name, FILE* f, char* indent) { percentilesover_usage (name, f, indent); }
 dspop* op_percentilesover_parse (char* name, int argc, char** argv) { return percentilesover_parse (name, argc, argv); }
@@ -194,6 +167,6 @@ static const dspinfo percentilesoverRows[] =
 	  dspinfoalias ("interval_percentiles"),
 	  dspinforecord("medianover", op_medianover), dspinfoalias ("median_over") };
 static const optraits percentilesoverTraits[] =
-	{ { op_percentilesover_apply, true, false, NULL, NULL, percentilesover_work },
-	  { op_medianover_apply,      true, false, NULL, NULL, percentilesover_work } };
+	{ { op_percentilesover_apply, true, false, NULL, NULL, interval_op_work },
+	  { op_medianover_apply,      true, false, NULL, NULL, interval_op_work } };
 const opgroup opgroup_percentilesover = OPGROUP (percentilesoverRows, percentilesoverTraits, NULL);

@@ -888,6 +888,7 @@ void gdsp_genome_regions_last (uint64_t out[4]);
 typedef struct gdsp_interval_stat  { uint64_t count;  double sum, mean, min, max;  uint32_t maxpos, image; } gdsp_interval_stat;
 typedef struct gdsp_interval_piece { double a0, a1, min, max;  uint32_t count, maxpos, flag, reserved; } gdsp_interval_piece;
 uint32_t gdsp_interval_stats_tile (void);
+int gdsp_interval_stats_set_launch_pieces (uint32_t pieces);       /* for tests: the most pieces of one launch (0: the default) */
 int gdsp_interval_stats       (const double* d_v, uint32_t n, const uint32_t* h_start, const uint32_t* h_end, uint32_t count,
                                double lo, double hi, gdsp_interval_stat* h_out, void* stream);
 int gdsp_interval_stats_batch (const gdsp_batch_item* items, int nitems, const uint32_t* h_vec, const uint32_t* h_start,

@@ -402,5 +402,48 @@ def test_flagged_pieces_beyond_the_first_tile_and_vector():
     assert p.stdout.strip().splitlines()[-1] == "%s %d" % (want, flagged)
 
 
+@pytest.mark.gpu
+def test_many_small_launches_give_the_same_figures():
+    """Three vectors in one call, the second a slice at offset 1 of its buffer, a few hundred intervals of one, two and
+    three pieces, unsorted; the first vector has huge cancelling values, so pieces over them are flagged.  At most three
+    pieces per launch: the figures are those of one launch, bit for bit, the flagged pieces' second sums among them."""
+    g = dev()
+    T = g.interval_stats_tile()
+    rng = np.random.default_rng(33)
+    ns = [2 * T + 300, T + 700, 3000]
+    xs = [rng.integers(0, 60, ns[0]).astype(np.float64), rng.integers(0, 60, ns[1] + 1).astype(np.float64),
+          rng.standard_normal(ns[2]) * 10.0]
+    a, b = T + 100, T + 400
+    xs[0][a:b:3], xs[0][a + 1:b:3], xs[0][a + 2:b:3] = 1e308, 1.0, -1e308
+    xs[0][2 * T:2 * T + 3] = -1e308, 8.0, 2.0 ** -200                        # a sum no two doubles hold: its piece is flagged
+    ds = [g.DeviceVector.from_numpy(x) for x in xs]
+    vecs = [ds[0], (ds[1], 1, ns[1]), ds[2]]
+    iv = [(0, T + 50, T + 500), (0, T + 100, T + 103), (0, T - 5, 2 * T + 5), (0, 0, ns[0]), (0, T - 1, T), (0, T, T + 1),
+          (0, 2 * T, 2 * T + 6),
+          (1, T - 3, T + 3), (1, 0, ns[1]), (1, T - 2, T - 1), (2, 0, ns[2]), (2, ns[2] - 1, ns[2])]
+    for _ in range(300):
+        k = int(rng.integers(0, 3))
+        s = int(rng.integers(0, ns[k] - 1))
+        iv.append((k, s, min(ns[k], s + 1 + int(rng.integers(0, 600)))))
+    order = rng.permutation(len(iv))
+    which, start, end = (np.array([iv[i][c] for i in order], np.uint32) for c in range(3))
+    got = g.interval_stats(vecs, start, end, vec=which)
+    whole = g.interval_stats_last()
+    assert whole["intervals"] == start.size and whole["pieces"] > start.size + 10 and whole["flagged"] >= 1
+    g.interval_stats_set_launch_pieces(3)
+    try:
+        small = g.interval_stats(vecs, start, end, vec=which)
+        split = g.interval_stats_last()
+    finally:
+        g.interval_stats_set_launch_pieces(0)
+    assert sorted(small) == sorted(got) and len(got) == 6
+    for name in got:
+        assert np.array_equal(small[name].view(np.uint64), got[name].view(np.uint64)), name
+    assert split["pieces"] == whole["pieces"] and split["intervals"] == start.size
+    assert split["flagged"] >= 1
+    with pytest.raises(g.GdspError):
+        g.interval_stats_set_launch_pieces((1 << 22) + 1)
+
+
 if __name__ == "__main__":
     print("%s %d" % flagged_beyond_the_first_tile())

@@ -111,6 +111,35 @@ def test_bad_arguments_are_refused_with_a_message():
     assert short <= 8192 and short & (short - 1) == 0 and piece >= short
 
 
+def test_every_interval_fault_of_the_batch_call_names_the_call_and_the_fault():
+    """one fault per call; each is refused before the device is touched"""
+    g = gd()
+    L = g.lib()
+    vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    count, values = np.zeros(2, np.uint32), np.zeros(2)
+    ok = np.array([50000], np.uint32)
+    u32 = lambda *a: np.array(a, np.uint32)
+
+    def table(*ptr_n):
+        items = (g.BatchItem * max(1, len(ptr_n)))()
+        for k, (ptr, n) in enumerate(ptr_n):
+            items[k].d_in, items[k].n = ptr, n
+        return items
+
+    two = table((0x10000, 100), (0x20000, 50))                           # never dereferenced: the arguments are refused first
+    for items, m, vec, start, end, text in (
+            (two, 2, u32(0, 1), None, u32(9, 9), "NULL interval arrays"),
+            (two, 2, u32(0, 1), u32(5, 5), None, "NULL interval arrays"),
+            (None, 2, u32(0, 1), u32(5, 5), u32(9, 9), "no vectors"),
+            (two, 0, u32(0, 1), u32(5, 5), u32(9, 9), "no vectors"),
+            (table((0x10000, 100), (0x20004, 50)), 2, u32(0, 1), u32(5, 5), u32(9, 9), "a vector must be 8-byte aligned"),
+            (two, 2, u32(0, 2), u32(5, 5), u32(9, 9), "an interval names a vector beyond the table"),
+            (two, 2, u32(0, 1), u32(5, 9), u32(9, 9), "an interval must have start < end"),
+            (two, 2, u32(0, 1), u32(5, 5), u32(9, 51), "an interval ends beyond its vector")):
+        rc = L.gdsp_interval_percentiles_batch(items, m, vp(vec), vp(start), vp(end), 2, vp(ok), 1, -DBL_MAX, DBL_MAX, vp(count), vp(values), None)
+        assert rc == 1 and L.gdsp_last_error().decode() == "gdsp_interval_percentiles_batch: " + text, (text, L.gdsp_last_error())
+
+
 # ------------------------------------------------------------------------------------------------ GPU ----
 
 @pytest.mark.gpu
