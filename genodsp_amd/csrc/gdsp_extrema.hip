@@ -11,9 +11,14 @@
 // is strictly greater" test: the centre itself never beats itself, NaN
 // neighbours never knock a value out and a NaN centre is never knocked out,
 // because E is formed with comparisons that ignore NaN exactly as `v[j] > val`
-// does.  All work is comparisons, so results are bit-identical to the
-// reference (ties between +0.0 and -0.0 in bestmin/bestmax excepted: the
-// reference's pick depends on its scan history).
+// does.  All work is comparisons, so localmin/localmax are bit-identical to
+// the reference on any input, and bestmin/bestmax on every window without NaN
+// (ties between +0.0 and -0.0 excepted: the reference's pick depends on its scan
+// history).  A window of nothing but NaN is NaN in the reference; one that mixes
+// NaN and numbers is the numbers' extreme or NaN, again by scan history.  Here E
+// ignores NaN, so a mixed window gives the numbers' extreme, and where E found no
+// number a NaN centre is written instead of the pad (ex_best).
+// tests/extrema_cases.py has the table, tests/test_hip_extrema_special.py runs it.
 //
 // HBM-bound (16 B/base).  A workgroup stages a tile plus its halo in LDS with
 // 16-byte loads.  Windows up to 4 bases are scanned directly from LDS (two
@@ -38,6 +43,14 @@ template <bool MAX> __device__ __forceinline__ bool ex_beats (double a, double b
 // extreme of two values with NaN never winning: v_max_f64 / v_min_f64 (IEEE maxNum/minNum)
 template <bool MAX> __device__ __forceinline__ double ex_pick (double a, double b)
 	{ return MAX? fmax (a, b) : fmin (a, b); }
+// bestmin/bestmax of a window in which pick found no number: what comes back is the pad, which is not in the input.
+// The reference answers NaN when every base of the window is NaN, and such a window holds its centre, so a NaN centre
+// is handed back; a window of nothing but -inf (+inf) has a centre that is a number and keeps its answer.
+__device__ __forceinline__ double ex_best (double e, double pad, const double* centre)
+	{
+	if (e == pad) { const double c = *centre;  if (c != c) e = c; }
+	return e;
+	}
 
 // Exclusive segmented scan of one (value, flag) pair per thread over the workgroup, with
 // `pick` as the operator: returns the extreme of the values of the threads before this one
@@ -108,6 +121,7 @@ void extrema_kernel (const double* __restrict__ in, double* __restrict__ out, ui
 				e0 = ex_beats<MAX> (e0, c0)? fill : c0;
 				e1 = ex_beats<MAX> (e1, c1)? fill : c1;
 				}
+			else { e0 = ex_best (e0, pad, x + o + lft);  e1 = ex_best (e1, pad, x + o + 1 + lft); }
 			int64_t g = tileStart + o;
 			if (g + 1 < (int64_t) n) gdsp_st2 (reinterpret_cast<double2*> (out + g), make_double2 (e0, e1));
 			else if (g < (int64_t) n) out[g] = e0;
@@ -177,6 +191,11 @@ void extrema_kernel (const double* __restrict__ in, double* __restrict__ out, ui
 			double c0 = in[g], c1 = (g + 1 < (int64_t) n)? in[g+1] : 0.0;
 			e0 = ex_beats<MAX> (e0, c0)? fill : c0;
 			e1 = ex_beats<MAX> (e1, c1)? fill : c1;
+			}
+		else
+			{
+			e0 = ex_best (e0, pad, in + g);
+			if (g + 1 < (int64_t) n) e1 = ex_best (e1, pad, in + g + 1);
 			}
 		if (g + 1 < (int64_t) n) gdsp_st2 (reinterpret_cast<double2*> (out + g), make_double2 (e0, e1));
 		else                     out[g] = e0;
@@ -269,6 +288,7 @@ void extrema_blocks_tile (const double* __restrict__ in, double* __restrict__ ou
 		for (int u=0 ; u<G ; u++) { run = ex_pick<MAX> (run, xb[u]);  P[u] = run; }
 		blockExt[0][p] = run;
 		}
+	const bool noFirst = (P[0] == pad);                            // the block's first element is NaN, outside the vector or the pad's own value
 	__syncthreads ();
 	// one level of the sparse table: entry q covers blocks q .. q + 2^level - 1
 	for (int l=1 ; l<=level ; l++)
@@ -308,6 +328,17 @@ void extrema_blocks_tile (const double* __restrict__ in, double* __restrict__ ou
 					}
 				if (SET != EXB_VALUES) e = (e != 0.0)? set.one : set.zero;
 				P[u] = e;
+				}
+			}
+		// bestmin/bestmax: a window in which pick found no number (ex_best).  Every window of this thread holds the first
+		// element of its block (a window is longer than a block), so one compare per thread rules all G of them out
+		if (!LOCAL && (SET == EXB_VALUES) && noFirst)
+			{
+#pragma unroll
+			for (int u=0 ; u<G ; u++)
+				{
+				const int c = G * p + u - rgt;                            // the centre, as in LOCAL
+				P[u] = ex_best (P[u], pad, lds + c + (c >> LOG_G));
 				}
 			}
 		}

@@ -99,6 +99,13 @@ void window_extreme_kernel (const double* __restrict__ in, const double* __restr
 			const double c = in[i];
 			e = (MAX? (e > c) : (e < c))? fill : c;
 			}
+		else if (e == (MAX? -INFINITY : INFINITY))
+			{
+			// no number in the window, the pad came back: the reference answers NaN when every base is NaN, and
+			// then the centre is one (ex_best in gdsp_extrema.hip); a window of nothing but the pad's value keeps it
+			const double c = in[i];
+			if (c != c) e = c;
+			}
 		out[i] = e;
 		}
 	}
