@@ -1447,6 +1447,58 @@ def interval_breadth_times():
     return dict(zip(("ms_cut", "ms_kernel", "ms_copy", "ms_combine"), [float(x) for x in ms]))
 
 
+# ---------------------------------------------------- correlateover (not in the reference) ----
+
+INTERVAL_CORR = np.dtype([("count", np.uint32), ("reserved", np.uint32), ("mean", np.float64), ("filemean", np.float64),
+                          ("stddev", np.float64), ("filestddev", np.float64), ("covariance", np.float64),
+                          ("correlation", np.float64), ("slope", np.float64), ("intercept", np.float64)])   # gdsp_interval_corr
+INTERVAL_CORR_FIGURES = ("count", "mean", "filemean", "stddev", "filestddev", "covariance", "correlation", "slope", "intercept")
+
+
+def interval_correlation_tile():
+    """The tile the kernel cuts intervals at (values of the 16-byte aligned frame the signal lies in)."""
+    return int(lib().gdsp_interval_correlation_tile())
+
+
+def interval_correlation_set_launch_pieces(pieces=0):
+    """The most pieces of one launch; 0: the default.  For tests."""
+    call("gdsp_interval_correlation_set_launch_pieces", int(pieces))
+
+
+def interval_correlation(x, y, start, end, lo=-DBL_MAX, hi=DBL_MAX, ylo=-DBL_MAX, yhi=DBL_MAX, stream=None, vec=None):
+    """correlate's figures of x against y over the intervals [start[i], end[i]) (gdsp_interval_correlation: the pair sample
+    inside each interval, lo <= x <= hi and ylo <= y <= yhi, never NaN or +-inf; every figure exact and rounded once or
+    derived from such; NaN where it is not defined).  -> dict of numpy arrays (INTERVAL_CORR_FIGURES) in the caller's
+    order.  x, y: a DeviceVector each, or a (vector, first, count) stretch of one; or LISTS of them of the same lengths
+    with vec[i] naming interval i's pair (gdsp_interval_correlation_batch).  Neither is written.  Waits."""
+    items, nvec, which, start, end = _interval_call(x, start, end, vec)
+    tracks = _read_only_items(y if isinstance(y, list) else [y])
+    assert nvec == (len(y) if isinstance(y, list) else 1)
+    for k in range(nvec):
+        assert items[k].n == tracks[k].n, "a track must be as long as its signal"
+        items[k].d_out = tracks[k].d_in
+    rec = np.zeros(start.size, INTERVAL_CORR)
+    call("gdsp_interval_correlation_batch", items, nvec, _vp(which), _vp(start), _vp(end), start.size, float(lo), float(hi),
+         float(ylo), float(yhi), _vp(rec), _sp(stream))
+    return {k: rec[k].copy() for k in INTERVAL_CORR_FIGURES}
+
+
+def interval_correlation_last():
+    """What the last interval_correlation did: intervals, pieces, and the pieces summed again through correlate's exact
+    pass after pass 1 and after pass 2."""
+    out = (C.c_uint64 * 4)()
+    lib().gdsp_interval_correlation_last(out)
+    return dict(zip(("intervals", "pieces", "flagged1", "flagged2"), [int(x) for x in out]))
+
+
+def interval_correlation_times():
+    """Where the last interval_correlation's time went, in ms: cutting, the kernels of both passes (HIP events), copies,
+    waiting and second sums, the means and combining."""
+    ms = (C.c_double * 4)()
+    lib().gdsp_interval_correlation_times(ms)
+    return dict(zip(("ms_cut", "ms_kernel", "ms_copy", "ms_combine"), [float(x) for x in ms]))
+
+
 # ------------------------------------------------------- segments (not in the reference) ----
 
 RUN_PIECE = np.dtype([("vec", np.uint32), ("start", np.uint32), ("end", np.uint32), ("reserved", np.uint32),

@@ -230,6 +230,12 @@ SIGNATURES = {
     "gdsp_interval_breadth_set_launch_pieces": (_int, [_u32]),
     "gdsp_interval_breadth_last": (None, [_vp]),
     "gdsp_interval_breadth_times": (None, [_vp]),
+    "gdsp_interval_correlation_tile": (_u32, []),
+    "gdsp_interval_correlation": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _f64, _f64, _f64, _f64, _vp, _vp]),
+    "gdsp_interval_correlation_batch": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _f64, _f64, _f64, _f64, _vp, _vp]),
+    "gdsp_interval_correlation_set_launch_pieces": (_int, [_u32]),
+    "gdsp_interval_correlation_last": (None, [_vp]),
+    "gdsp_interval_correlation_times": (None, [_vp]),
     # segments (not in the reference)
     "gdsp_segments_tile": (_u32, []),
     "gdsp_run_pieces_batch": (_int, [_vp, _int, _f64, _int, _vp, _vp, _vp]),

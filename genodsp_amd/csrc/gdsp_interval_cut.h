@@ -1,5 +1,5 @@
 // gdsp_interval_cut.h -- what the operators that reduce arbitrary intervals of a file piece by piece share
-// (gdsp_intervalstats.hip: statsover; gdsp_intervalbreadth.hip: breadthover): the refusals of a call (ic_check, which
+// (gdsp_intervalstats.hip: statsover; gdsp_intervalbreadth.hip: breadthover; gdsp_intervalcorr.hip: correlateover): the refusals of a call (ic_check, which
 // percentilesover takes too), the walk over a call's vectors a launch table at a time and over its intervals a launch at
 // a time, the cut of a launch's intervals into PIECES -- an interval intersected with a tile of IC_TILE values of the
 // 16-byte aligned frame its vector lies in --, their counting sort by tile (the caller's order kept inside a tile), the
@@ -258,10 +258,11 @@ struct IcBuffers
 // events), copying and waiting, combining; and the most pieces of a launch (set by tests; 0: IC_LAUNCH_PIECES)
 struct IcReport { uint64_t last[4];  double ms[4];  uint32_t launchPieces; };
 
-// a launch as the operator's hooks see it: its vectors and their table, its intervals sel[0 .. nsel), its cut
+// a launch as the operator's hooks see it: its vectors (vecs[k] is the caller's vector vecBase + k) and their table, its
+// intervals sel[0 .. nsel), its cut
 struct IcLaunch
 	{
-	const IcVector* vecs;  int nvec;  const uint32_t* sel;  uint32_t nsel;
+	const IcVector* vecs;  int nvec, vecBase;  const uint32_t* sel;  uint32_t nsel;
 	IcBatch B;  IcCut cut;  int dev;  hipStream_t s;
 	};
 
@@ -293,7 +294,7 @@ static inline int ic_run (const char* entry, const char* who, IcReport& rep, Buf
 		[&] (const IcVector* vecs, int nvec, int v0, uint32_t tiles, const uint32_t* sel, uint32_t nsel)
 			{
 			const GdspTimer tCut;
-			L.vecs = vecs;  L.nvec = nvec;  L.sel = sel;  L.nsel = nsel;
+			L.vecs = vecs;  L.nvec = nvec;  L.vecBase = v0;  L.sel = sel;  L.nsel = nsel;
 			rc = ic_cut (who, W.pieces, W.items, vecs, nvec, v0, tiles, sel, nsel, h_vec, h_start, h_end, L.cut);
 			if (rc == GDSP_OK) rc = W.out.grow ((size_t) L.cut.P * recs, who);
 			if (rc != GDSP_OK) return rc;

@@ -26,6 +26,7 @@
 #include "gdsp_common.h"
 #include "gdsp_xsum_dev.h"
 #include "gdsp_sample.h"
+#include "gdsp_corr_derive.h"
 
 #define XP_THREADS    256
 #define XP_UNROLL     4                               // 16-byte loads in flight per lane and stream
@@ -248,9 +249,6 @@ static int xp_genome_pass (int pass, const gdsp_xsum_pair* pairs, int npairs, co
 	                            onDevice, reduce, reduceCtx, img);
 	}
 
-// fl(a * b), never contracted into what follows
-static double xp_mul (double a, double b) { volatile double p = a * b;  return p; }
-
 extern "C" {
 
 int gdsp_genome_correlation_use_comm (gdsp_comm* comm) { xpComm = comm;  return GDSP_OK; }
@@ -280,26 +278,10 @@ int gdsp_genome_correlation (const gdsp_xsum_pair* pairs, int npairs, uint32_t w
 	rc = xp_genome_pass (2, pairs, npairs, xs.data (), window, lo, hi, ylo, yhi, meanx, meany, reduce, reduceCtx, img);
 	if (rc != GDSP_OK) return rc;
 	for (int k=0 ; k<3 ; k++) { xpLast[2] += img[k*XP_W + GDSP_XSUM_WORD_FLUSHES];  xpLast[3+k] = img[k*XP_W + GDSP_XSUM_WORD_INF]; }
-	const double varx = out[GDSP_CORR_VARX] = gdsp_xsum_div_round (img, n);                 // (+inf when some qxx was not finite)
-	const double vary = out[GDSP_CORR_VARY] = gdsp_xsum_div_round (img + XP_W, n);
-	const double sdx  = out[GDSP_CORR_SDX]  = sqrt (varx);
-	const double sdy  = out[GDSP_CORR_SDY]  = sqrt (vary);
-	const double cov  = out[GDSP_CORR_COV]  = (img[2*XP_W + GDSP_XSUM_WORD_INF] != 0)? NAN : gdsp_xsum_div_round (img + 2*XP_W, n);
-	const bool xok = (varx > 0) && (varx <= DBL_MAX), yok = (vary > 0) && (vary <= DBL_MAX), cok = !isnan (cov);
-	if (xok && yok && cok)
-		{
-		int ex, ey;
-		const double mx = frexp (sdx, &ex), my = frexp (sdy, &ey);
-		double r = ldexp (cov, -(ex + ey)) / xp_mul (mx, my);
-		if (r >  1.0) r =  1.0;
-		if (r < -1.0) r = -1.0;
-		out[GDSP_CORR_CORRELATION] = r;
-		}
-	if (xok && cok)
-		{
-		const double slope = out[GDSP_CORR_SLOPE] = cov / varx;
-		out[GDSP_CORR_INTERCEPT] = meany - xp_mul (slope, meanx);
-		}
+	out[GDSP_CORR_VARX] = gdsp_xsum_div_round (img, n);                                       // (+inf when some qxx was not finite)
+	out[GDSP_CORR_VARY] = gdsp_xsum_div_round (img + XP_W, n);
+	out[GDSP_CORR_COV]  = (img[2*XP_W + GDSP_XSUM_WORD_INF] != 0)? NAN : gdsp_xsum_div_round (img + 2*XP_W, n);
+	gdsp_corr_derive (out);
 	return GDSP_OK;
 	}
 

@@ -123,11 +123,12 @@ extern const opgroup opgroup_fillgaps   __attribute__((weak));      /* the signa
 extern const opgroup opgroup_percentilesover __attribute__((weak)); /* median and percentiles of the signal over the intervals of a file */
 extern const opgroup opgroup_breadthover __attribute__((weak));     /* the bases at or above each threshold over the intervals of a file */
 extern const opgroup opgroup_regionsover __attribute__((weak));     /* each region of a file scaled to the same columns, row by row */
+extern const opgroup opgroup_correlateover __attribute__((weak));   /* the signal against a second track over the intervals of a file */
 static const opgroup* const opGroups[] =
 	{ &opgroup_rankfilt, &opgroup_stats, &opgroup_statsover, &opgroup_histogram, &opgroup_correlate, &opgroup_lagcorr,
 	  &opgroup_segments, &opgroup_prominence, &opgroup_localstats, &opgroup_distance, &opgroup_profileover,
 	  &opgroup_localcorrelate, &opgroup_matrixover, &opgroup_localmad, &opgroup_fillgaps, &opgroup_percentilesover,
-	  &opgroup_breadthover, &opgroup_regionsover };
+	  &opgroup_breadthover, &opgroup_regionsover, &opgroup_correlateover };
 #define numOpGroups ((int) (sizeof(opGroups)/sizeof(opGroups[0])))
 
 #ifdef GDSP_EXTRA_DSPTABLE_ROWS

@@ -197,7 +197,7 @@ void  segments_run             (dspop* op, segments_opts* o, int wantTable, cons
 int   ib_chromosomes      (void);
 u32   ib_pending_of       (int ci, spec** s, u32** start, u32** end, valtype** val);
 char* put_value_fixed     (char* p, valtype v, int precision);
-/* what statsover, percentilesover and breadthover share (ops_common.c): a table with one line per interval of a file, in file order --
+/* what statsover, percentilesover, breadthover and correlateover share (ops_common.c): a table with one line per interval of a file, in file order --
  * chromosome, start and end as the file has them, then the operator's figures.  The file is read like mask's (read_interval
  * without a value column, place_interval), the intervals may overlap and come in any order; they are buffered with ib_add
  * and every ib_batch_limit() of them, and at the end of the file, each device answers those on its chromosomes in one call
@@ -205,7 +205,8 @@ char* put_value_fixed     (char* p, valtype v, int precision);
 typedef struct interval_table
 	{
 	size_t recSize;                               /* bytes of what is kept of an interval until its line is written */
-	/* one device's share, that device selected: record i of `out` for interval i, [start[i], end[i]) of items[vec[i]] */
+	/* one device's share, that device selected: record i of `out` for interval i, [start[i], end[i]) of items[vec[i]]
+	 * (d_in a chromosome's vector, d_out NULL: an operator with a second track names it there, as correlateover does) */
 	void (*answer) (void* ctx, gdsp_batch_item* items, int m, u32* vec, u32* start, u32* end, u32 k, void* out);
 	/* a line behind its end column, from its record, newline included, at p; -> behind what was written */
 	char* (*put) (void* ctx, char* p, const void* rec, spec* s);

@@ -499,7 +499,7 @@ void row_table_report (char* rowsName, u64 numUsed, u64 cells, int quiet)
 	if (!quiet) fprintf (stderr, "%s is %llu, cells is %llu\n", rowsName, (unsigned long long) numUsed, (unsigned long long) cells);
 	}
 
-/* ----------------------- a table with one line per interval of a file (statsover, percentilesover, breadthover) ---- */
+/* -------- a table with one line per interval of a file (statsover, percentilesover, breadthover, correlateover) ---- */
 /* a kept interval as its line names it; its record arrives in rec under the same serial number */
 typedef struct itrow { spec* s;  u32 fileStart, fileEnd; } itrow;
 

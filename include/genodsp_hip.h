@@ -975,6 +975,45 @@ int  gdsp_interval_breadth_set_launch_pieces (uint32_t pieces);
 void gdsp_interval_breadth_last  (uint64_t out[4]);
 void gdsp_interval_breadth_times (double ms[4]);
 
+/* ---- correlateover (not in the reference): correlate's figures of the signal against a second track, per interval ----
+ * For a vector x of n doubles, a second track y of the same length, an interval [s, e) with 0 <= s < e <= n and limits
+ * lo, hi, ylo, yhi, the interval's pair sample is correlate's, without a window: the bases i in [s, e) with
+ *   !(x[i] < lo) && !(x[i] > hi), x[i] finite, !(y[i] < ylo) && !(y[i] > yhi), y[i] finite.
+ * The interval's record is what gdsp_genome_correlation gives for that sample (the definitions are there and are not
+ * reworded): count; mean and filemean, the exact sums of x and of y over the count, each rounded once; then with
+ * dx = fl(x - mean), dy = fl(y - filemean) the products fl(dx dx), fl(dy dy), fl(dx dy), each summed exactly and divided
+ * once by the count -- a product that is not finite makes its variance +inf, the covariance NaN --; stddev and filestddev
+ * the square roots of the two variances; covariance; correlation, slope and intercept derived operation by operation as
+ * correlate derives them.  An empty sample has count 0 and NaN in every other figure; a figure that is not defined is
+ * NaN.  An interval [0, n) has, bit for bit, gdsp_genome_correlation's figures of the one pair (x, y) with window 1.
+ * Intervals may overlap, repeat and come in any order.  Every figure is a function of the interval's sample alone: nothing
+ * depends on tiles, grid, the split into launches, dispatch order, the order of the intervals or how they overlap, or
+ * devices.
+ *
+ * The conventions are gdsp_interval_breadth[_batch]'s: HOST arrays in, h_out[i] for interval i in the caller's order, the
+ * vectors read on the current device and never written, the call waits for the device.  items[k].d_in is the signal and
+ * items[k].d_out the second track of the same length, READ ONLY here (gdsp_localcorr_batch's way of naming two vectors).
+ * Both are 8-byte aligned and the track's 16-byte alignment may differ from the signal's.  GDSP_EINVAL before the device
+ * is touched for what gdsp_interval_breadth_batch refuses and for a track that is NULL or not 8-byte aligned; count == 0
+ * is a no-op.  The device reduces statsover's pieces in two passes, sums and then products around the interval's means,
+ * to two-term expansions that the host combines exactly; a piece whose expansion did not hold its sum is summed again
+ * through correlate's exact pass (gdsp_intervalcorr.hip).  gdsp_interval_correlation_set_launch_pieces sets the most
+ * pieces of one launch (0: the default) so that a test can force several launches. */
+typedef struct gdsp_interval_corr
+	{ uint32_t count, reserved;  double mean, filemean, stddev, filestddev, covariance, correlation, slope, intercept; } gdsp_interval_corr;
+uint32_t gdsp_interval_correlation_tile (void);
+int gdsp_interval_correlation       (const double* d_x, const double* d_y, uint32_t n, const uint32_t* h_start, const uint32_t* h_end,
+                                     uint32_t count, double lo, double hi, double ylo, double yhi, gdsp_interval_corr* h_out, void* stream);
+int gdsp_interval_correlation_batch (const gdsp_batch_item* items, int nitems, const uint32_t* h_vec, const uint32_t* h_start,
+                                     const uint32_t* h_end, uint32_t count, double lo, double hi, double ylo, double yhi,
+                                     gdsp_interval_corr* h_out, void* stream);
+int  gdsp_interval_correlation_set_launch_pieces (uint32_t pieces);
+/* what the last gdsp_interval_correlation[_batch] did: [0] intervals, [1] pieces, [2] pieces summed again after pass 1,
+ * [3] after pass 2; and where its time went, in ms: [0] cutting the intervals into pieces (host), [1] the kernels of both
+ * passes (HIP events), [2] copies, waiting and the second sums, [3] the means and combining the pieces (host) */
+void gdsp_interval_correlation_last  (uint64_t out[4]);
+void gdsp_interval_correlation_times (double ms[4]);
+
 /* ---- segments (not in the reference): the signal's own thresholded regions, each with statsover's figures, exact ------
  * For a vector v of n doubles, a threshold T and tiesAbove:
  *   member   base i is a member iff v[i] > T, or v[i] >= T with ties above: binarize's test.  A NaN is never a member
